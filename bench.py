@@ -14,6 +14,11 @@ SST write-back), i.e. the loop of the reference's own harness scripts/benchmark_
 
 Prints ONE JSON line (rank 0).  No PyTorch anywhere: ranks rendezvous through the filesystem
 (single node) and synchronise / reduce through RCCL inside libqingdai_hip.so.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`).  `--full` adds what
+takes measurements of its own: HIP-event kernel timing inside the timed region (`roofline`, `roofline_ocean_substep`), the copy
+ceiling, the committed profile's traffic, the collective counts of a banded run, the ecology leg and the CPU baseline.
+`--dump-outputs DIR` writes the fields the last timed step left on the device (dump_outputs).
 """
 import argparse
 import json
@@ -261,6 +266,30 @@ def find_profile(nlat, nlon):
     return best
 
 
+def dump_outputs(dev, out_dir, with_ocean, with_phys, budget_bytes=64_000_000):
+    """--dump-outputs: the fields a caller of the timed loop reads after its last step -- the prognostic state, and the diagnostics
+    the driver couples to -- as <out_dir>/<FIELD>.npy in float64.  When the whole fields would exceed `budget_bytes` in all, every
+    field is cut to the same fixed sample of cells (np.random.default_rng(0) over the flat index, sorted), whose indices go to
+    sample_cells.npy; the inputs are the seed-42 planet, so two builds run with the same arguments can be compared file for file."""
+    names = ["U", "V", "H", "TS", "Q", "CLOUD", "HICE", "ALBEDO", "OLR"]
+    names += ["PRECIP"] if with_phys else []
+    names += ["UO", "VO", "ETA", "SST", "QNET"] if with_ocean else []
+    ncell = dev.shape[0] * dev.shape[1]
+    header = 256                                              # per .npy file, an upper bound
+    cells = None
+    if len(names) * (ncell * 8 + header) > budget_bytes:
+        n = (budget_bytes - (len(names) + 1) * header) // ((len(names) + 1) * 8)
+        cells = np.sort(np.random.default_rng(0).choice(ncell, size=n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    if cells is not None:
+        np.save(os.path.join(out_dir, "sample_cells.npy"), cells.astype(np.float64))
+    for k in names:
+        dev._host.pop(k, None)
+        a = np.array(dev.get(k), dtype=np.float64)
+        dev._host.pop(k, None)
+        np.save(os.path.join(out_dir, k + ".npy"), a if cells is None else a.reshape(-1)[cells])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -281,7 +310,19 @@ def main():
                     help="(test hook) every rank prints its launcher environment and exits before loading the library")
     ap.add_argument("--profile-kernel", default="k_dyn_hyper",
                     help="kernel whose HIP-event time feeds `roofline` (k_dyn_hyper: the fused dynamics + del^4 kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the HIP-event kernel timing inside the timed region "
+                         "and the roofline figures, the copy ceiling, the committed profile's traffic, the collective counts of a "
+                         "banded run, the ecology leg and the CPU baseline (the options above that tune these act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the fields the last timed step left on the device as DIR/<FIELD>.npy (float64); "
+                         "when they would exceed 64 MB in all, the same seeded sample of cells of each (flat indices in "
+                         "DIR/sample_cells.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("QD_BENCH_SELF_RING", "0")) > 1):
+        ap.error("--dump-outputs needs the whole globe on one handle (--gpus 1, no QD_BENCH_SELF_RING)")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -343,21 +384,22 @@ def main():
         dev.step_n(stars_w, dt, with_ocean=with_ocean, with_physics=with_phys, pass_albedo=True)
     barrier()
     comm0 = (0, 0, 0)
-    if banded:
+    if banded and args.full:
         import ctypes as _ct
         ne, na, nh = _ct.c_int(0), _ct.c_int(0), _ct.c_int(0)
         dev.lib.qd_comm_stats(dev.h, _ct.byref(ne)); dev.lib.qd_comm_allreduce_count(dev.h, _ct.byref(na))
         dev.lib.qd_comm_host_allreduce_count(dev.h, _ct.byref(nh))
         comm0 = (ne.value, na.value, nh.value)
     also = "k_ocn_hyper" if (with_ocean and args.profile_kernel != "k_ocn_hyper") else None
-    # HIP events inside the timed region, on the handle's stream, SAMPLED.  The two profiled kernels are single launches whose start /
-    # stop events ride on the dispatch itself (hipExtLaunchKernelGGL: the timestamps of the dispatch's completion signal, the interval
-    # the rocprofv3 kernel trace reports); a timed dispatch still idles the stream for a few us (kernel trace, profiles/README.md: 14
-    # timed launches a step were 7 % of the step), so the per-step kernel is timed on ~16 steps of the K and the per-sub-step kernel
-    # on every 16th launch (about one a step).
-    s_main = max(1, K // 16) if args.timing_stride < 0 else max(1, args.timing_stride)
-    s_also = 16 if args.timing_stride < 0 else max(1, args.timing_stride)
-    dev.timing(select=f"{args.profile_kernel}:{s_main}" + (f",{also}:{s_also}" if also else ""))
+    if args.full:
+        # HIP events inside the timed region, on the handle's stream, SAMPLED.  The two profiled kernels are single launches whose start /
+        # stop events ride on the dispatch itself (hipExtLaunchKernelGGL: the timestamps of the dispatch's completion signal, the interval
+        # the rocprofv3 kernel trace reports); a timed dispatch still idles the stream for a few us (kernel trace, profiles/README.md: 14
+        # timed launches a step were 7 % of the step), so the per-step kernel is timed on ~16 steps of the K and the per-sub-step kernel
+        # on every 16th launch (about one a step).
+        s_main = max(1, K // 16) if args.timing_stride < 0 else max(1, args.timing_stride)
+        s_also = 16 if args.timing_stride < 0 else max(1, args.timing_stride)
+        dev.timing(select=f"{args.profile_kernel}:{s_main}" + (f",{also}:{s_also}" if also else ""))
     t0 = time.perf_counter()
     dev.step_n(stars_k, dt, with_ocean=with_ocean, with_physics=with_phys, pass_albedo=True)
     barrier()
@@ -367,8 +409,10 @@ def main():
         v = (ctypes.c_double * 1)(el)
         dev._chk(dev.lib.qd_comm_allreduce_max(dev.h, v, 1), "qd_comm_allreduce_max")
         el = v[0]
+    if args.dump_outputs:
+        dump_outputs(dev, args.dump_outputs, with_ocean, with_phys)
     comm = None
-    if banded:                                     # collectives this rank issued inside the timed region, per step
+    if banded and args.full:                       # collectives this rank issued inside the timed region, per step
         import ctypes as _ct
         ne, na, nh = _ct.c_int(0), _ct.c_int(0), _ct.c_int(0)
         dev.lib.qd_comm_stats(dev.h, _ct.byref(ne)); dev.lib.qd_comm_allreduce_count(dev.h, _ct.byref(na))
@@ -393,7 +437,7 @@ def main():
         else:
             comm["collective_launches_per_step"] = comm["halo_exchanges_per_step"] + comm["rccl_allreduces_per_step"] - ng.value / max(1, K + W)
     end_state = None
-    if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
         # what the CPU baseline continues from (downloaded AFTER the timed region; the ecology leg below runs on)
         names = ["U", "V", "H", "TS", "Q", "CLOUD", "HICE"] + (["UO", "VO", "ETA", "SST"] if with_ocean else [])
         end_state = {}
@@ -401,15 +445,9 @@ def main():
             dev._host.pop(k, None)
             end_state[k] = np.array(dev.get(k), dtype=float)
             dev._host.pop(k, None)
-    kern_ms, kern_n = dev.timing_get(args.profile_kernel)
-    also_ms, also_n = dev.timing_get(also) if also else (0.0, 0)
-    dev.timing(on=False)
 
     ms_per_step = el / K * 1e3
     value = (K * dt / PLANET_DAY_S) / el
-    cells = (band[1] if band else args.nlat) * args.nlon     # cells one launch of this rank's kernel covers
-    bpc = BYTES_PER_CELL.get(args.profile_kernel, 0.0)
-    achieved = (bpc * cells / 1e9) / (kern_ms / 1e3) if kern_ms > 0 else 0.0
     out = {
         "metric": f"simulated planet-days/sec at {args.nlat}x{args.nlon} f64", "value": value, "unit": "planet-days/s",
         "n_gpus": args.gpus, "steps": K, "warmup": W, "ms_per_step": ms_per_step,
@@ -420,14 +458,25 @@ def main():
                                " (BASELINE configs[2]; loop order of benchmark_jax.py:124-158)",
                    "grid": [args.nlat, args.nlon], "dt_s": dt, "ocean_n_sub": dev.last_ocean_nsub() if with_ocean else 0,
                    "parallelism": f"lat-bands x{args.gpus}"},
-        "roofline": {"bound": "hbm", "kernel": args.profile_kernel, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                     "bytes_per_cell": bpc, "cells": cells, "avg_kernel_ms": kern_ms, "launches": kern_n},
     }
+    if args.full:
+        kern_ms, kern_n = dev.timing_get(args.profile_kernel)
+        also_ms, also_n = dev.timing_get(also) if also else (0.0, 0)
+        dev.timing(on=False)
+        cells = (band[1] if band else args.nlat) * args.nlon     # cells one launch of this rank's kernel covers
+        bpc = BYTES_PER_CELL.get(args.profile_kernel, 0.0)
+        achieved = (bpc * cells / 1e9) / (kern_ms / 1e3) if kern_ms > 0 else 0.0
+        out["roofline"] = {"bound": "hbm", "kernel": args.profile_kernel, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                           "bytes_per_cell": bpc, "cells": cells, "avg_kernel_ms": kern_ms, "launches": kern_n}
     if comm:
         out["config"]["collectives"] = comm
     if ring > 1:
         out["rehearsal"] = f"self-ring: ONE band of {ring} on one GPU, halos refreshed from the band itself -- not a benchmark result"
+    if not args.full:                 # a plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(out))
+        return
     if also and also_ms > 0:     # the kernel with the largest share of the step (ocean sub-steps), same accounting
         a2 = (BYTES_PER_CELL[also] * cells / 1e9) / (also_ms / 1e3)
         out["roofline_ocean_substep"] = {"bound": "hbm", "kernel": also, "achieved": a2, "peak": HBM_PEAK_GBS, "unit": "GB/s",

@@ -3,7 +3,7 @@
 out=$1; shift
 mkdir -p $out
 one() { tag=$1; lib=$2
-  env QD_LIB_PATH=$lib timeout -k 10 300 python bench.py --steps 120 --warmup 24 --no-cpu-baseline --no-ecology-leg --profile-kernel ocean_tail > $out/$tag.json 2>$out/$tag.err || { echo "$tag FAILED"; return; }
+  env QD_LIB_PATH=$lib timeout -k 10 300 python bench.py --full --steps 120 --warmup 24 --no-cpu-baseline --no-ecology-leg --profile-kernel ocean_tail > $out/$tag.json 2>$out/$tag.err || { echo "$tag FAILED"; return; }
   python - <<PY
 import json
 j=json.loads(open("$out/$tag.json").read().strip().splitlines()[-1]); print("$tag", round(j["ms_per_step"],4), j["config"]["ocean_n_sub"], "tail us", round(j["roofline"]["avg_kernel_ms"]*1e3,2), "k_ocn_stream us", round(j["roofline_ocean_substep"]["avg_kernel_ms"]*1e3,2))

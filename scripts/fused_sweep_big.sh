@@ -3,7 +3,7 @@
 out=$1; shift
 mkdir -p $out
 one() { tag=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --nlat 1441 --nlon 2880 --steps 24 --warmup 6 --no-cpu-baseline --no-ecology-leg --profile-kernel ocean_step > $out/$tag.json 2>$out/$tag.err || { echo "$tag FAILED"; return; }
+  env "$@" timeout -k 10 300 python bench.py --full --nlat 1441 --nlon 2880 --steps 24 --warmup 6 --no-cpu-baseline --no-ecology-leg --profile-kernel ocean_step > $out/$tag.json 2>$out/$tag.err || { echo "$tag FAILED"; return; }
   python - <<PY
 import json
 j=json.loads(open("$out/$tag.json").read().strip().splitlines()[-1]); print("$tag", round(j["ms_per_step"],4), j["config"]["ocean_n_sub"], "ocean_step kernel us", round(j["roofline"]["avg_kernel_ms"]*1e3,2))

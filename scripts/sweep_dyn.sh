@@ -1,7 +1,7 @@
 #!/bin/bash
 # strip-height sweep of the momentum kernels in the 240-step bench:  bash scripts/sweep_dyn.sh [nlat nlon "extra bench args"]
 set -e
-NLAT=${1:-721}; NLON=${2:-1440}; EXTRA=${3:-}
+NLAT=${1:-721}; NLON=${2:-1440}; EXTRA="--full ${3:-}"     # --full: the roofline figures read below
 run() { lab=$1; shift
   env "$@" timeout -k 10 250 python bench.py --no-cpu-baseline --no-ecology-leg --nlat $NLAT --nlon $NLON $EXTRA > gpurun_out/sd_$lab.json 2> gpurun_out/sd_$lab.err
   python - <<PY
