@@ -152,7 +152,7 @@ int qd_driver_physics(qd_handle h, double dt);
 int qd_hydrology_commit(qd_handle h, double dt);
 /* benchmark_jax.py:124-158 as one resident loop of n steps: forcing -> albedo -> time_step [-> ocean
  * coupling] [-> hydrology commit].  flags bit0 = with_ocean, bit1 = with_driver_physics (else the simple
- * ocean/land albedo of benchmark_jax.py:129), bit2 = pass albedo to time_step, bit3 = hydrology commit, bit4 = energy diagnostics on the first step (qd_energy_diagnostics_last), bit5 = ecology sub-step (qd_eco_substep, and qd_indiv_substep when a pool is configured; needs bit1), bit6 = tracer transport after the ocean step (qd_phyto_advect_diffuse; needs bit0 and qd_phyto_configure).  `stars` holds n rows of 7 host scalars
+ * ocean/land albedo of benchmark_jax.py:129), bit2 = pass albedo to time_step, bit3 = hydrology commit, bit4 = energy diagnostics on the first step (qd_energy_diagnostics_last), bit5 = ecology sub-step (qd_eco_substep, and qd_indiv_substep when a pool is configured; needs bit1), bit6 = tracer transport after the ocean step (qd_phyto_advect_diffuse; needs bit0 and qd_phyto_configure), bit7 = river routing after the hydrology commit (qd_route_accumulate, and qd_route_event on the steps a qd_route_schedule of n entries names; needs bit3 and qd_route_configure).  `stars` holds n rows of 7 host scalars
  * (flux_A, decl_A, ra_A, flux_B, decl_B, ra_B, theta), evaluated by the caller as forcing.py:85-125 does. */
 int qd_step_n(qd_handle h, int n, double dt, int flags, const double* stars);
 int qd_last_ocean_nsub(qd_handle h, int* n_sub);
@@ -244,6 +244,38 @@ int qd_phyto_configure(qd_handle h, int n_species, double K_h, double adv_alpha)
 int qd_phyto_upload(qd_handle h, int species, const double* host);      /* [n_lat][n_lon] f64 */
 int qd_phyto_download(qd_handle h, int species, double* host);
 int qd_phyto_advect_diffuse(qd_handle h, double dt_seconds);             /* all species, three launches */
+
+/* ---- river routing (P014, pygcm/routing.py), whole-globe handles ----------------------------------
+ * The host plans the network once (qingdai_amd/routing.py: build_plan): per cell a target code (>= 0 a live edge to that
+ * cell; -1 ocean, -2 void, -3 residual, -4 never processed, -5 - k lake storage k) and the reference's sequential loop cut into
+ * segments ordered by junction level.  The buffer accumulates RUNOFF every step; an event routes it with at most seven launches,
+ * fills the flow map and appends one record of QD_ROUTE_LOG_W = 8 doubles to a device event log:
+ * {step, event_dt, ocean_inflow_kgps, mass_closure_error_kg, mass_input_kg, ocean_kg, residual_kg, lake_delta_kg}. */
+typedef struct qd_route_plan {
+    int32_t n_cells;                    /* n_lat * n_lon */
+    int32_t n_seg, n_seg_cells, n_levels, n_jp, n_lakes;
+    int32_t pe_lakes;                   /* 1: the lake P - E update runs on events that come with P and E */
+    int32_t reserved;
+    const uint8_t* cflags;              /* [n_cells] bit0 network land, bit1 lake cell of the P - E update */
+    const double* area_row;             /* [n_lat] cell area per row (m^2) */
+    const int32_t* code;                /* [n_cells] */
+    const int32_t* seg_start;           /* [n_seg + 1] into seg_cells */
+    const int32_t* seg_cells;           /* [n_seg_cells] head first */
+    const int32_t* level_start;         /* [n_levels + 1] into the segments */
+    const int32_t* jp_start;            /* [n_seg + 1] into jp_cells */
+    const int32_t* jp_cells;            /* [n_jp] live predecessors of each head, in flow_order position */
+    const int32_t* lake_start;          /* [n_lakes + 1] into lake_cells */
+    const int32_t* lake_cells;          /* cells that drain into each lake storage, in flow_order position */
+    const double* lake_frac;            /* [n_lakes] lake-area fraction of the P - E update */
+} qd_route_plan;
+int qd_route_configure(qd_handle h, const qd_route_plan* plan, size_t plan_bytes);   /* uploads the plan; zeroes the state */
+int qd_route_free(qd_handle h);
+int qd_route_reset(qd_handle h);                             /* buffer, flow map, lake volumes, log and step count to zero */
+int qd_route_accumulate(qd_handle h, double dt);             /* buffer += where(land, (RUNOFF * area) * dt, 0) */
+int qd_route_event(qd_handle h, double event_dt, int with_pe);   /* route the buffer (P, E: the PRECIP / EFLUX fields) */
+int qd_route_schedule(qd_handle h, int n, const double* event_dt);   /* the next qd_step_n span: event_dt per step, 0 = none */
+int qd_route_download(qd_handle h, int which, double* host, size_t n);   /* 0 flow map kg/s [n_cells], 1 lake volumes [n_lakes], 2 buffer */
+int qd_route_events(qd_handle h, double* out, int max, int* n);   /* drains the event log: *n records of 8 doubles */
 
 /* ---- reductions for diagnostics (energy.py:494-538, ocean.py:535-561) -------------- */
 /* compute_energy_diagnostics (energy.py:494-538) from the resident state, with the flux formulas of the driver's

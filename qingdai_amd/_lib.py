@@ -40,6 +40,8 @@ SYMBOLS = [
     "qd_eco_configure", "qd_eco_set_lai_layers", "qd_eco_substep", "qd_eco_banded_alpha", "qd_eco_get_state", "qd_eco_set_state",
     "qd_indiv_configure", "qd_indiv_substep", "qd_indiv_download", "qd_indiv_upload",
     "qd_phyto_configure", "qd_phyto_upload", "qd_phyto_download", "qd_phyto_advect_diffuse",
+    "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
+    "qd_route_download", "qd_route_events",
     "qd_copy_ceiling", "qd_timing_enable", "qd_timing_select", "qd_timing_get", "qd_timing_reset",
 ]
 
@@ -49,6 +51,16 @@ class qd_eco_params(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_double) for n in ("k_canopy", "leaf_scalar", "soil_ref", "w_lai", "light_update_hours",
                                                  "recompute_lai_delta")] +
                 [(n, ctypes.c_int32) for n in ("substep_every_nphys", "albedo_couple", "bands_couple", "water_couple", "use_lai", "map_f32")])
+
+
+class qd_route_plan(ctypes.Structure):
+    """include/qingdai_hip.h: qd_route_plan"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("n_cells", "n_seg", "n_seg_cells", "n_levels", "n_jp", "n_lakes", "pe_lakes",
+                                                "reserved")] +
+                [("cflags", ctypes.c_void_p), ("area_row", ctypes.c_void_p), ("code", ctypes.c_void_p),
+                 ("seg_start", ctypes.c_void_p), ("seg_cells", ctypes.c_void_p), ("level_start", ctypes.c_void_p),
+                 ("jp_start", ctypes.c_void_p), ("jp_cells", ctypes.c_void_p), ("lake_start", ctypes.c_void_p),
+                 ("lake_cells", ctypes.c_void_p), ("lake_frac", ctypes.c_void_p)])
 
 
 class qd_grid_desc(ctypes.Structure):
@@ -152,6 +164,14 @@ def load():
     lib.qd_plansim_segments.argtypes = [vp, i32, ip]
     lib.qd_plansim_pop_exchange.argtypes = [vp, ip, i32, ip]
     lib.qd_plansim_segments_rows.argtypes = [vp, i32, i32, ip]
+    lib.qd_route_configure.argtypes = [vp, ctypes.POINTER(qd_route_plan), sz]
+    lib.qd_route_free.argtypes = [vp]
+    lib.qd_route_reset.argtypes = [vp]
+    lib.qd_route_accumulate.argtypes = [vp, dbl]
+    lib.qd_route_event.argtypes = [vp, dbl, i32]
+    lib.qd_route_schedule.argtypes = [vp, i32, dp]
+    lib.qd_route_download.argtypes = [vp, i32, dp, sz]
+    lib.qd_route_events.argtypes = [vp, dp, i32, ip]
     lib.qd_timing_enable.argtypes = [vp, i32]
     lib.qd_timing_select.argtypes = [vp, ctypes.c_char_p]
     lib.qd_timing_get.argtypes = [vp, ctypes.c_char_p, dp, ctypes.POINTER(i64)]

@@ -470,6 +470,7 @@ extern "C" int qd_destroy(qd_handle c) {
                         h[16 * s + 5], h[16 * s + 6], h[16 * s + 7], h[16 * s + 13], h[16 * s + 14], h[16 * s + 15]);
     }
     qd_phyto_release(c);
+    qd_route_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -683,6 +684,11 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     if (with_phyto && c->phyto.S == 0) return qd_fail(c, "qd_step_n: bit6 set but qd_phyto_configure has not been called");
     if (with_eco && !with_phys) return qd_fail(c, "qd_step_n: the ecology sub-step (bit5) needs the driver physics (bit1)");
     if (with_eco && !c->eco.configured) return qd_fail(c, "qd_step_n: bit5 set but qd_eco_configure has not been called");
+    const int with_route = flags & 128;
+    if (with_route && !with_hydro) return qd_fail(c, "qd_step_n: river routing (bit7) needs the hydrology commit (bit3)");
+    if (with_route && qd_route_span_check(c, n)) return -1;
+    // the schedule is for this span only, whatever way it ends
+    struct RouteGuard { qd_ctx* c; int on; ~RouteGuard() { if (on) qd_route_span_done(c); } } route_guard{c, with_route};
     // whatever way this call ends, the per-span switches are back to what a stand-alone qd_* call expects
     struct SpanGuard { qd_ctx* c; ~SpanGuard() { c->diag_write = 1; c->want_pcond_ahead = 0; c->pcond_ahead = 0; c->defer_final = 0; c->final_pending.on = 0; qd_saf_drop(c); } } span_guard{c};
     for (int s = 0; s < n; ++s) {
@@ -719,13 +725,15 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // The precipitation block of step s + 1 (run_simulation.py:1740-1790) reads u, v and P_cond as time_step left them and
         // nothing the ocean step, the tracers, the individuals or the bucket touch, and writes only what the rest of step s + 1's
         // driver physics reads: it is queued inside the ocean step, between the stress kernel and the host's wait for the CFL maxima.
-        if (with_ocean && with_phys && c->geo.full && c->hoist_precip && s + 1 < n)
+        // (not on a routing event step: the event reads this step's PRECIP, which the hoisted block would overwrite)
+        if (with_ocean && with_phys && c->geo.full && c->hoist_precip && s + 1 < n && !(with_route && qd_route_is_event(c, s)))
             c->before_cfl_wait = [c, dt]() { const int r = qd_driver_physics_impl(c, dt, nullptr, 1); if (!r) c->precip_done = 1; return r; };
         if (with_ocean) { rc = qd_ocean_step_impl(c, dt, 1, 1, 1); c->before_cfl_wait = nullptr; if (rc) return rc; }
         if (with_phyto && (rc = qd_phyto_step_impl(c, dt))) return rc;      // run_simulation.py:2254-2258
         // IndividualPool.try_substep reads this step's isr_A / isr_B and W_land before the bucket update (run_simulation.py:2021-2046)
         if (with_eco && c->eco.n_indiv > 0 && (rc = qd_indiv_substep_impl(c, dt, nullptr))) return rc;
         if (with_hydro && (rc = qd_hydrology_commit_impl(c, dt))) return rc;
+        if (with_route && (rc = qd_route_step_impl(c, dt, s))) return rc;           // run_simulation.py:2342-2348
     }
     c->diag_write = 1;
     hipError_t e = hipGetLastError();

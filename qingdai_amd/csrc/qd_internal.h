@@ -203,6 +203,7 @@ struct qd_ctx {
     int has_elevation = 0;           // an ELEVATION map has been uploaded (orographic factor needs one)
     QdPhyto phyto;                   // resident tracers of PhytoManager.advect_diffuse
     QdEco eco;                       // ecology sub-step state
+    struct QdRoute* route = nullptr; // river routing network, buffer and event log (qd_route.hip), whole-globe handles
     double* zonal_tw = nullptr;      // [2][nlon] cos / sin(2 pi m / nlon) of the zonal spectral filter
     double* sel_cand = nullptr;      // [2][cells] candidates of the two middle ranks after two radix passes (whole-globe handles)
     unsigned int* sel_ccount = nullptr; // [2] candidate counts
@@ -439,6 +440,11 @@ void qd_eco_free(qd_ctx* c);
 int  qd_band_copy_in(qd_ctx* c, void* dst, const void* host, size_t esz);   // qd_api.hip
 int  qd_phyto_step_impl(qd_ctx* c, double dt);                              // qd_phyto.hip
 void qd_phyto_release(qd_ctx* c);
+int  qd_route_span_check(qd_ctx* c, int n);                                 // qd_route.hip
+int  qd_route_step_impl(qd_ctx* c, double dt, int s);
+int  qd_route_is_event(const qd_ctx* c, int s);                               // step s of the span routes
+void qd_route_span_done(qd_ctx* c);
+void qd_route_release(qd_ctx* c);
 bool qd_eco_is_f32(const qd_ctx* c, int field);                             // qd_eco.hip: slab stored as f32 (qd_eco_params.map_f32)
 void qd_eco_convert_slab(qd_ctx* c, const double* src, int src_f32, double* dst, int dst_f32);
 

@@ -130,19 +130,88 @@ class Device:
         self._chk(self.lib.qd_hydrology_commit(self.h, float(dt)), "qd_hydrology_commit")
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
-               ecology=False, phyto=False):
+               ecology=False, phyto=False, routing=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
-        scalars from ThermalForcing.star_table()."""
+        scalars from ThermalForcing.star_table().  `routing`: a RiverRouting on this handle -- bit7, after the
+        hydrology commit (which it needs); the host's t_accum schedule names the event steps, and the span's
+        event records stay in the device log (route_events) until the caller drains them."""
         self.flush()
         st = np.ascontiguousarray(stars, dtype=np.float64)
         assert st.ndim == 2 and st.shape[1] == 7
         flags = ((1 if with_ocean else 0) | (2 if with_physics else 0) | (4 if pass_albedo else 0) | (8 if with_hydrology else 0) |
-                 (16 if energy_diag else 0) | (32 if ecology else 0) | (64 if phyto else 0))
+                 (16 if energy_diag else 0) | (32 if ecology else 0) | (64 if phyto else 0) | (128 if routing is not None else 0))
+        if routing is not None:
+            if routing.dev is not self:
+                raise ValueError("step_n: the RiverRouting runs on another device handle")
+            t0, s0 = routing.t_accum, routing._steps
+            ev = np.ascontiguousarray(routing.schedule(dt, st.shape[0]))
+            rc = self.lib.qd_route_schedule(self.h, int(ev.size), ev.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+            if rc != 0:
+                routing.t_accum, routing._steps = t0, s0
+                self._chk(rc, "qd_route_schedule")
+            rc = self.lib.qd_step_n(self.h, int(st.shape[0]), float(dt), flags, st.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+            if rc != 0:
+                routing.t_accum, routing._steps = t0, s0
+                self._chk(rc, "qd_step_n")
+            return
         self._chk(self.lib.qd_step_n(self.h, int(st.shape[0]), float(dt), flags,
                                      st.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "qd_step_n")
 
     def sync(self):
         self._chk(self.lib.qd_sync(self.h), "qd_sync")
+
+    # ---- river routing (qd_route.hip): plan upload, class seam, results
+    ROUTE_WHICH = {"FLOW": 0, "LAKES": 1, "BUFFER": 2}
+
+    def route_configure(self, plan):
+        """Upload a routing.RoutingPlan (whole-globe handles only)."""
+        keep = [np.ascontiguousarray(a) for a in (plan.cflags, plan.area_row, plan.code, plan.seg_start, plan.seg_cells,
+                                                  plan.level_start, plan.jp_start, plan.jp_cells, plan.lake_start,
+                                                  plan.lake_cells, plan.lake_frac)]
+        ptr = [a.ctypes.data for a in keep]
+        ps = _lib.qd_route_plan(plan.n_lat * plan.n_lon, len(plan.seg_start) - 1, len(plan.seg_cells), plan.n_levels,
+                                len(plan.jp_cells), plan.n_lakes, plan.pe_lakes, 0, *ptr)
+        self._chk(self.lib.qd_route_configure(self.h, ctypes.byref(ps), ctypes.sizeof(ps)), "qd_route_configure")
+        self._route_n = (plan.n_lat * plan.n_lon, plan.n_lakes)
+        self._route_last = None
+
+    def route_free(self):
+        self._chk(self.lib.qd_route_free(self.h), "qd_route_free")
+
+    def route_reset(self):
+        self._chk(self.lib.qd_route_reset(self.h), "qd_route_reset")
+        self._route_last = None
+
+    def route_accumulate(self, dt):
+        self.flush()
+        self._chk(self.lib.qd_route_accumulate(self.h, float(dt)), "qd_route_accumulate")
+
+    def route_event(self, event_dt, with_pe):
+        self.flush()
+        self._chk(self.lib.qd_route_event(self.h, float(event_dt), 1 if with_pe else 0), "qd_route_event")
+
+    def route_download(self, which):
+        n = self._route_n[1] if which == "LAKES" else self._route_n[0]
+        out = np.zeros(n, dtype=np.float64)
+        self._chk(self.lib.qd_route_download(self.h, self.ROUTE_WHICH[which], out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n),
+                  "qd_route_download")
+        return out
+
+    def route_events(self):
+        """Drain the device event log -> list of dicts (routing.LOG_KEYS), oldest first."""
+        from .routing import LOG_KEYS
+        cap = 4096
+        buf = np.zeros((cap, len(LOG_KEYS)), dtype=np.float64)
+        n = ctypes.c_int32(0)
+        self._chk(self.lib.qd_route_events(self.h, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cap, ctypes.byref(n)),
+                  "qd_route_events")
+        out = [dict(zip(LOG_KEYS, (float(x) for x in row))) for row in buf[:n.value]]
+        if out:
+            self._route_last = out[-1]
+        return out
+
+    def route_last_event(self):
+        return self._route_last
 
     # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident
     def phyto_configure(self, n_species, K_h, adv_alpha):

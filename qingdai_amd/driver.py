@@ -16,13 +16,19 @@ where the reference calls eco.step_daily (run_simulation.py:1786-1864).  Without
 Phytoplankton (QD_PHYTO_ENABLE and QD_PHYTO_ADVECTION, default on like the reference, needs the ocean): the per-step transport of
 the tracers by the ocean currents (phyto.advect_diffuse, run_simulation.py:2254-2258) runs inside the resident loop on resident
 tracers (qingdai_amd/phyto.py PhytoTracers, qd_phyto_*); data/plankton.nc carries C_phyto_s through autosave / startup load.
-Not carried over (out of the hot path): phytoplankton daily growth / optics, river routing, genes /
+River routing (P014; QD_HYDRO_ENABLE default 1, QD_HYDRO_NETCDF default data/hydrology.nc, QD_HYDRO_DT_HOURS default 6,
+QD_HYDRO_DIAG default 1, run_simulation.py:1294-1321): the network file is planned once on the host (qingdai_amd/routing.py), the
+accumulation and the events run inside the resident loop after the snow commit + land bucket (qd_step_n bit7), and each chunk's
+[HydroRouting] event lines are printed after it from the device event log.  Deviation: when the network file is missing the
+reference generates one (run_simulation.py:1063-1127, a pit fill that takes minutes at size); here the run goes on WITHOUT routing,
+with the reference's message.  The routing buffer is not part of the restart files (as in the reference).
+Not carried over (out of the hot path): phytoplankton daily growth / optics, genes /
 diversity, matplotlib panels (a note is printed instead of a plot).
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
   SpectralModel.time_step(Teq, dt) [no albedo argument, like the reference driver] -> ocean coupling ->
-  snow commit + land bucket.
+  snow commit + land bucket [-> river routing accumulation, and an event when t_accum reaches dt_hydro].
 """
 from __future__ import annotations
 
@@ -310,10 +316,39 @@ class Simulation:
     def _run_chunk(self, n, energy_diag=False):
         times = self.t + self.dt * np.arange(n)
         stars = self.forcing.star_table(times)
+        routing = getattr(self, "routing", None)
         self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
-                        with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto is not None)
+                        with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto is not None,
+                        routing=routing)
         self.t = float(times[-1] + self.dt)
         self._step_index += n
+        if routing is not None:
+            routing.take_events(self.dev.route_events())      # the span's events, oldest first
+
+    def enable_routing(self, env=None):
+        """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
+        env = os.environ if env is None else env
+        self.routing = None
+        try:
+            enabled, net, dt_h, diag = hydro_env(env)
+            if not enabled:
+                print("[HydroRouting] Disabled by QD_HYDRO_ENABLE=0.")
+                return None
+            if not (net and os.path.exists(net)):
+                # deviation: no automatic network generation (the reference's _try_autogen_hydro_network)
+                print(f"[HydroRouting] Enabled but network not available; running WITHOUT routing "
+                      f"(QD_HYDRO_NETCDF='{net}').")
+                return None
+            from .routing import RiverRouting
+            self.routing = RiverRouting(self.grid, net, dt_hydro_hours=dt_h,
+                                        treat_lake_as_water=(int(env.get("QD_TREAT_LAKE_AS_WATER", "1")) == 1),
+                                        alpha_lake=(float(env["QD_ALPHA_LAKE"]) if env.get("QD_ALPHA_LAKE") else None),
+                                        diag=diag, dev=self.dev)
+            print(f"[HydroRouting] Enabled with network '{net}'.")
+        except Exception as e:      # noqa: BLE001  (the reference never lets routing stop the run)
+            print(f"[HydroRouting] Initialization skipped due to error: {e}")
+            self.routing = None
+        return self.routing
 
     def diagnostics(self):
         d = self.dev
@@ -321,6 +356,13 @@ class Simulation:
         return {"max|u|": d.reduce("U", R_MAXABS), "max|v|": d.reduce("V", R_MAXABS), "max|h|": d.reduce("H", R_MAXABS),
                 "<T_s>": d.reduce("TS", R_COSMEAN), "<cloud>": d.reduce("CLOUD", R_COSMEAN),
                 "<E>": d.reduce("EFLUX", R_COSMEAN), "<P>": d.reduce("PRECIP", R_COSMEAN)}
+
+
+def hydro_env(env):
+    """-> (enabled, network path, dt_hydro hours, diag) from QD_HYDRO_ENABLE / QD_HYDRO_NETCDF / QD_HYDRO_DT_HOURS / QD_HYDRO_DIAG
+    with the reference's defaults (run_simulation.py:1297-1314)."""
+    return (int(env.get("QD_HYDRO_ENABLE", "1")) == 1, env.get("QD_HYDRO_NETCDF", "data/hydrology.nc"),
+            float(env.get("QD_HYDRO_DT_HOURS", "6")), int(env.get("QD_HYDRO_DIAG", "1")) == 1)
 
 
 def chunk_until(t, dt, next_autosave_t, remaining, max_chunk=200):
@@ -384,6 +426,7 @@ def main(argv=None):
             sim.t = float(env["QD_ORBIT_EPOCH_SECONDS"])
         elif env.get("QD_ORBIT_EPOCH_DAYS"):
             sim.t = float(env["QD_ORBIT_EPOCH_DAYS"]) * day
+    sim.enable_routing(env)
     sim.bootstrap_ecology()
     t0 = sim.t
     n_total = len(np.arange(t0, t0 + duration, sim.dt))
