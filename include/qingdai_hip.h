@@ -277,6 +277,22 @@ int qd_route_schedule(qd_handle h, int n, const double* event_dt);   /* the next
 int qd_route_download(qd_handle h, int which, double* host, size_t n);   /* 0 flow map kg/s [n_cells], 1 lake volumes [n_lakes], 2 buffer */
 int qd_route_events(qd_handle h, double* out, int max, int* n);   /* drains the event log: *n records of 8 doubles */
 
+/* ---- river network generation (P014, scripts/generate_hydrology_maps.py:64-311), whole-globe handles ------------------
+ * pit_fill(elevation, land_mask, max_iters, eps), compute_flow_to_index, identify_lakes, compute_lake_outlets and
+ * topo_sort_flow_order on the handle's stream, every output bit-identical to the reference's.  land_mask and elevation are
+ * [n_lat][n_lon] (the handle's grid); the host tables are the reference's spherical_distance operands: lat_rad [n_lat] and
+ * lon_rad [n_lon] (np.deg2rad of the grid's axes) and cos_pair [n_lat][3] = cos(0.5 (lat_rad[j] + lat_rad[j + dj])) for
+ * dj = -1, 0, 1 (unused entries at the poles are ignored); radius is PLANET_RADIUS.  Outputs: elevation_filled [n_lat][n_lon],
+ * flow_to_index [n_lat][n_lon] (-1: ocean, sink), flow_order [*n_land], lake_mask, lake_id [n_lat][n_lon] and
+ * lake_outlet_index [*n_lakes] (room for lake_outlet_cap).  Refused (nonzero): a shape that is not the handle's, n_lat < 2 or
+ * n_lon < 3, land_mask values other than 0 / 1, and non-finite elevation on a land cell or a neighbour of one (NaN comparisons
+ * make the reference depend on its visiting order). */
+int qd_hydronet_build(qd_handle h, int n_lat, int n_lon, const uint8_t* land_mask, const double* elevation, double eps, int max_iters,
+                      const double* lat_rad, const double* lon_rad, const double* cos_pair, double radius,
+                      double* elevation_filled, int32_t* flow_to_index, int32_t* flow_order, uint8_t* lake_mask, int32_t* lake_id,
+                      int32_t* lake_outlet_index, int lake_outlet_cap, int* n_land, int* n_lakes);
+int qd_hydronet_sweeps(qd_handle h, int* sweeps);   /* pit-fill sweeps the last qd_hydronet_build on this handle ran */
+
 /* ---- reductions for diagnostics (energy.py:494-538, ocean.py:535-561) -------------- */
 /* compute_energy_diagnostics (energy.py:494-538) from the resident state, with the flux formulas of the driver's
  * coupling block (run_simulation.py:2199-2239): out[10] = cos-weighted global means of

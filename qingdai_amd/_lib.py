@@ -42,6 +42,7 @@ SYMBOLS = [
     "qd_phyto_configure", "qd_phyto_upload", "qd_phyto_download", "qd_phyto_advect_diffuse",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
+    "qd_hydronet_build", "qd_hydronet_sweeps",
     "qd_copy_ceiling", "qd_timing_enable", "qd_timing_select", "qd_timing_get", "qd_timing_reset",
 ]
 
@@ -172,6 +173,11 @@ def load():
     lib.qd_route_schedule.argtypes = [vp, i32, dp]
     lib.qd_route_download.argtypes = [vp, i32, dp, sz]
     lib.qd_route_events.argtypes = [vp, dp, i32, ip]
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    lib.qd_hydronet_build.argtypes = [vp, i32, i32, u8p, dp, dbl, i32, dp, dp, dp, dbl, dp, i32p, i32p, u8p, i32p, i32p, i32,
+                                      ip, ip]
+    lib.qd_hydronet_sweeps.argtypes = [vp, ip]
     lib.qd_timing_enable.argtypes = [vp, i32]
     lib.qd_timing_select.argtypes = [vp, ctypes.c_char_p]
     lib.qd_timing_get.argtypes = [vp, ctypes.c_char_p, dp, ctypes.POINTER(i64)]

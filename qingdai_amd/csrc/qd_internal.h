@@ -204,6 +204,7 @@ struct qd_ctx {
     QdPhyto phyto;                   // resident tracers of PhytoManager.advect_diffuse
     QdEco eco;                       // ecology sub-step state
     struct QdRoute* route = nullptr; // river routing network, buffer and event log (qd_route.hip), whole-globe handles
+    int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
     double* zonal_tw = nullptr;      // [2][nlon] cos / sin(2 pi m / nlon) of the zonal spectral filter
     double* sel_cand = nullptr;      // [2][cells] candidates of the two middle ranks after two radix passes (whole-globe handles)
     unsigned int* sel_ccount = nullptr; // [2] candidate counts

@@ -19,9 +19,10 @@ tracers (qingdai_amd/phyto.py PhytoTracers, qd_phyto_*); data/plankton.nc carrie
 River routing (P014; QD_HYDRO_ENABLE default 1, QD_HYDRO_NETCDF default data/hydrology.nc, QD_HYDRO_DT_HOURS default 6,
 QD_HYDRO_DIAG default 1, run_simulation.py:1294-1321): the network file is planned once on the host (qingdai_amd/routing.py), the
 accumulation and the events run inside the resident loop after the snow commit + land bucket (qd_step_n bit7), and each chunk's
-[HydroRouting] event lines are printed after it from the device event log.  Deviation: when the network file is missing the
-reference generates one (run_simulation.py:1063-1127, a pit fill that takes minutes at size); here the run goes on WITHOUT routing,
-with the reference's message.  The routing buffer is not part of the restart files (as in the reference).
+[HydroRouting] event lines are printed after it from the device event log.  A missing network file is generated on the device
+(qingdai_amd/hydronet.py, the reference's run_simulation.py:1063-1127 bit for bit) when QD_HYDRO_AUTOGEN=1 -- the reference's
+behaviour; by default (QD_HYDRO_AUTOGEN=0) the run goes on WITHOUT routing, with the reference's message.  The routing buffer is
+not part of the restart files (as in the reference).
 Not carried over (out of the hot path): phytoplankton daily growth / optics, genes /
 diversity, matplotlib panels (a note is printed instead of a plot).
 
@@ -335,10 +336,13 @@ class Simulation:
                 print("[HydroRouting] Disabled by QD_HYDRO_ENABLE=0.")
                 return None
             if not (net and os.path.exists(net)):
-                # deviation: no automatic network generation (the reference's _try_autogen_hydro_network)
-                print(f"[HydroRouting] Enabled but network not available; running WITHOUT routing "
-                      f"(QD_HYDRO_NETCDF='{net}').")
-                return None
+                # QD_HYDRO_AUTOGEN=1: the reference's _try_autogen_hydro_network (run_simulation.py:1063-1127), on the device
+                if hydro_autogen(env):
+                    self.autogen_network(net, env)
+                if not (net and os.path.exists(net)):
+                    print(f"[HydroRouting] Enabled but network not available; running WITHOUT routing "
+                          f"(QD_HYDRO_NETCDF='{net}').")
+                    return None
             from .routing import RiverRouting
             self.routing = RiverRouting(self.grid, net, dt_hydro_hours=dt_h,
                                         treat_lake_as_water=(int(env.get("QD_TREAT_LAKE_AS_WATER", "1")) == 1),
@@ -349,6 +353,27 @@ class Simulation:
             print(f"[HydroRouting] Initialization skipped due to error: {e}")
             self.routing = None
         return self.routing
+
+    def autogen_network(self, path, env=None):
+        """run_simulation.py:1063-1127: build the network from the run's own land mask and elevation (zeros for the procedural
+        planet) with eps 1e-3 and 200 sweeps (qingdai_amd/hydronet.py, on this handle) and write it to `path` -> True on
+        success.  Failures print the reference's message and return False."""
+        env = os.environ if env is None else env
+        try:
+            from .hydronet import generate_network, write_network
+            topo_nc = env.get("QD_TOPO_NC")
+            src = "procedural" if (not topo_nc or not os.path.exists(str(topo_nc))) else os.path.basename(str(topo_nc))
+            print(f"[HydroRouting] Auto-generating network to '{path}' (source={src})...")
+            t0 = time.perf_counter()
+            net = generate_network(self.grid, self.land_mask, self.elevation, eps=1e-3, max_iters=200, dev=self.dev)
+            write_network(path, self.grid, net, auto=True)
+            print("[HydroRouting] Network auto-generation complete.")
+            print(f"[HydroNet] built on the device in {time.perf_counter() - t0:.2f} s: {net['sweeps']} pit-fill sweeps, "
+                  f"{net['n_lakes']} lakes.")
+            return True
+        except Exception as e:      # noqa: BLE001  (the reference goes on without routing)
+            print(f"[HydroRouting] Auto-generation failed: {e}")
+            return False
 
     def diagnostics(self):
         d = self.dev
@@ -363,6 +388,11 @@ def hydro_env(env):
     with the reference's defaults (run_simulation.py:1297-1314)."""
     return (int(env.get("QD_HYDRO_ENABLE", "1")) == 1, env.get("QD_HYDRO_NETCDF", "data/hydrology.nc"),
             float(env.get("QD_HYDRO_DT_HOURS", "6")), int(env.get("QD_HYDRO_DIAG", "1")) == 1)
+
+
+def hydro_autogen(env):
+    """QD_HYDRO_AUTOGEN (default 0): 1 generates a missing network file, as the reference driver always does."""
+    return int(env.get("QD_HYDRO_AUTOGEN", "0")) == 1
 
 
 def chunk_until(t, dt, next_autosave_t, remaining, max_chunk=200):
