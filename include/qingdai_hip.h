@@ -64,6 +64,8 @@ enum qd_field {
      * total LAI, its snapshot at the last canopy recompute, cached canopy factor f, daily energy buffer, land-only
      * ecology alpha (NaN elsewhere), daily banded alpha, ocean-colour alpha of the phytoplankton coupling */
     QD_F_ECO_LAI, QD_F_ECO_LAI_SNAP, QD_F_ECO_F, QD_F_ECO_EDAY, QD_F_ECO_ALPHA, QD_F_ECO_ALPHA_BANDED, QD_F_WATER_ALPHA,
+    /* daily phytoplankton step (phyto.py:339-435): nutrient pool N (mmol m^-3), Kd(490) (m^-1) */
+    QD_F_PHYTO_N, QD_F_KD490,
     QD_F_COUNT_F64,
     /* uint8 masks */
     QD_F_LAND_MASK = 100, QD_F_ICE_MASK = 101
@@ -152,7 +154,7 @@ int qd_driver_physics(qd_handle h, double dt);
 int qd_hydrology_commit(qd_handle h, double dt);
 /* benchmark_jax.py:124-158 as one resident loop of n steps: forcing -> albedo -> time_step [-> ocean
  * coupling] [-> hydrology commit].  flags bit0 = with_ocean, bit1 = with_driver_physics (else the simple
- * ocean/land albedo of benchmark_jax.py:129), bit2 = pass albedo to time_step, bit3 = hydrology commit, bit4 = energy diagnostics on the first step (qd_energy_diagnostics_last), bit5 = ecology sub-step (qd_eco_substep, and qd_indiv_substep when a pool is configured; needs bit1), bit6 = tracer transport after the ocean step (qd_phyto_advect_diffuse; needs bit0 and qd_phyto_configure), bit7 = river routing after the hydrology commit (qd_route_accumulate, and qd_route_event on the steps a qd_route_schedule of n entries names; needs bit3 and qd_route_configure).  `stars` holds n rows of 7 host scalars
+ * ocean/land albedo of benchmark_jax.py:129), bit2 = pass albedo to time_step, bit3 = hydrology commit, bit4 = energy diagnostics on the first step (qd_energy_diagnostics_last), bit5 = ecology sub-step (qd_eco_substep, and qd_indiv_substep when a pool is configured; needs bit1), bit6 = tracer transport after the ocean step (qd_phyto_advect_diffuse; needs bit0 and qd_phyto_configure), bit7 = river routing after the hydrology commit (qd_route_accumulate, and qd_route_event on the steps a qd_route_schedule of n entries names; needs bit3 and qd_route_configure), bit8 = daily phytoplankton step at the top of the steps a qd_phyto_daily_schedule of n entries names (SST with bit0, else TS; needs bit1 and qd_phyto_daily_configure).  `stars` holds n rows of 7 host scalars
  * (flux_A, decl_A, ra_A, flux_B, decl_B, ra_B, theta), evaluated by the caller as forcing.py:85-125 does. */
 int qd_step_n(qd_handle h, int n, double dt, int flags, const double* stars);
 int qd_last_ocean_nsub(qd_handle h, int* n_sub);
@@ -244,6 +246,41 @@ int qd_phyto_configure(qd_handle h, int n_species, double K_h, double adv_alpha)
 int qd_phyto_upload(qd_handle h, int species, const double* host);      /* [n_lat][n_lon] f64 */
 int qd_phyto_download(qd_handle h, int species, double* host);
 int qd_phyto_advect_diffuse(qd_handle h, double dt_seconds);             /* all species, three launches */
+
+/* ---- daily phytoplankton step (P017, PhytoManager.step_daily, pygcm/ecology/phyto.py:339-435), whole-globe handles -------
+ * One pointwise launch per planet-day on the resident tracers of qd_phyto_configure (n_species must match): the cell's two-star
+ * insolation from the step's star row (7 scalars as in qd_step_n), the band split, Kd, mixed-layer light, growth, the nutrient
+ * pool, the band reflectances and their scalar reduction.  Writes the tracers, PHYTO_N, KD490, WATER_ALPHA and a resident
+ * [n_bands][n_lat][n_lon] band stack, and appends one record of QD_PHYTO_DAILY_LOG_W = 4 doubles to a device log:
+ * {daily steps so far, <C_tot>, <Kd490>, <alpha_water>} with the max(cos lat, 0)-weighted means of the [PhytoDiag] line.
+ * With `couple` set, the albedo launches override the ocean base albedo with clip(WATER_ALPHA, 0, 1) from the first daily step on
+ * (run_simulation.py:2121-2128). */
+#define QD_PHYTO_DAILY_LOG_W 4
+typedef struct qd_phyto_daily_params {
+    int32_t n_species, n_bands;
+    int32_t idx_490;             /* band nearest 490 nm */
+    int32_t enable_N;            /* QD_PHYTO_ENABLE_N */
+    int32_t couple;              /* QD_PHYTO_ALBEDO_COUPLE */
+    int32_t reserved;
+    double H_mld;                /* max(0.1, H) */
+    double alpha_P, Q10, T_ref, kd_exp_m;
+    double sink;                 /* lambda_sink / max(1e-6, H_mld) when lambda_sink > 0, else 0 */
+    double R_remin;
+    double alpha_clip_min, alpha_clip_max;
+    double dt_days;              /* 1 in the driver */
+} qd_phyto_daily_params;
+/* band_tab [8][n_bands] rows: Kd0, k_chl, A_pure, delta_lambda, w (scalar reduction weights), specA, specB, T_ray (the band split
+ * of qd_band_insolation); species_tab [6][n_species] rows: c_reflect, p_reflect, mu_max, m0, KN, Y; shape [n_species][n_bands].
+ * The first call, and a call that changes n_bands, zeroes the band stack, KD490 and the step count. */
+int qd_phyto_daily_configure(qd_handle h, const qd_phyto_daily_params* p, size_t sizeof_params, const double* band_tab,
+                             const double* species_tab, const double* shape);
+int qd_phyto_daily(qd_handle h, const double* star_row, int use_sst);   /* one daily step now (T_w = SST or TS) */
+int qd_phyto_daily_schedule(qd_handle h, int n, const int32_t* fire);   /* the next qd_step_n span: 1 = the step fires */
+int qd_phyto_daily_log(qd_handle h, double* out, int max, int* n);      /* drains the log: *n records of 4 doubles */
+int qd_phyto_daily_download_bands(qd_handle h, double* host, size_t n); /* [n_bands][n_lat][n_lon] */
+int qd_phyto_daily_state(qd_handle h, int64_t* n_steps);                /* daily steps run since the configure */
+/* the two per-star insolation maps [n_lat][n_lon] the daily kernel evaluates for a star row (checks against qd_forcing) */
+int qd_phyto_daily_insolation(qd_handle h, const double* star_row, double* insA, double* insB);
 
 /* ---- river routing (P014, pygcm/routing.py), whole-globe handles ----------------------------------
  * The host plans the network once (qingdai_amd/routing.py: build_plan): per cell a target code (>= 0 a live edge to that

@@ -20,7 +20,8 @@ FIELDS = ["U", "V", "H", "TS", "Q", "CLOUD", "HICE", "ISR", "ISR_A", "ISR_B", "T
           "OLR", "EFLUX", "PCOND", "LH", "LHREL", "CLOUD_EFF", "FRICTION", "CSMAP", "BASE_ALBEDO", "ELEVATION",
           "UO", "VO", "ETA", "SST", "QNET", "PRECIP", "CLOUD_FROM_P", "CLOUD_SRC", "W_LAND", "S_SNOW", "C_SNOW",
           "S_SNOW_NEXT", "MELT", "P_RAIN", "GLACIER", "RUNOFF",
-          "ECO_LAI", "ECO_LAI_SNAP", "ECO_F", "ECO_EDAY", "ECO_ALPHA", "ECO_ALPHA_BANDED", "WATER_ALPHA"]
+          "ECO_LAI", "ECO_LAI_SNAP", "ECO_F", "ECO_EDAY", "ECO_ALPHA", "ECO_ALPHA_BANDED", "WATER_ALPHA",
+          "PHYTO_N", "KD490"]
 F = {n: i for i, n in enumerate(FIELDS)}
 F["LAND_MASK"] = 100
 F["ICE_MASK"] = 101
@@ -40,6 +41,8 @@ SYMBOLS = [
     "qd_eco_configure", "qd_eco_set_lai_layers", "qd_eco_substep", "qd_eco_banded_alpha", "qd_eco_get_state", "qd_eco_set_state",
     "qd_indiv_configure", "qd_indiv_substep", "qd_indiv_download", "qd_indiv_upload",
     "qd_phyto_configure", "qd_phyto_upload", "qd_phyto_download", "qd_phyto_advect_diffuse",
+    "qd_phyto_daily_configure", "qd_phyto_daily", "qd_phyto_daily_schedule", "qd_phyto_daily_log", "qd_phyto_daily_download_bands",
+    "qd_phyto_daily_state", "qd_phyto_daily_insolation",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
     "qd_hydronet_build", "qd_hydronet_sweeps",
@@ -52,6 +55,16 @@ class qd_eco_params(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_double) for n in ("k_canopy", "leaf_scalar", "soil_ref", "w_lai", "light_update_hours",
                                                  "recompute_lai_delta")] +
                 [(n, ctypes.c_int32) for n in ("substep_every_nphys", "albedo_couple", "bands_couple", "water_couple", "use_lai", "map_f32")])
+
+
+class qd_phyto_daily_params(ctypes.Structure):
+    """include/qingdai_hip.h: qd_phyto_daily_params"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("n_species", "n_bands", "idx_490", "enable_N", "couple", "reserved")] +
+                [(n, ctypes.c_double) for n in ("H_mld", "alpha_P", "Q10", "T_ref", "kd_exp_m", "sink", "R_remin", "alpha_clip_min",
+                                                 "alpha_clip_max", "dt_days")])
+
+
+PHYTO_DAILY_LOG_W = 4
 
 
 class qd_route_plan(ctypes.Structure):
@@ -135,6 +148,13 @@ def load():
     lib.qd_phyto_upload.argtypes = [vp, i32, vp]
     lib.qd_phyto_download.argtypes = [vp, i32, vp]
     lib.qd_phyto_advect_diffuse.argtypes = [vp, dbl]
+    lib.qd_phyto_daily_configure.argtypes = [vp, ctypes.POINTER(qd_phyto_daily_params), sz, dp, dp, dp]
+    lib.qd_phyto_daily.argtypes = [vp, dp, i32]
+    lib.qd_phyto_daily_schedule.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int32)]
+    lib.qd_phyto_daily_log.argtypes = [vp, dp, i32, ctypes.POINTER(i32)]
+    lib.qd_phyto_daily_download_bands.argtypes = [vp, dp, sz]
+    lib.qd_phyto_daily_state.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.qd_phyto_daily_insolation.argtypes = [vp, dp, dp, dp]
     lib.qd_comm_unique_id.argtypes = [vp, sz]
     lib.qd_comm_init.argtypes = [vp, vp, sz]
     lib.qd_comm_barrier.argtypes = [vp]

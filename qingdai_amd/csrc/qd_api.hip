@@ -471,6 +471,7 @@ extern "C" int qd_destroy(qd_handle c) {
     }
     qd_phyto_release(c);
     qd_route_release(c);
+    qd_phyto_daily_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -689,11 +690,17 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     if (with_route && qd_route_span_check(c, n)) return -1;
     // the schedule is for this span only, whatever way it ends
     struct RouteGuard { qd_ctx* c; int on; ~RouteGuard() { if (on) qd_route_span_done(c); } } route_guard{c, with_route};
+    const int with_pdaily = flags & 256;
+    if (with_pdaily && qd_phyto_daily_span_check(c, n, with_phys)) return -1;
+    struct DailyGuard { qd_ctx* c; int on; ~DailyGuard() { if (on) qd_phyto_daily_span_done(c); } } daily_guard{c, with_pdaily};
     // whatever way this call ends, the per-span switches are back to what a stand-alone qd_* call expects
     struct SpanGuard { qd_ctx* c; ~SpanGuard() { c->diag_write = 1; c->want_pcond_ahead = 0; c->pcond_ahead = 0; c->defer_final = 0; c->final_pending.on = 0; qd_saf_drop(c); } } span_guard{c};
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
         int rc;
+        // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
+        // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
+        if (with_pdaily && qd_phyto_daily_fires(c, s) && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0, s))) return rc;
         // EcologyAdapter.step_subdaily sits between the glacier mask and the base-albedo blend (run_simulation.py:2075-2104):
         // its clock / canopy / alpha part runs before the albedo kernel, its E_day += isr dt rides on this step's forcing launch
         if (with_eco && c->eco.p.albedo_couple) { if ((rc = qd_eco_canopy_impl(c, dt))) return rc; c->eco.eday_dt = c->eco.p.use_lai ? dt : 0.0; }

@@ -544,7 +544,8 @@ int qd_driver_physics_impl(qd_ctx* c, double dt, const QdForcingCall* fc, int pa
         QdAlbP A{p.cloud_adv_alpha, std::max(1e-6, p.hice_ref), p.alpha_ice, p.alpha_cloud, p.alpha_water, p.snow_albedo_fresh, E.p.w_lai,
                  p.cloud_advect ? 1 : 0, p.use_topo_albedo ? 1 : 0, p.swe_enable ? 1 : 0,
                  (E.configured && E.p.albedo_couple && E.alpha_valid) ? 1 : 0, (E.configured && E.p.bands_couple && E.banded_valid) ? 1 : 0,
-                 (E.configured && E.p.water_couple && E.water_valid) ? 1 : 0, (E.configured && E.p.map_f32) ? 1 : 0};
+                 ((E.configured && E.p.water_couple && E.water_valid) || qd_phyto_daily_couples(c)) ? 1 : 0,
+                 (E.configured && E.p.map_f32) ? 1 : 0};
         if (A.eco) { const int me = qd_plan(c, {QD_IN(F[QD_F_ECO_ALPHA], 0)}); if (me < 0) return -1; m = std::min(m, me); }
         if (A.banded) { const int me = qd_plan(c, {QD_IN(F[QD_F_ECO_ALPHA_BANDED], 0)}); if (me < 0) return -1; m = std::min(m, me); }
         if (A.water) { const int me = qd_plan(c, {QD_IN(F[QD_F_WATER_ALPHA], 0)}); if (me < 0) return -1; m = std::min(m, me); }

@@ -81,18 +81,26 @@ __device__ __forceinline__ double qd_albedo_cell(const QdAlbP& P, size_t o, doub
 struct QdStar { double flux, sin_d, cos_d, alpha; };
 struct QdForcingP { QdStar A, B; double theta, sigma; int with_teq; };
 
+// per-star insolation of cell (i, j): isr_A, isr_B of forcing.py:85-103.  Shared by the forcing stages and the daily phytoplankton
+// kernel (qd_phyto_daily.hip), which needs the step's values in registers before any launch of the step has stored them.
+__device__ __forceinline__ void qd_star_insolation(const QdTabs& T, const QdStar& A, const QdStar& B, double theta, int i, int j,
+                                                   double& a_, double& b_) {
+    const double sl = T.sin_raw[i], cl = T.cos_raw[i], lon = T.lon_rad[j];
+    const double hA = theta + lon - A.alpha;
+    const double hB = theta + lon - B.alpha;
+    const double czA = qd_max(0.0, sl * A.sin_d + cl * A.cos_d * cos(hA));
+    const double czB = qd_max(0.0, sl * B.sin_d + cl * B.cos_d * cos(hB));
+    a_ = A.flux * czA; b_ = B.flux * czB;
+}
+
 // alb: the cell's albedo (only read when P.with_teq).  Returns {total insolation, Teq} of the cell; Teq == nullptr: not stored (the
 // caller hands it on in a register)
 struct QdForcingOut { double tot, teq; };
 __device__ __forceinline__ QdForcingOut qd_forcing_cell(const QdTabs& T, const QdForcingP& P, int i, int j, size_t o, double alb,
                                                         double* __restrict__ isrA, double* __restrict__ isrB, double* __restrict__ isr,
                                                         double* __restrict__ Teq, double* __restrict__ eday, double eday_dt) {
-    const double sl = T.sin_raw[i], cl = T.cos_raw[i], lon = T.lon_rad[j];
-    const double hA = P.theta + lon - P.A.alpha;
-    const double hB = P.theta + lon - P.B.alpha;
-    const double czA = qd_max(0.0, sl * P.A.sin_d + cl * P.A.cos_d * cos(hA));
-    const double czB = qd_max(0.0, sl * P.B.sin_d + cl * P.B.cos_d * cos(hB));
-    const double a_ = P.A.flux * czA, b_ = P.B.flux * czB;
+    double a_, b_;
+    qd_star_insolation(T, P.A, P.B, P.theta, i, j, a_, b_);
     const double tot = a_ + b_;
     if (isrA) { isrA[o] = a_; isrB[o] = b_; }                  // nullptr: a step inside a span whose per-star fluxes nobody reads (lazy diagnostics)
     isr[o] = tot;

@@ -130,29 +130,54 @@ class Device:
         self._chk(self.lib.qd_hydrology_commit(self.h, float(dt)), "qd_hydrology_commit")
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
-               ecology=False, phyto=False, routing=None):
+               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  `routing`: a RiverRouting on this handle -- bit7, after the
         hydrology commit (which it needs); the host's t_accum schedule names the event steps, and the span's
-        event records stay in the device log (route_events) until the caller drains them."""
+        event records stay in the device log (route_events) until the caller drains them.  `phyto_daily`: a phyto.PhytoDaily on
+        this handle -- bit8; its firing clock turns the span's times t0 + dt * arange(n) into the schedule, and the span's
+        [PhytoDiag] records stay in the device log (phyto_daily_log) until the caller drains them."""
         self.flush()
         st = np.ascontiguousarray(stars, dtype=np.float64)
         assert st.ndim == 2 and st.shape[1] == 7
         flags = ((1 if with_ocean else 0) | (2 if with_physics else 0) | (4 if pass_albedo else 0) | (8 if with_hydrology else 0) |
-                 (16 if energy_diag else 0) | (32 if ecology else 0) | (64 if phyto else 0) | (128 if routing is not None else 0))
+                 (16 if energy_diag else 0) | (32 if ecology else 0) | (64 if phyto else 0) | (128 if routing is not None else 0) |
+                 (256 if phyto_daily is not None else 0))
+        if phyto_daily is not None:
+            if phyto_daily.dev is not self:
+                raise ValueError("step_n: the PhytoDaily runs on another device handle")
+            if t0 is None:
+                raise ValueError("step_n: phyto_daily needs the span's start time t0")
+            clock = phyto_daily.phyto_next_time
+            fire = np.ascontiguousarray(phyto_daily.schedule(float(t0), float(dt), st.shape[0]), dtype=np.int32)
+            rc = self.lib.qd_phyto_daily_schedule(self.h, int(fire.size), fire.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+            if rc != 0:
+                phyto_daily.phyto_next_time = clock
+                self._chk(rc, "qd_phyto_daily_schedule")
+            if routing is None:
+                rc = self.lib.qd_step_n(self.h, int(st.shape[0]), float(dt), flags, st.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+                if rc != 0:
+                    phyto_daily.phyto_next_time = clock
+                    self._chk(rc, "qd_step_n")
+                phyto_daily._fired(int(fire.sum()))
+                return
         if routing is not None:
             if routing.dev is not self:
                 raise ValueError("step_n: the RiverRouting runs on another device handle")
-            t0, s0 = routing.t_accum, routing._steps
+            t0_acc, s0 = routing.t_accum, routing._steps
             ev = np.ascontiguousarray(routing.schedule(dt, st.shape[0]))
             rc = self.lib.qd_route_schedule(self.h, int(ev.size), ev.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
             if rc != 0:
-                routing.t_accum, routing._steps = t0, s0
+                routing.t_accum, routing._steps = t0_acc, s0
                 self._chk(rc, "qd_route_schedule")
             rc = self.lib.qd_step_n(self.h, int(st.shape[0]), float(dt), flags, st.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
             if rc != 0:
-                routing.t_accum, routing._steps = t0, s0
+                routing.t_accum, routing._steps = t0_acc, s0
+                if phyto_daily is not None:
+                    phyto_daily.phyto_next_time = clock
                 self._chk(rc, "qd_step_n")
+            if phyto_daily is not None:
+                phyto_daily._fired(int(fire.sum()))
             return
         self._chk(self.lib.qd_step_n(self.h, int(st.shape[0]), float(dt), flags,
                                      st.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "qd_step_n")
@@ -214,6 +239,39 @@ class Device:
         return self._route_last
 
     # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident
+    # ---- daily phytoplankton step (qd_phyto_daily.hip)
+    def phyto_daily_configure(self, params, band_tab, species_tab, shape):
+        keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (band_tab, species_tab, shape)]
+        dp = ctypes.POINTER(ctypes.c_double)
+        self._chk(self.lib.qd_phyto_daily_configure(self.h, ctypes.byref(params), ctypes.sizeof(params),
+                                                    *[a.ctypes.data_as(dp) for a in keep]), "qd_phyto_daily_configure")
+
+    def phyto_daily(self, star_row, use_sst):
+        self.flush()
+        row = np.ascontiguousarray(star_row, dtype=np.float64).reshape(7)
+        self._chk(self.lib.qd_phyto_daily(self.h, row.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 1 if use_sst else 0),
+                  "qd_phyto_daily")
+
+    def phyto_daily_log(self):
+        """Drain the [PhytoDiag] records -> [n][4] (daily steps so far, <C_tot>, <Kd490>, <alpha_water>)."""
+        n = ctypes.c_int(0)
+        cap = 4096
+        out = np.empty((cap, _lib.PHYTO_DAILY_LOG_W), dtype=np.float64)
+        self._chk(self.lib.qd_phyto_daily_log(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cap, ctypes.byref(n)),
+                  "qd_phyto_daily_log")
+        return out[:n.value].copy()
+
+    def phyto_daily_bands(self, nb):
+        out = np.empty((nb,) + self.shape, dtype=np.float64)
+        self._chk(self.lib.qd_phyto_daily_download_bands(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.size),
+                  "qd_phyto_daily_download_bands")
+        return out
+
+    def phyto_daily_steps(self):
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.qd_phyto_daily_state(self.h, ctypes.byref(n)), "qd_phyto_daily_state")
+        return int(n.value)
+
     def phyto_configure(self, n_species, K_h, adv_alpha):
         self._chk(self.lib.qd_phyto_configure(self.h, int(n_species), float(K_h), float(adv_alpha)), "qd_phyto_configure")
         self._phyto_S = int(n_species)

@@ -23,8 +23,13 @@ accumulation and the events run inside the resident loop after the snow commit +
 (qingdai_amd/hydronet.py, the reference's run_simulation.py:1063-1127 bit for bit) when QD_HYDRO_AUTOGEN=1 -- the reference's
 behaviour; by default (QD_HYDRO_AUTOGEN=0) the run goes on WITHOUT routing, with the reference's message.  The routing buffer is
 not part of the restart files (as in the reference).
-Not carried over (out of the hot path): phytoplankton daily growth / optics, genes /
-diversity, matplotlib panels (a note is printed instead of a plot).
+Phytoplankton daily step (P017; QD_PHYTO_DAILY=1, default 0, with QD_PHYTO_ENABLE=1): PhytoManager.step_daily runs inside the
+resident loop on the steps its firing clock names (qd_step_n bit8, at the top of the step; qingdai_amd/phyto.py PhytoDaily), the
+ocean-colour albedo overrides the ocean base albedo from the first daily step on (QD_PHYTO_ALBEDO_COUPLE, default 1), each chunk's
+[PhytoDiag] lines are printed after it from the device log, and data/plankton.nc is written and read with the reference's
+variable set.  The tracers exist then even without the ocean (the transport still needs it).
+Not carried over (out of the hot path): genes / diversity, plankton.json, matplotlib panels (a note is
+printed instead of a plot).
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -190,15 +195,30 @@ class Simulation:
                 lai = f"LAI mean {self.eco.pop.summary()['LAI_mean']:.2f}" if self.eco.pop is not None else "no population (M1)"
                 print(f"[Ecology] device sub-step: NB={self.eco.bands.nbands}, alpha_leaf={self.eco.alpha_leaf_scalar:.3f}, "
                       f"{lai}, individuals {self.indiv.n_indiv if self.indiv else 0}")
-        # phytoplankton tracers (run_simulation.py:1346-1364): only their transport by the currents is on this path
+        # phytoplankton tracers (run_simulation.py:1346-1364): their transport by the currents (needs the ocean), and under
+        # QD_PHYTO_DAILY=1 the daily growth / optics step with its ocean-colour albedo, which the reference runs with or without the
+        # ocean or the transport
         self.phyto = None
+        self.phyto_daily = None
         if phyto is None:
             phyto = int(env.get("QD_PHYTO_ENABLE", "1")) == 1 and int(env.get("QD_PHYTO_ADVECTION", "1")) == 1
-        if phyto and self.ocean is not None:
+        self.phyto_transport = bool(phyto) and self.ocean is not None
+        daily_on = int(env.get("QD_PHYTO_ENABLE", "1")) == 1 and int(env.get("QD_PHYTO_DAILY", "0")) == 1
+        if self.phyto_transport or daily_on:
             from .phyto import PhytoTracers
             self.phyto = PhytoTracers(self.grid, self.land_mask, dev=self.dev)
             if not quiet:
                 print(f"[Phyto] resident tracers: S={self.phyto.S}, K_h={self.phyto.K_h:g} m^2/s, adv_alpha={self.phyto.adv_alpha:g}")
+        if daily_on:
+            from .phyto import PhytoDaily
+            try:
+                H_phyto = float(env.get("QD_OCEAN_H_M", env.get("QD_MLD_M", "50")))       # run_simulation.py:1354-1359
+            except ValueError:
+                H_phyto = 50.0
+            diag = int(env.get("QD_PHYTO_DIAG", "1")) == 1
+            self.phyto_daily = PhytoDaily(self.phyto, H_mld_m=H_phyto, diag=diag, dev=self.dev, day_seconds=2 * np.pi / PLANET_OMEGA)
+            if diag:
+                print("[Phyto] Manager initialized.")
         # banded initial surface temperature (run_simulation.py:310-328)
         if int(env.get("QD_INIT_BANDED", "0")) == 1:
             T_eq, T_pole = float(env.get("QD_INIT_T_EQ", "295.0")), float(env.get("QD_INIT_T_POLE", "265.0"))
@@ -243,7 +263,9 @@ class Simulation:
             save_ocean(os.path.join(data_dir, "ocean.nc"), self.grid, self.dev, day_value=day)
         topo.export_topography_to_netcdf(os.path.join(data_dir, "topography.nc"), self.grid, self.land_mask, self.base_albedo,
                                          self.friction, elevation=self.elevation)
-        if self.phyto is not None:                              # run_simulation.py:1677-1685 (the tracer part of plankton.nc)
+        if self.phyto_daily is not None:                        # run_simulation.py:1677-1685, the reference's variable set
+            self.phyto_daily.save_distribution_nc(os.path.join(data_dir, "plankton.nc"), day_value=day)
+        elif self.phyto is not None:                            # (the tracer part of plankton.nc)
             self.phyto.save_distribution_nc(os.path.join(data_dir, "plankton.nc"), day_value=day)
 
     # -- the loop
@@ -318,11 +340,14 @@ class Simulation:
         times = self.t + self.dt * np.arange(n)
         stars = self.forcing.star_table(times)
         routing = getattr(self, "routing", None)
+        daily = self.phyto_daily
         self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
-                        with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto is not None,
-                        routing=routing)
+                        with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto_transport,
+                        routing=routing, phyto_daily=daily, t0=self.t)
         self.t = float(times[-1] + self.dt)
         self._step_index += n
+        if daily is not None:
+            daily.print_diag(self.dev.phyto_daily_log())      # the span's [PhytoDiag] lines, oldest first
         if routing is not None:
             routing.take_events(self.dev.route_events())      # the span's events, oldest first
 
@@ -450,7 +475,8 @@ def main(argv=None):
     if sim.phyto is not None and int(env.get("QD_LOAD_PLANKTON", "1")) == 1:
         pnc = os.path.join(data_dir, "plankton.nc")
         if os.path.exists(pnc):
-            print(f"[Phyto] plankton.nc load {'OK' if sim.phyto.load_distribution_nc(pnc) else 'skipped/failed'}.")
+            loader = sim.phyto_daily if sim.phyto_daily is not None else sim.phyto
+            print(f"[Phyto] plankton.nc load {'OK' if loader.load_distribution_nc(pnc) else 'skipped/failed'}.")
     if not loaded and sim.t == 0.0:
         if env.get("QD_ORBIT_EPOCH_SECONDS"):
             sim.t = float(env["QD_ORBIT_EPOCH_SECONDS"])
