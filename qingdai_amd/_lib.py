@@ -64,7 +64,16 @@ class qd_phyto_daily_params(ctypes.Structure):
                                                  "alpha_clip_max", "dt_days")])
 
 
-PHYTO_DAILY_LOG_W = 4
+SPAN_LOG_CAP = 4096          # records a span lane's device log holds between two drains (csrc/qd_span.h: QD_SPAN_LOG_CAP is the same number)
+PHYTO_DAILY_LOG_W = 4        # doubles per [PhytoDiag] record
+ROUTE_LOG_W = 8              # doubles per routing event record (routing.LOG_KEYS)
+
+# qd_step_n flags (include/qingdai_hip.h): bit k switches STEP_BITS[k], named as Device.step_n's keywords
+STEP_BITS = ("with_ocean", "with_physics", "pass_albedo", "with_hydrology", "energy_diag", "ecology", "phyto", "routing", "phyto_daily")
+
+
+def step_flags(**on):
+    return sum(1 << STEP_BITS.index(k) for k, v in on.items() if v)
 
 
 class qd_route_plan(ctypes.Structure):
@@ -99,12 +108,10 @@ def load():
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     vp, dp, i32, i64, dbl, sz = (ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int64,
                                  ctypes.c_double, ctypes.c_size_t)
-    lib.qd_abi_version.restype = i32
-    lib.qd_device_count.restype = i32
+    ip, u8p = ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint8)
     lib.qd_create.argtypes = [ctypes.POINTER(qd_grid_desc), ctypes.POINTER(qd_params), dbl, ctypes.POINTER(vp)]
     lib.qd_destroy.argtypes = [vp]
     lib.qd_last_error.argtypes = [vp]
-    lib.qd_last_error.restype = ctypes.c_char_p
     lib.qd_upload.argtypes = [vp, i32, vp, sz]
     lib.qd_download.argtypes = [vp, i32, vp, sz]
     lib.qd_set_params.argtypes = [vp, ctypes.POINTER(qd_params), sz]
@@ -133,7 +140,6 @@ def load():
     lib.qd_energy_diagnostics_last.argtypes = [vp, dp]
     lib.qd_copy_ceiling.argtypes = [vp, sz, i32, dp]
     lib.qd_band_insolation.argtypes = [vp, i32, dp, dp, dp, vp]
-    ip = ctypes.POINTER(ctypes.c_int32)
     lib.qd_eco_configure.argtypes = [vp, ctypes.POINTER(qd_eco_params), sz]
     lib.qd_eco_set_lai_layers.argtypes = [vp, vp, i32, i32]
     lib.qd_eco_substep.argtypes = [vp, dbl]
@@ -150,8 +156,8 @@ def load():
     lib.qd_phyto_advect_diffuse.argtypes = [vp, dbl]
     lib.qd_phyto_daily_configure.argtypes = [vp, ctypes.POINTER(qd_phyto_daily_params), sz, dp, dp, dp]
     lib.qd_phyto_daily.argtypes = [vp, dp, i32]
-    lib.qd_phyto_daily_schedule.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int32)]
-    lib.qd_phyto_daily_log.argtypes = [vp, dp, i32, ctypes.POINTER(i32)]
+    lib.qd_phyto_daily_schedule.argtypes = [vp, i32, ip]
+    lib.qd_phyto_daily_log.argtypes = [vp, dp, i32, ip]
     lib.qd_phyto_daily_download_bands.argtypes = [vp, dp, sz]
     lib.qd_phyto_daily_state.argtypes = [vp, ctypes.POINTER(i64)]
     lib.qd_phyto_daily_insolation.argtypes = [vp, dp, dp, dp]
@@ -176,7 +182,6 @@ def load():
     lib.qd_peer_disable.argtypes = [vp]
     lib.qd_comm_peer_stats.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.qd_comm_peer_carried.argtypes = [vp]
-    ip = ctypes.POINTER(i32)
     lib.qd_plansim_create.argtypes = [ctypes.POINTER(qd_grid_desc), ctypes.POINTER(vp)]
     lib.qd_plansim_destroy.argtypes = [vp]
     lib.qd_plansim_plan.argtypes = [vp, ip, ip, i32, i32]
@@ -193,9 +198,7 @@ def load():
     lib.qd_route_schedule.argtypes = [vp, i32, dp]
     lib.qd_route_download.argtypes = [vp, i32, dp, sz]
     lib.qd_route_events.argtypes = [vp, dp, i32, ip]
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    lib.qd_hydronet_build.argtypes = [vp, i32, i32, u8p, dp, dbl, i32, dp, dp, dp, dbl, dp, i32p, i32p, u8p, i32p, i32p, i32,
+    lib.qd_hydronet_build.argtypes = [vp, i32, i32, u8p, dp, dbl, i32, dp, dp, dp, dbl, dp, ip, ip, u8p, ip, ip, i32,
                                       ip, ip]
     lib.qd_hydronet_sweeps.argtypes = [vp, ip]
     lib.qd_timing_enable.argtypes = [vp, i32]
@@ -203,9 +206,7 @@ def load():
     lib.qd_timing_get.argtypes = [vp, ctypes.c_char_p, dp, ctypes.POINTER(i64)]
     lib.qd_timing_reset.argtypes = [vp]
     for s in SYMBOLS:
-        fn = getattr(lib, s)
-        if s not in ("qd_last_error",):
-            fn.restype = i32
+        getattr(lib, s).restype = i32
     lib.qd_last_error.restype = ctypes.c_char_p
     _lib = lib
     return lib

@@ -1,5 +1,5 @@
 // qd_api.hip -- the C-ABI of include/qingdai_hip.h: context, memory, tables, operator seam.
-#include "qd_internal.h"
+#include "qd_span.h"
 #include <chrono>
 #include <atomic>
 #include <cstring>
@@ -687,20 +687,22 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     if (with_eco && !c->eco.configured) return qd_fail(c, "qd_step_n: bit5 set but qd_eco_configure has not been called");
     const int with_route = flags & 128;
     if (with_route && !with_hydro) return qd_fail(c, "qd_step_n: river routing (bit7) needs the hydrology commit (bit3)");
-    if (with_route && qd_route_span_check(c, n)) return -1;
-    // the schedule is for this span only, whatever way it ends
-    struct RouteGuard { qd_ctx* c; int on; ~RouteGuard() { if (on) qd_route_span_done(c); } } route_guard{c, with_route};
+    // whatever way this call ends: a lane's schedule was for this span only, and once the loop has begun the per-span switches are
+    // back to what a stand-alone qd_* call expects
+    struct SpanGuard { qd_ctx* c; QdSpanLane* route = nullptr; QdSpanLane* daily = nullptr; bool begun = false; ~SpanGuard() {
+        for (QdSpanLane* l : {route, daily}) if (l) l->clear_schedule();
+        if (begun) { c->diag_write = 1; c->want_pcond_ahead = 0; c->pcond_ahead = 0; c->defer_final = 0; c->final_pending.on = 0; qd_saf_drop(c); }
+    } } span{c};
+    if (with_route && !(span.route = qd_route_span_begin(c, n))) return -1;
     const int with_pdaily = flags & 256;
-    if (with_pdaily && qd_phyto_daily_span_check(c, n, with_phys)) return -1;
-    struct DailyGuard { qd_ctx* c; int on; ~DailyGuard() { if (on) qd_phyto_daily_span_done(c); } } daily_guard{c, with_pdaily};
-    // whatever way this call ends, the per-span switches are back to what a stand-alone qd_* call expects
-    struct SpanGuard { qd_ctx* c; ~SpanGuard() { c->diag_write = 1; c->want_pcond_ahead = 0; c->pcond_ahead = 0; c->defer_final = 0; c->final_pending.on = 0; qd_saf_drop(c); } } span_guard{c};
+    if (with_pdaily && !(span.daily = qd_phyto_daily_span_begin(c, n, with_phys))) return -1;
+    span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
         int rc;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
-        if (with_pdaily && qd_phyto_daily_fires(c, s) && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0, s))) return rc;
+        if (with_pdaily && span.daily->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
         // EcologyAdapter.step_subdaily sits between the glacier mask and the base-albedo blend (run_simulation.py:2075-2104):
         // its clock / canopy / alpha part runs before the albedo kernel, its E_day += isr dt rides on this step's forcing launch
         if (with_eco && c->eco.p.albedo_couple) { if ((rc = qd_eco_canopy_impl(c, dt))) return rc; c->eco.eday_dt = c->eco.p.use_lai ? dt : 0.0; }
@@ -733,7 +735,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // nothing the ocean step, the tracers, the individuals or the bucket touch, and writes only what the rest of step s + 1's
         // driver physics reads: it is queued inside the ocean step, between the stress kernel and the host's wait for the CFL maxima.
         // (not on a routing event step: the event reads this step's PRECIP, which the hoisted block would overwrite)
-        if (with_ocean && with_phys && c->geo.full && c->hoist_precip && s + 1 < n && !(with_route && qd_route_is_event(c, s)))
+        if (with_ocean && with_phys && c->geo.full && c->hoist_precip && s + 1 < n && !(with_route && span.route->at(s) != 0.0))
             c->before_cfl_wait = [c, dt]() { const int r = qd_driver_physics_impl(c, dt, nullptr, 1); if (!r) c->precip_done = 1; return r; };
         if (with_ocean) { rc = qd_ocean_step_impl(c, dt, 1, 1, 1); c->before_cfl_wait = nullptr; if (rc) return rc; }
         if (with_phyto && (rc = qd_phyto_step_impl(c, dt))) return rc;      // run_simulation.py:2254-2258

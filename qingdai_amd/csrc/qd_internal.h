@@ -442,15 +442,12 @@ void qd_eco_free(qd_ctx* c);
 int  qd_band_copy_in(qd_ctx* c, void* dst, const void* host, size_t esz);   // qd_api.hip
 int  qd_phyto_step_impl(qd_ctx* c, double dt);                              // qd_phyto.hip
 void qd_phyto_release(qd_ctx* c);
-int  qd_route_span_check(qd_ctx* c, int n);                                 // qd_route.hip
-int  qd_route_step_impl(qd_ctx* c, double dt, int s);
-int  qd_route_is_event(const qd_ctx* c, int s);                               // step s of the span routes
-void qd_route_span_done(qd_ctx* c);
+// span lanes (qd_span.h): *_span_begin checks the subsystem and its schedule against a span of n steps -> its lane, or nullptr (error set)
+struct QdSpanLane* qd_route_span_begin(qd_ctx* c, int n);                   // qd_route.hip
+int  qd_route_step_impl(qd_ctx* c, double dt, int s);                       // s: step of the span
 void qd_route_release(qd_ctx* c);
-int  qd_phyto_daily_span_check(qd_ctx* c, int n, int with_phys);              // qd_phyto_daily.hip
-int  qd_phyto_daily_step_impl(qd_ctx* c, const double* star_row, int use_sst, int s);   // s: step of the span (-1: stand-alone call)
-int  qd_phyto_daily_fires(const qd_ctx* c, int s);                            // step s of the span runs the daily step
-void qd_phyto_daily_span_done(qd_ctx* c);
+struct QdSpanLane* qd_phyto_daily_span_begin(qd_ctx* c, int n, int with_phys);   // qd_phyto_daily.hip
+int  qd_phyto_daily_step_impl(qd_ctx* c, const double* star_row, int use_sst);
 void qd_phyto_daily_release(qd_ctx* c);
 bool qd_phyto_daily_couples(const qd_ctx* c);                               // the albedo launches blend WATER_ALPHA into the ocean
 bool qd_eco_is_f32(const qd_ctx* c, int field);                             // qd_eco.hip: slab stored as f32 (qd_eco_params.map_f32)

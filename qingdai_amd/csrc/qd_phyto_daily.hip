@@ -15,13 +15,9 @@
 // of a qd_step_n step.  The band loops are unrolled over a register array of 16 (or 32) bands and guarded by n_bands; species are
 // a runtime loop (their planes are read twice: once for C_tot, once for the update).  The per-block cos-weighted partial sums of
 // the [PhytoDiag] line are finished by one workgroup into a device log the host drains after the span.
-#include "qd_internal.h"
+#include "qd_span.h"
 #include "qd_pointwise.h"
 #include <algorithm>
-#include <cmath>
-#include <vector>
-
-#define QD_PD_LOG_CAP 4096
 
 struct QdPhytoDaily {
     qd_phyto_daily_params p{};
@@ -30,10 +26,8 @@ struct QdPhytoDaily {
     int nb_alloc = 0;
     double* partial = nullptr;        // [3][nblk]
     int nblk = 0;
-    double* log = nullptr;            // [QD_PD_LOG_CAP][QD_PHYTO_DAILY_LOG_W]
-    int log_n = 0;
     int64_t n_steps = 0;
-    std::vector<int32_t> sched;       // qd_phyto_daily_schedule: 1 per firing step of the next span
+    QdSpanLane lane;                  // qd_phyto_daily_schedule: 1 per firing step of the next span; the [PhytoDiag] log
 };
 
 struct QdPDArgs {
@@ -222,7 +216,7 @@ k_phyto_daily_insolation(QdGeom G, QdTabs T, QdStar A, QdStar B, double theta, d
 // ------------------------------------------------------------------ host side
 static void pd_free(QdPhytoDaily* d) {
     if (!d) return;
-    void* p[] = {d->tab, d->bands, d->partial, d->log};
+    void* p[] = {d->tab, d->bands, d->partial, d->lane.log};
     for (void* q : p) if (q) hipFree(q);
     delete d;
 }
@@ -288,17 +282,17 @@ extern "C" int qd_phyto_daily_configure(qd_handle c, const qd_phyto_daily_params
         QD_HIP(c, hipMalloc(&d->partial, (size_t)3 * nblk * sizeof(double)));
         d->nblk = nblk;
     }
-    if (!d->log) QD_HIP(c, hipMalloc(&d->log, (size_t)QD_PD_LOG_CAP * QD_PHYTO_DAILY_LOG_W * sizeof(double)));
+    d->lane.width = QD_PHYTO_DAILY_LOG_W;
+    if (!d->lane.log) QD_HIP(c, hipMalloc(&d->lane.log, d->lane.log_doubles() * sizeof(double)));
     d->p = *p;
     QD_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
-int qd_phyto_daily_step_impl(qd_ctx* c, const double* st, int use_sst, int s) {
+int qd_phyto_daily_step_impl(qd_ctx* c, const double* st, int use_sst) {
     QdPhytoDaily* d = c->pdaily;
     if (c->phyto.S != d->p.n_species) return qd_fail(c, "qd_phyto_daily: the resident tracers changed their species count since the configure");
-    if (d->log_n >= QD_PD_LOG_CAP) return qd_fail(c, "qd_phyto_daily: diagnostic log full (drain it with qd_phyto_daily_log)");
-    (void)s;
+    if (d->lane.full()) return qd_fail(c, "qd_phyto_daily: diagnostic log full (drain it with qd_phyto_daily_log)");
     QdScope sc(c, "phyto_daily");
     QdPDArgs K;
     K.G = qd_segments(c, 0).g[0];
@@ -317,8 +311,7 @@ int qd_phyto_daily_step_impl(qd_ctx* c, const double* st, int use_sst, int s) {
     else hipLaunchKernelGGL(k_phyto_daily<32>, grid, dim3(QD_BLOCK), 0, c->stream, K);
     d->n_steps += 1;
     hipLaunchKernelGGL(k_phyto_daily_finish, dim3(1), dim3(QD_BLOCK), 0, c->stream, d->partial, (int)(grid.x * grid.y), c->tabs.warea,
-                       c->geo.nlat, c->geo.nlon, (double)d->n_steps, d->log + (size_t)d->log_n * QD_PHYTO_DAILY_LOG_W);
-    d->log_n += 1;
+                       c->geo.nlat, c->geo.nlon, (double)d->n_steps, d->lane.next());
     for (int k = 0; k < c->phyto.S; ++k) qd_mark(c, {c->phyto.cur[k]}, 0);
     qd_mark(c, {c->f[QD_F_PHYTO_N], c->f[QD_F_KD490], c->f[QD_F_WATER_ALPHA]}, 0);
     return 0;
@@ -329,7 +322,7 @@ extern "C" int qd_phyto_daily(qd_handle c, const double* star_row, int use_sst) 
     if (!pd_whole_globe(c)) return qd_fail(c, "qd_phyto_daily: the daily phytoplankton step needs a whole-globe handle; latitude bands are not supported");
     if (!c->pdaily) return qd_fail(c, "qd_phyto_daily: qd_phyto_daily_configure has not been called");
     hipSetDevice(c->desc.device);
-    int rc = qd_phyto_daily_step_impl(c, star_row, use_sst ? 1 : 0, -1);
+    int rc = qd_phyto_daily_step_impl(c, star_row, use_sst ? 1 : 0);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return qd_fail(c, "qd_phyto_daily: launch", e);
@@ -339,46 +332,28 @@ extern "C" int qd_phyto_daily(qd_handle c, const double* star_row, int use_sst) 
 extern "C" int qd_phyto_daily_schedule(qd_handle c, int n, const int32_t* fire) {
     if (!c || n < 0 || (n && !fire)) return -1;
     if (!c->pdaily) return qd_fail(c, "qd_phyto_daily_schedule: qd_phyto_daily_configure has not been called");
-    c->pdaily->sched.assign(fire, fire + n);
+    c->pdaily->lane.set(fire, n);
     return 0;
 }
 
-int qd_phyto_daily_span_check(qd_ctx* c, int n, int with_phys) {
-    if (!pd_whole_globe(c))
-        return qd_fail(c, "qd_step_n: the daily phytoplankton step (bit8) needs a whole-globe handle; latitude bands are not supported");
+QdSpanLane* qd_phyto_daily_span_begin(qd_ctx* c, int n, int with_phys) {
+    const char* why = nullptr;
     QdPhytoDaily* d = c->pdaily;
-    if (!d) return qd_fail(c, "qd_step_n: bit8 set but qd_phyto_daily_configure has not been called");
-    if (!with_phys) return qd_fail(c, "qd_step_n: the daily phytoplankton step (bit8) needs the driver physics (bit1)");
-    if ((int)d->sched.size() != n) return qd_fail(c, "qd_step_n: bit8 needs a qd_phyto_daily_schedule of exactly n steps before the span");
-    if (c->phyto.S != d->p.n_species) return qd_fail(c, "qd_step_n: the resident tracers changed their species count since qd_phyto_daily_configure");
-    int ev = 0;
-    for (int32_t x : d->sched) ev += x != 0;
-    if (d->log_n + ev > QD_PD_LOG_CAP) return qd_fail(c, "qd_step_n: the span's daily steps would overflow the diagnostic log (drain it first)");
-    return 0;
+    if (!pd_whole_globe(c)) why = "qd_step_n: the daily phytoplankton step (bit8) needs a whole-globe handle; latitude bands are not supported";
+    else if (!d) why = "qd_step_n: bit8 set but qd_phyto_daily_configure has not been called";
+    else if (!with_phys) why = "qd_step_n: the daily phytoplankton step (bit8) needs the driver physics (bit1)";
+    else if (!d->lane.scheduled(n)) why = "qd_step_n: bit8 needs a qd_phyto_daily_schedule of exactly n steps before the span";
+    else if (c->phyto.S != d->p.n_species) why = "qd_step_n: the resident tracers changed their species count since qd_phyto_daily_configure";
+    else if (!d->lane.fits()) why = "qd_step_n: the span's daily steps would overflow the diagnostic log (drain it first)";
+    if (why) qd_fail(c, why);
+    return why ? nullptr : &d->lane;
 }
-
-int qd_phyto_daily_fires(const qd_ctx* c, int s) {
-    return c->pdaily && s < (int)c->pdaily->sched.size() && c->pdaily->sched[s] != 0;
-}
-
-void qd_phyto_daily_span_done(qd_ctx* c) { if (c->pdaily) c->pdaily->sched.clear(); }
 
 extern "C" int qd_phyto_daily_log(qd_handle c, double* out, int max, int* n) {
     if (!c || !n) return -1;
     QdPhytoDaily* d = c->pdaily;
     if (!d) return qd_fail(c, "qd_phyto_daily_log: qd_phyto_daily_configure has not been called");
-    if (d->log_n > max) return qd_fail(c, "qd_phyto_daily_log: more records than room");
-    hipSetDevice(c->desc.device);
-    if (d->log_n) {
-        if (!out) return -1;
-        QD_HIP(c, hipMemcpyAsync(out, d->log, (size_t)d->log_n * QD_PHYTO_DAILY_LOG_W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
-    QD_HIP(c, hipStreamSynchronize(c->stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_phyto_daily_log: kernel", e);
-    *n = d->log_n;
-    d->log_n = 0;
-    return 0;
+    return d->lane.drain(c, "qd_phyto_daily_log", out, max, n);
 }
 
 extern "C" int qd_phyto_daily_download_bands(qd_handle c, double* host, size_t n) {

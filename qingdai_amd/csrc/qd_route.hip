@@ -15,13 +15,11 @@
 // -- the reference's own f64 additions in its own order, so the flow map is bit-identical.  There are no atomics on the
 // accumulation path and every reduction has a fixed order: the results do not depend on scheduling.
 // Whole-globe handles only (the network is global; routing across latitude bands is not built).
-#include "qd_internal.h"
-#include <vector>
+#include "qd_span.h"
 
 #define QD_ROUTE_BLOCK 256
 #define QD_ROUTE_LVL_BLOCK 1024
 #define QD_ROUTE_RED_BLOCKS 1024
-#define QD_ROUTE_LOG_CAP 4096
 #define QD_ROUTE_WIDE_LEVELS 4    // at most this many levels go out as wide launches ...
 #define QD_ROUTE_WIDE_MIN 2048    // ... and beyond level 0 only while a level holds this many segments
 #define QD_ROUTE_LOG_W 8          // step, event_dt, ocean_kgps, closure, input, ocean_kg, residual, lake_delta
@@ -37,11 +35,10 @@ struct QdRoute {
     int32_t* jp_start = nullptr; int32_t* jp_cells = nullptr;
     int32_t* lake_start = nullptr; int32_t* lake_cells = nullptr; double* lake_frac = nullptr;
     double* buf = nullptr; double* M = nullptr; double* flow = nullptr; double* lake_vol = nullptr;
-    double* partial = nullptr; double* log = nullptr;
+    double* partial = nullptr;
     int red_blocks = 0;
-    int log_n = 0;                        // records queued since the last qd_route_events
     int64_t steps = 0;                    // accumulations since configure / reset
-    std::vector<double> sched;            // qd_route_schedule: event_dt per step of the next qd_step_n span (0: none)
+    QdSpanLane lane;                      // qd_route_schedule: event_dt per step of the next span (0: none); the event log
 };
 
 // ------------------------------------------------------------------ kernels
@@ -188,7 +185,7 @@ k_route_final(int nb, const double* __restrict__ partial, int n_lakes, const int
 // ------------------------------------------------------------------ host side
 static void qr_free(QdRoute* r) {
     void* ptrs[] = {r->cflags, r->area_row, r->code, r->seg_start, r->seg_cells, r->level_start, r->jp_start, r->jp_cells,
-                    r->lake_start, r->lake_cells, r->lake_frac, r->buf, r->M, r->flow, r->lake_vol, r->partial, r->log};
+                    r->lake_start, r->lake_cells, r->lake_frac, r->buf, r->M, r->flow, r->lake_vol, r->partial, r->lane.log};
     for (void* p : ptrs) if (p) hipFree(p);
     delete r;
 }
@@ -271,7 +268,7 @@ extern "C" int qd_route_configure(qd_handle c, const qd_route_plan* p, size_t pl
     QdRoute* r = new QdRoute();
     r->nlat = c->geo.nlat; r->nlon = c->geo.nlon; r->cells = cells;
     r->n_seg = p->n_seg; r->n_seg_cells = p->n_seg_cells; r->n_levels = p->n_levels; r->n_jp = p->n_jp;
-    r->n_lakes = p->n_lakes; r->pe_lakes = p->pe_lakes;
+    r->n_lakes = p->n_lakes; r->pe_lakes = p->pe_lakes; r->lane.width = QD_ROUTE_LOG_W;
     r->lvl.assign(p->level_start, p->level_start + (p->n_levels ? p->n_levels + 1 : 0));
     r->red_blocks = (int)std::min<size_t>(QD_ROUTE_RED_BLOCKS, (cells + QD_ROUTE_BLOCK - 1) / QD_ROUTE_BLOCK);
     const int nlk = p->n_lakes ? p->lake_start[p->n_lakes] : 0;
@@ -287,7 +284,7 @@ extern "C" int qd_route_configure(qd_handle c, const qd_route_plan* p, size_t pl
               qr_up(c, &r->lake_frac, p->lake_frac, (size_t)p->n_lakes) &&
               qr_zero(c, &r->buf, cells) && qr_zero(c, &r->M, cells) && qr_zero(c, &r->flow, cells) &&
               qr_zero(c, &r->lake_vol, (size_t)p->n_lakes) && qr_zero(c, &r->partial, 4 * (size_t)r->red_blocks) &&
-              qr_zero(c, &r->log, (size_t)QD_ROUTE_LOG_CAP * QD_ROUTE_LOG_W);
+              qr_zero(c, &r->lane.log, r->lane.log_doubles());
     // the host arrays are the caller's: the copies finish before this returns
     ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) { hipStreamSynchronize(c->stream); qr_free(r); return qd_fail(c, "qd_route_configure: device allocation or upload failed"); }
@@ -304,7 +301,7 @@ extern "C" int qd_route_reset(qd_handle c) {
     QD_HIP(c, hipMemsetAsync(r->flow, 0, r->cells * sizeof(double), c->stream));
     if (r->n_lakes) QD_HIP(c, hipMemsetAsync(r->lake_vol, 0, r->n_lakes * sizeof(double), c->stream));
     QD_HIP(c, hipStreamSynchronize(c->stream));
-    r->log_n = 0; r->steps = 0; r->sched.clear();
+    r->steps = 0; r->lane.reset();
     return 0;
 }
 
@@ -319,7 +316,7 @@ static int qr_accumulate(qd_ctx* c, double dt) {
 
 static int qr_event(qd_ctx* c, double event_dt, int with_pe) {
     QdRoute* r = c->route;
-    if (r->log_n >= QD_ROUTE_LOG_CAP) return qd_fail(c, "qd_route: event log full (drain it with qd_route_events)");
+    if (r->lane.full()) return qd_fail(c, "qd_route: event log full (drain it with qd_route_events)");
     QdScope sc(c, "route_event");
     const double dt_den = std::max(event_dt, 1e-9);
     const int pe = (with_pe && r->pe_lakes && r->n_lakes > 0) ? 1 : 0;
@@ -340,8 +337,7 @@ static int qr_event(qd_ctx* c, double event_dt, int with_pe) {
                        r->flow, (const double*)c->f[QD_F_PRECIP], (const double*)c->f[QD_F_EFLUX], pe, event_dt, dt_den, r->partial);
     hipLaunchKernelGGL(k_route_final, dim3(1), dim3(QD_ROUTE_BLOCK), 0, c->stream, r->red_blocks, (const double*)r->partial, r->n_lakes,
                        (const int32_t*)r->lake_start, (const int32_t*)r->lake_cells, (const double*)r->lake_frac, (const double*)r->M,
-                       r->lake_vol, pe, event_dt, dt_den, (double)r->steps, r->log + (size_t)r->log_n * QD_ROUTE_LOG_W);
-    r->log_n += 1;
+                       r->lake_vol, pe, event_dt, dt_den, (double)r->steps, r->lane.next());
     return 0;
 }
 
@@ -369,31 +365,26 @@ extern "C" int qd_route_event(qd_handle c, double event_dt, int with_pe) {
 extern "C" int qd_route_schedule(qd_handle c, int n, const double* event_dt) {
     if (!c || n < 0 || (n && !event_dt)) return -1;
     if (!c->route) return qd_fail(c, "qd_route_schedule: no network configured (qd_route_configure first)");
-    c->route->sched.assign(event_dt, event_dt + n);
+    c->route->lane.set(event_dt, n);
     return 0;
 }
 
-int qd_route_span_check(qd_ctx* c, int n) {
+QdSpanLane* qd_route_span_begin(qd_ctx* c, int n) {
+    const char* why = nullptr;
     QdRoute* r = c->route;
-    if (!c->geo.full || c->desc.world > 1) return qd_fail(c, "qd_step_n: river routing (bit7) needs a whole-globe handle; routing across latitude bands is not supported");
-    if (!r) return qd_fail(c, "qd_step_n: bit7 set but qd_route_configure has not been called");
-    if ((int)r->sched.size() != n) return qd_fail(c, "qd_step_n: bit7 needs a qd_route_schedule of exactly n steps before the span");
-    int ev = 0;
-    for (double x : r->sched) ev += x != 0.0;
-    if (r->log_n + ev > QD_ROUTE_LOG_CAP) return qd_fail(c, "qd_step_n: the span's routing events would overflow the event log (drain it first)");
-    return 0;
+    if (!c->geo.full || c->desc.world > 1) why = "qd_step_n: river routing (bit7) needs a whole-globe handle; routing across latitude bands is not supported";
+    else if (!r) why = "qd_step_n: bit7 set but qd_route_configure has not been called";
+    else if (!r->lane.scheduled(n)) why = "qd_step_n: bit7 needs a qd_route_schedule of exactly n steps before the span";
+    else if (!r->lane.fits()) why = "qd_step_n: the span's routing events would overflow the event log (drain it first)";
+    if (why) qd_fail(c, why);
+    return why ? nullptr : &r->lane;
 }
 
 int qd_route_step_impl(qd_ctx* c, double dt, int s) {
-    QdRoute* r = c->route;
     qr_accumulate(c, dt);
-    const double ev = r->sched[s];
+    const double ev = c->route->lane.at(s);
     return ev != 0.0 ? qr_event(c, ev, 1) : 0;
 }
-
-int qd_route_is_event(const qd_ctx* c, int s) { return c->route && s < (int)c->route->sched.size() && c->route->sched[s] != 0.0; }
-
-void qd_route_span_done(qd_ctx* c) { if (c->route) c->route->sched.clear(); }
 
 extern "C" int qd_route_download(qd_handle c, int which, double* host, size_t n) {
     if (!c || !host) return -1;
@@ -413,16 +404,5 @@ extern "C" int qd_route_events(qd_handle c, double* out, int max, int* n) {
     if (!c || !n) return -1;
     QdRoute* r = c->route;
     if (!r) return qd_fail(c, "qd_route_events: no network configured");
-    if (r->log_n > max) return qd_fail(c, "qd_route_events: more records than room");
-    hipSetDevice(c->desc.device);
-    if (r->log_n) {
-        if (!out) return -1;
-        QD_HIP(c, hipMemcpyAsync(out, r->log, (size_t)r->log_n * QD_ROUTE_LOG_W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
-    QD_HIP(c, hipStreamSynchronize(c->stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_route_events: kernel", e);
-    *n = r->log_n;
-    r->log_n = 0;
-    return 0;
+    return r->lane.drain(c, "qd_route_events", out, max, n);
 }

@@ -140,47 +140,25 @@ class Device:
         self.flush()
         st = np.ascontiguousarray(stars, dtype=np.float64)
         assert st.ndim == 2 and st.shape[1] == 7
-        flags = ((1 if with_ocean else 0) | (2 if with_physics else 0) | (4 if pass_albedo else 0) | (8 if with_hydrology else 0) |
-                 (16 if energy_diag else 0) | (32 if ecology else 0) | (64 if phyto else 0) | (128 if routing is not None else 0) |
-                 (256 if phyto_daily is not None else 0))
+        n = int(st.shape[0])
+        lanes = [p for p in (phyto_daily, routing) if p is not None]          # the span's participants (csrc/qd_span.h)
+        for p in lanes:
+            if p.dev is not self:
+                raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
+        if phyto_daily is not None and t0 is None:
+            raise ValueError("step_n: phyto_daily needs the span's start time t0")
+        flags = _lib.step_flags(with_ocean=with_ocean, with_physics=with_physics, pass_albedo=pass_albedo, with_hydrology=with_hydrology,
+                                energy_diag=energy_diag, ecology=ecology, phyto=phyto, routing=routing is not None, phyto_daily=phyto_daily is not None)
+        clocks = [p.span_clock() for p in lanes]
+        try:
+            fired = [p.span_schedule(t0, float(dt), n) for p in lanes]      # each uploads its schedule for this span
+            self._chk(self.lib.qd_step_n(self.h, n, float(dt), flags, st.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "qd_step_n")
+        except Exception:
+            for p, clock in zip(lanes, clocks):                               # nothing ran: every host clock back to before the call
+                p.span_restore(clock)
+            raise
         if phyto_daily is not None:
-            if phyto_daily.dev is not self:
-                raise ValueError("step_n: the PhytoDaily runs on another device handle")
-            if t0 is None:
-                raise ValueError("step_n: phyto_daily needs the span's start time t0")
-            clock = phyto_daily.phyto_next_time
-            fire = np.ascontiguousarray(phyto_daily.schedule(float(t0), float(dt), st.shape[0]), dtype=np.int32)
-            rc = self.lib.qd_phyto_daily_schedule(self.h, int(fire.size), fire.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-            if rc != 0:
-                phyto_daily.phyto_next_time = clock
-                self._chk(rc, "qd_phyto_daily_schedule")
-            if routing is None:
-                rc = self.lib.qd_step_n(self.h, int(st.shape[0]), float(dt), flags, st.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
-                if rc != 0:
-                    phyto_daily.phyto_next_time = clock
-                    self._chk(rc, "qd_step_n")
-                phyto_daily._fired(int(fire.sum()))
-                return
-        if routing is not None:
-            if routing.dev is not self:
-                raise ValueError("step_n: the RiverRouting runs on another device handle")
-            t0_acc, s0 = routing.t_accum, routing._steps
-            ev = np.ascontiguousarray(routing.schedule(dt, st.shape[0]))
-            rc = self.lib.qd_route_schedule(self.h, int(ev.size), ev.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
-            if rc != 0:
-                routing.t_accum, routing._steps = t0_acc, s0
-                self._chk(rc, "qd_route_schedule")
-            rc = self.lib.qd_step_n(self.h, int(st.shape[0]), float(dt), flags, st.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
-            if rc != 0:
-                routing.t_accum, routing._steps = t0_acc, s0
-                if phyto_daily is not None:
-                    phyto_daily.phyto_next_time = clock
-                self._chk(rc, "qd_step_n")
-            if phyto_daily is not None:
-                phyto_daily._fired(int(fire.sum()))
-            return
-        self._chk(self.lib.qd_step_n(self.h, int(st.shape[0]), float(dt), flags,
-                                     st.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "qd_step_n")
+            phyto_daily._fired(fired[0])
 
     def sync(self):
         self._chk(self.lib.qd_sync(self.h), "qd_sync")
@@ -222,15 +200,21 @@ class Device:
                   "qd_route_download")
         return out
 
+    def route_schedule(self, event_dt):
+        ev = _c(event_dt)
+        self._chk(self.lib.qd_route_schedule(self.h, int(ev.size), ev.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "qd_route_schedule")
+
+    def _drain(self, fn, width, what):
+        """A span lane's device log (csrc/qd_span.h) -> [n][width] records, oldest first; the log is empty afterwards."""
+        buf = np.empty((_lib.SPAN_LOG_CAP, width), dtype=np.float64)
+        n = ctypes.c_int32(0)
+        self._chk(fn(self.h, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.SPAN_LOG_CAP, ctypes.byref(n)), what)
+        return buf[:n.value].copy()
+
     def route_events(self):
         """Drain the device event log -> list of dicts (routing.LOG_KEYS), oldest first."""
         from .routing import LOG_KEYS
-        cap = 4096
-        buf = np.zeros((cap, len(LOG_KEYS)), dtype=np.float64)
-        n = ctypes.c_int32(0)
-        self._chk(self.lib.qd_route_events(self.h, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cap, ctypes.byref(n)),
-                  "qd_route_events")
-        out = [dict(zip(LOG_KEYS, (float(x) for x in row))) for row in buf[:n.value]]
+        out = [dict(zip(LOG_KEYS, (float(x) for x in row))) for row in self._drain(self.lib.qd_route_events, _lib.ROUTE_LOG_W, "qd_route_events")]
         if out:
             self._route_last = out[-1]
         return out
@@ -238,7 +222,6 @@ class Device:
     def route_last_event(self):
         return self._route_last
 
-    # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident
     # ---- daily phytoplankton step (qd_phyto_daily.hip)
     def phyto_daily_configure(self, params, band_tab, species_tab, shape):
         keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (band_tab, species_tab, shape)]
@@ -252,14 +235,13 @@ class Device:
         self._chk(self.lib.qd_phyto_daily(self.h, row.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 1 if use_sst else 0),
                   "qd_phyto_daily")
 
+    def phyto_daily_schedule(self, fire):
+        f = _c(fire, np.int32)
+        self._chk(self.lib.qd_phyto_daily_schedule(self.h, int(f.size), f.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "qd_phyto_daily_schedule")
+
     def phyto_daily_log(self):
         """Drain the [PhytoDiag] records -> [n][4] (daily steps so far, <C_tot>, <Kd490>, <alpha_water>)."""
-        n = ctypes.c_int(0)
-        cap = 4096
-        out = np.empty((cap, _lib.PHYTO_DAILY_LOG_W), dtype=np.float64)
-        self._chk(self.lib.qd_phyto_daily_log(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cap, ctypes.byref(n)),
-                  "qd_phyto_daily_log")
-        return out[:n.value].copy()
+        return self._drain(self.lib.qd_phyto_daily_log, _lib.PHYTO_DAILY_LOG_W, "qd_phyto_daily_log")
 
     def phyto_daily_bands(self, nb):
         out = np.empty((nb,) + self.shape, dtype=np.float64)
@@ -272,6 +254,7 @@ class Device:
         self._chk(self.lib.qd_phyto_daily_state(self.h, ctypes.byref(n)), "qd_phyto_daily_state")
         return int(n.value)
 
+    # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident
     def phyto_configure(self, n_species, K_h, adv_alpha):
         self._chk(self.lib.qd_phyto_configure(self.h, int(n_species), float(K_h), float(adv_alpha)), "qd_phyto_configure")
         self._phyto_S = int(n_species)

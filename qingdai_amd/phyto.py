@@ -357,6 +357,18 @@ class PhytoDaily:
         fire, self.phyto_next_time = daily_schedule(self.phyto_next_time, t0, dt, n, self.day_seconds)
         return fire
 
+    # ---- span participant (Device.step_n): the host clock before the span, this span's schedule to the device, the clock put back
+    def span_clock(self):
+        return self.phyto_next_time
+
+    def span_schedule(self, t0, dt, n):
+        fire = self.schedule(float(t0), dt, n)
+        self.dev.phyto_daily_schedule(fire)
+        return int(fire.sum())                 # -> the span's daily steps, for _fired once the span has run
+
+    def span_restore(self, clock):
+        self.phyto_next_time = clock
+
     def print_diag(self, records):
         if self.diag:
             for rec in records:

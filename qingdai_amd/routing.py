@@ -32,7 +32,7 @@ from .params import PLANET_RADIUS
 T_OCEAN, T_VOID, T_DEAD, T_NOTPROC, T_LAKE0 = -1, -2, -3, -4, -5
 
 LOG_KEYS = ("step", "event_dt", "ocean_inflow_kgps", "mass_closure_error_kg", "mass_input_kg", "ocean_kg", "residual_kg",
-            "lake_delta_kg")
+            "lake_delta_kg")                   # one event record of the device log: _lib.ROUTE_LOG_W doubles
 
 
 @dataclass
@@ -352,6 +352,16 @@ class RiverRouting:
                 self.t_accum = 0.0
         self._steps += n
         return ev
+
+    # ---- span participant (Device.step_n): the host clock before the span, this span's schedule to the device, the clock put back
+    def span_clock(self):
+        return self.t_accum, self._steps
+
+    def span_schedule(self, t0, dt, n):
+        self.dev.route_schedule(self.schedule(dt, n))
+
+    def span_restore(self, clock):
+        self.t_accum, self._steps = clock
 
     def step(self, R_land_flux, dt_seconds, precip_flux=None, evap_flux=None):
         """routing.py:199-312 on host arrays: upload, accumulate on the device, route when the window is full."""
