@@ -64,6 +64,8 @@ enum qd_field {
      * total LAI, its snapshot at the last canopy recompute, cached canopy factor f, daily energy buffer, land-only
      * ecology alpha (NaN elsewhere), daily banded alpha, ocean-colour alpha of the phytoplankton coupling */
     QD_F_ECO_LAI, QD_F_ECO_LAI_SNAP, QD_F_ECO_F, QD_F_ECO_EDAY, QD_F_ECO_ALPHA, QD_F_ECO_ALPHA_BANDED, QD_F_WATER_ALPHA,
+    /* daily vegetation step (population.py:389-596): age_days, seed_bank, _spread_gate */
+    QD_F_ECO_AGE, QD_F_ECO_SEEDBANK, QD_F_ECO_GATE,
     /* daily phytoplankton step (phyto.py:339-435): nutrient pool N (mmol m^-3), Kd(490) (m^-1) */
     QD_F_PHYTO_N, QD_F_KD490,
     QD_F_COUNT_F64,
@@ -154,7 +156,7 @@ int qd_driver_physics(qd_handle h, double dt);
 int qd_hydrology_commit(qd_handle h, double dt);
 /* benchmark_jax.py:124-158 as one resident loop of n steps: forcing -> albedo -> time_step [-> ocean
  * coupling] [-> hydrology commit].  flags bit0 = with_ocean, bit1 = with_driver_physics (else the simple
- * ocean/land albedo of benchmark_jax.py:129), bit2 = pass albedo to time_step, bit3 = hydrology commit, bit4 = energy diagnostics on the first step (qd_energy_diagnostics_last), bit5 = ecology sub-step (qd_eco_substep, and qd_indiv_substep when a pool is configured; needs bit1), bit6 = tracer transport after the ocean step (qd_phyto_advect_diffuse; needs bit0 and qd_phyto_configure), bit7 = river routing after the hydrology commit (qd_route_accumulate, and qd_route_event on the steps a qd_route_schedule of n entries names; needs bit3 and qd_route_configure), bit8 = daily phytoplankton step at the top of the steps a qd_phyto_daily_schedule of n entries names (SST with bit0, else TS; needs bit1 and qd_phyto_daily_configure).  `stars` holds n rows of 7 host scalars
+ * ocean/land albedo of benchmark_jax.py:129), bit2 = pass albedo to time_step, bit3 = hydrology commit, bit4 = energy diagnostics on the first step (qd_energy_diagnostics_last), bit5 = ecology sub-step (qd_eco_substep, and qd_indiv_substep when a pool is configured; needs bit1), bit6 = tracer transport after the ocean step (qd_phyto_advect_diffuse; needs bit0 and qd_phyto_configure), bit7 = river routing after the hydrology commit (qd_route_accumulate, and qd_route_event on the steps a qd_route_schedule of n entries names; needs bit3 and qd_route_configure), bit8 = daily phytoplankton step at the top of the steps a qd_phyto_daily_schedule of n entries names (SST with bit0, else TS; needs bit1 and qd_phyto_daily_configure), bit9 = daily vegetation step at the top of the steps a qd_eco_daily_schedule of n entries names (needs bit5 and qd_eco_daily_configure).  `stars` holds n rows of 7 host scalars
  * (flux_A, decl_A, ra_A, flux_B, decl_B, ra_B, theta), evaluated by the caller as forcing.py:85-125 does. */
 int qd_step_n(qd_handle h, int n, double dt, int flags, const double* stars);
 int qd_last_ocean_nsub(qd_handle h, int* n_sub);
@@ -281,6 +283,44 @@ int qd_phyto_daily_download_bands(qd_handle h, double* host, size_t n); /* [n_ba
 int qd_phyto_daily_state(qd_handle h, int64_t* n_steps);                /* daily steps run since the configure */
 /* the two per-star insolation maps [n_lat][n_lon] the daily kernel evaluates for a star row (checks against qd_forcing) */
 int qd_phyto_daily_insolation(qd_handle h, const double* star_row, double* insA, double* insB);
+
+/* ---- daily vegetation step (PopulationManager.step_daily, pygcm/ecology/population.py:389-828), whole-globe handles --------
+ * One firing: growth from E_day and senescence under soil-water stress, the layered Beer-Lambert allocation (K > 1), per-species
+ * neighbour / seed spread in species order, age, soil-gated germination from the seed bank, its decay, ECO_LAI = sum of the
+ * layers, E_day = 0; all f64 in the reference's operation order.  The [n_species][K][n_lat][n_lon] LAI stack is resident
+ * (qd_eco_daily_set_layers / _get_layers); ECO_AGE, ECO_SEEDBANK and ECO_GATE are ordinary fields.  A firing leaves the canopy
+ * state as qd_eco_set_lai_layers(h, layers, n, 0) does (snapshot and recompute clock untouched) and appends one record of
+ * QD_ECO_DAILY_LOG_W = 4 doubles to a device log: {firings so far, LAI_min, LAI_mean, LAI_max} over land (summary(),
+ * population.py:947-957; zeros without land).  Mutation, genes and the individuals' daily step are not part of it. */
+#define QD_ECO_DAILY_LOG_W 4
+#define QD_ECO_DAILY_MAX_K 8
+typedef struct qd_eco_daily_params {
+    int32_t n_species, n_layers;      /* Ns (1..64), QD_ECO_COHORT_K (1..8) */
+    int32_t spread;                   /* QD_ECO_SPREAD_ENABLE == 1 and QD_ECO_SPREAD_RATE > 0 */
+    int32_t moore;                    /* QD_ECO_SPREAD_NEIGHBORS in moore / 8 / 8n, else von Neumann */
+    int32_t gate_soil;                /* QD_ECO_SPREAD_GATE_SOIL */
+    int32_t reserved;
+    double lai_max, k_canopy, growth_per_j, senesce_per_day, stress_thresh, stress_strength;   /* LAIParams */
+    double soil_cap;                  /* QD_ECO_SOIL_WATER_CAP: soil = clip(W_LAND / max(1e-6, cap), 0, 1), 0 on GLACIER */
+    double repro_frac;                /* clip(QD_ECO_REPRO_FRACTION, 0, 0.95) */
+    double spread_rate;               /* clip(QD_ECO_SPREAD_RATE, 0, 0.5) */
+    double soil_exp, upfrac, dlai_max;
+    double seed_energy, seed_scale;   /* max(1e-12, .) */
+    double seedling_lai, retain, bank_max, seed_dlai_max, germ_frac, bank_decay;
+} qd_eco_daily_params;
+/* species_mode [n_species]: 0 diffusion, 1 seed; species_weights [n_species]: already divided by (their sum + 1e-12).
+ * The first call, and a call that changes n_species * n_layers, allocates the stack; every call zeroes ECO_AGE and ECO_SEEDBANK,
+ * the firing count and the log.  Refused on latitude bands. */
+int qd_eco_daily_configure(qd_handle h, const qd_eco_daily_params* p, size_t sizeof_params, const int32_t* species_mode,
+                           const double* species_weights);
+int qd_eco_daily_set_layers(qd_handle h, const double* layers, int n_planes);   /* [n_species * n_layers][n_lat][n_lon] */
+int qd_eco_daily_get_layers(qd_handle h, double* layers, int n_planes);
+/* one firing now.  soil_index NULL: from the resident W_LAND and GLACIER, as inside a span; else a host [n_lat][n_lon] map,
+ * the soil_water_index argument of step_daily */
+int qd_eco_daily_step(qd_handle h, const double* soil_index);
+int qd_eco_daily_schedule(qd_handle h, int n, const int32_t* fire);   /* the next qd_step_n span: firings at the top of each step */
+int qd_eco_daily_log(qd_handle h, double* out, int max, int* n);      /* drains the log: *n records of 4 doubles */
+int qd_eco_daily_state(qd_handle h, int64_t* n_firings);              /* firings since the configure */
 
 /* ---- river routing (P014, pygcm/routing.py), whole-globe handles ----------------------------------
  * The host plans the network once (qingdai_amd/routing.py: build_plan): per cell a target code (>= 0 a live edge to that

@@ -21,7 +21,7 @@ FIELDS = ["U", "V", "H", "TS", "Q", "CLOUD", "HICE", "ISR", "ISR_A", "ISR_B", "T
           "UO", "VO", "ETA", "SST", "QNET", "PRECIP", "CLOUD_FROM_P", "CLOUD_SRC", "W_LAND", "S_SNOW", "C_SNOW",
           "S_SNOW_NEXT", "MELT", "P_RAIN", "GLACIER", "RUNOFF",
           "ECO_LAI", "ECO_LAI_SNAP", "ECO_F", "ECO_EDAY", "ECO_ALPHA", "ECO_ALPHA_BANDED", "WATER_ALPHA",
-          "PHYTO_N", "KD490"]
+          "ECO_AGE", "ECO_SEEDBANK", "ECO_GATE", "PHYTO_N", "KD490"]
 F = {n: i for i, n in enumerate(FIELDS)}
 F["LAND_MASK"] = 100
 F["ICE_MASK"] = 101
@@ -43,6 +43,8 @@ SYMBOLS = [
     "qd_phyto_configure", "qd_phyto_upload", "qd_phyto_download", "qd_phyto_advect_diffuse",
     "qd_phyto_daily_configure", "qd_phyto_daily", "qd_phyto_daily_schedule", "qd_phyto_daily_log", "qd_phyto_daily_download_bands",
     "qd_phyto_daily_state", "qd_phyto_daily_insolation",
+    "qd_eco_daily_configure", "qd_eco_daily_set_layers", "qd_eco_daily_get_layers", "qd_eco_daily_step", "qd_eco_daily_schedule",
+    "qd_eco_daily_log", "qd_eco_daily_state",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
     "qd_hydronet_build", "qd_hydronet_sweeps",
@@ -64,12 +66,22 @@ class qd_phyto_daily_params(ctypes.Structure):
                                                  "alpha_clip_max", "dt_days")])
 
 
+class qd_eco_daily_params(ctypes.Structure):
+    """include/qingdai_hip.h: qd_eco_daily_params"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("n_species", "n_layers", "spread", "moore", "gate_soil", "reserved")] +
+                [(n, ctypes.c_double) for n in ("lai_max", "k_canopy", "growth_per_j", "senesce_per_day", "stress_thresh", "stress_strength",
+                                                 "soil_cap", "repro_frac", "spread_rate", "soil_exp", "upfrac", "dlai_max", "seed_energy",
+                                                 "seed_scale", "seedling_lai", "retain", "bank_max", "seed_dlai_max", "germ_frac",
+                                                 "bank_decay")])
+
+
 SPAN_LOG_CAP = 4096          # records a span lane's device log holds between two drains (csrc/qd_span.h: QD_SPAN_LOG_CAP is the same number)
 PHYTO_DAILY_LOG_W = 4        # doubles per [PhytoDiag] record
+ECO_DAILY_LOG_W = 4          # doubles per daily vegetation record {firings, LAI_min, LAI_mean, LAI_max}
 ROUTE_LOG_W = 8              # doubles per routing event record (routing.LOG_KEYS)
 
 # qd_step_n flags (include/qingdai_hip.h): bit k switches STEP_BITS[k], named as Device.step_n's keywords
-STEP_BITS = ("with_ocean", "with_physics", "pass_albedo", "with_hydrology", "energy_diag", "ecology", "phyto", "routing", "phyto_daily")
+STEP_BITS = ("with_ocean", "with_physics", "pass_albedo", "with_hydrology", "energy_diag", "ecology", "phyto", "routing", "phyto_daily", "eco_daily")
 
 
 def step_flags(**on):
@@ -161,6 +173,13 @@ def load():
     lib.qd_phyto_daily_download_bands.argtypes = [vp, dp, sz]
     lib.qd_phyto_daily_state.argtypes = [vp, ctypes.POINTER(i64)]
     lib.qd_phyto_daily_insolation.argtypes = [vp, dp, dp, dp]
+    lib.qd_eco_daily_configure.argtypes = [vp, ctypes.POINTER(qd_eco_daily_params), sz, ip, dp]
+    lib.qd_eco_daily_set_layers.argtypes = [vp, vp, i32]
+    lib.qd_eco_daily_get_layers.argtypes = [vp, vp, i32]
+    lib.qd_eco_daily_step.argtypes = [vp, vp]
+    lib.qd_eco_daily_schedule.argtypes = [vp, i32, ip]
+    lib.qd_eco_daily_log.argtypes = [vp, dp, i32, ip]
+    lib.qd_eco_daily_state.argtypes = [vp, ctypes.POINTER(i64)]
     lib.qd_comm_unique_id.argtypes = [vp, sz]
     lib.qd_comm_init.argtypes = [vp, vp, sz]
     lib.qd_comm_barrier.argtypes = [vp]

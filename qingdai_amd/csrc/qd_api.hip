@@ -472,6 +472,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_phyto_release(c);
     qd_route_release(c);
     qd_phyto_daily_release(c);
+    qd_eco_daily_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -689,13 +690,15 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     if (with_route && !with_hydro) return qd_fail(c, "qd_step_n: river routing (bit7) needs the hydrology commit (bit3)");
     // whatever way this call ends: a lane's schedule was for this span only, and once the loop has begun the per-span switches are
     // back to what a stand-alone qd_* call expects
-    struct SpanGuard { qd_ctx* c; QdSpanLane* route = nullptr; QdSpanLane* daily = nullptr; bool begun = false; ~SpanGuard() {
-        for (QdSpanLane* l : {route, daily}) if (l) l->clear_schedule();
+    struct SpanGuard { qd_ctx* c; QdSpanLane* route = nullptr; QdSpanLane* daily = nullptr; QdSpanLane* edaily = nullptr; bool begun = false; ~SpanGuard() {
+        for (QdSpanLane* l : {route, daily, edaily}) if (l) l->clear_schedule();
         if (begun) { c->diag_write = 1; c->want_pcond_ahead = 0; c->pcond_ahead = 0; c->defer_final = 0; c->final_pending.on = 0; qd_saf_drop(c); }
     } } span{c};
     if (with_route && !(span.route = qd_route_span_begin(c, n))) return -1;
     const int with_pdaily = flags & 256;
     if (with_pdaily && !(span.daily = qd_phyto_daily_span_begin(c, n, with_phys))) return -1;
+    const int with_edaily = flags & 512;
+    if (with_edaily && !(span.edaily = qd_eco_daily_span_begin(c, n, with_eco))) return -1;
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -703,6 +706,11 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
         if (with_pdaily && span.daily->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
+        // PopulationManager.step_daily (run_simulation.py:1786-1810) reads W_LAND, GLACIER and E_day as the previous step left them and
+        // writes the LAI stack, ECO_LAI and E_day before this step's canopy test and E_day accumulation; dt > day fires more than once.
+        // The hoisted precipitation block of this step (part 1) reads and writes none of these, so it stays hoisted on firing steps
+        if (with_edaily)
+            for (int r = (int)span.edaily->at(s); r > 0; --r) if ((rc = qd_eco_daily_step_impl(c, nullptr))) return rc;
         // EcologyAdapter.step_subdaily sits between the glacier mask and the base-albedo blend (run_simulation.py:2075-2104):
         // its clock / canopy / alpha part runs before the albedo kernel, its E_day += isr dt rides on this step's forcing launch
         if (with_eco && c->eco.p.albedo_couple) { if ((rc = qd_eco_canopy_impl(c, dt))) return rc; c->eco.eday_dt = c->eco.p.use_lai ? dt : 0.0; }

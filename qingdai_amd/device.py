@@ -130,25 +130,28 @@ class Device:
         self._chk(self.lib.qd_hydrology_commit(self.h, float(dt)), "qd_hydrology_commit")
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
-               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None):
+               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  `routing`: a RiverRouting on this handle -- bit7, after the
         hydrology commit (which it needs); the host's t_accum schedule names the event steps, and the span's
         event records stay in the device log (route_events) until the caller drains them.  `phyto_daily`: a phyto.PhytoDaily on
         this handle -- bit8; its firing clock turns the span's times t0 + dt * arange(n) into the schedule, and the span's
-        [PhytoDiag] records stay in the device log (phyto_daily_log) until the caller drains them."""
+        [PhytoDiag] records stay in the device log (phyto_daily_log) until the caller drains them.  `eco_daily`: an
+        ecology.PopulationDaily on this handle -- bit9 (needs `ecology`); its day accumulator names the firing steps, and the span's
+        LAI summaries stay in the device log (eco_daily_log) until the caller drains them."""
         self.flush()
         st = np.ascontiguousarray(stars, dtype=np.float64)
         assert st.ndim == 2 and st.shape[1] == 7
         n = int(st.shape[0])
-        lanes = [p for p in (phyto_daily, routing) if p is not None]          # the span's participants (csrc/qd_span.h)
+        lanes = [p for p in (phyto_daily, routing, eco_daily) if p is not None]          # the span's participants (csrc/qd_span.h)
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
         if phyto_daily is not None and t0 is None:
             raise ValueError("step_n: phyto_daily needs the span's start time t0")
         flags = _lib.step_flags(with_ocean=with_ocean, with_physics=with_physics, pass_albedo=pass_albedo, with_hydrology=with_hydrology,
-                                energy_diag=energy_diag, ecology=ecology, phyto=phyto, routing=routing is not None, phyto_daily=phyto_daily is not None)
+                                energy_diag=energy_diag, ecology=ecology, phyto=phyto, routing=routing is not None, phyto_daily=phyto_daily is not None,
+                                eco_daily=eco_daily is not None)
         clocks = [p.span_clock() for p in lanes]
         try:
             fired = [p.span_schedule(t0, float(dt), n) for p in lanes]      # each uploads its schedule for this span
@@ -157,8 +160,9 @@ class Device:
             for p, clock in zip(lanes, clocks):                               # nothing ran: every host clock back to before the call
                 p.span_restore(clock)
             raise
-        if phyto_daily is not None:
-            phyto_daily._fired(fired[0])
+        for p, k in zip(lanes, fired):
+            if p is not routing:
+                p._fired(k)
 
     def sync(self):
         self._chk(self.lib.qd_sync(self.h), "qd_sync")
@@ -252,6 +256,43 @@ class Device:
     def phyto_daily_steps(self):
         n = ctypes.c_int64(0)
         self._chk(self.lib.qd_phyto_daily_state(self.h, ctypes.byref(n)), "qd_phyto_daily_state")
+        return int(n.value)
+
+    # ---- daily vegetation step (qd_eco_daily.hip)
+    def eco_daily_configure(self, params, species_mode, species_weights):
+        m, w = _c(species_mode, np.int32), _c(species_weights)
+        self._chk(self.lib.qd_eco_daily_configure(self.h, ctypes.byref(params), ctypes.sizeof(params),
+                                                  m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                  w.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "qd_eco_daily_configure")
+
+    def eco_daily_set_layers(self, layers):
+        a = _c(layers)
+        self._chk(self.lib.qd_eco_daily_set_layers(self.h, a.ctypes.data, int(np.prod(a.shape[:-2]))), "qd_eco_daily_set_layers")
+
+    def eco_daily_get_layers(self, n_species, n_layers):
+        out = np.empty((n_species, n_layers) + self.shape, dtype=np.float64)
+        self._chk(self.lib.qd_eco_daily_get_layers(self.h, out.ctypes.data, n_species * n_layers), "qd_eco_daily_get_layers")
+        return out
+
+    def eco_daily_step(self, soil_index=None):
+        """One firing now; soil_index None = from the resident W_LAND and GLACIER, as inside a span."""
+        self.flush()
+        a = None if soil_index is None else _c(np.broadcast_to(np.asarray(soil_index, dtype=np.float64), self.shape))
+        self._chk(self.lib.qd_eco_daily_step(self.h, None if a is None else a.ctypes.data), "qd_eco_daily_step")
+        for k in ("ECO_LAI", "ECO_EDAY", "ECO_AGE", "ECO_SEEDBANK", "ECO_GATE"):
+            self._host.pop(k, None)
+
+    def eco_daily_schedule(self, fire):
+        f = _c(fire, np.int32)
+        self._chk(self.lib.qd_eco_daily_schedule(self.h, int(f.size), f.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "qd_eco_daily_schedule")
+
+    def eco_daily_log(self):
+        """Drain the daily vegetation records -> [n][4] (firings so far, LAI_min, LAI_mean, LAI_max over land)."""
+        return self._drain(self.lib.qd_eco_daily_log, _lib.ECO_DAILY_LOG_W, "qd_eco_daily_log")
+
+    def eco_daily_firings(self):
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.qd_eco_daily_state(self.h, ctypes.byref(n)), "qd_eco_daily_state")
         return int(n.value)
 
     # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident

@@ -28,6 +28,11 @@ resident loop on the steps its firing clock names (qd_step_n bit8, at the top of
 ocean-colour albedo overrides the ocean base albedo from the first daily step on (QD_PHYTO_ALBEDO_COUPLE, default 1), each chunk's
 [PhytoDiag] lines are printed after it from the device log, and data/plankton.nc is written and read with the reference's
 variable set.  The tracers exist then even without the ocean (the transport still needs it).
+Daily vegetation dynamics (QD_ECO_DAILY=1, default 0, with QD_ECO_ENABLE=1 and no daily_hook): PopulationManager.step_daily --
+growth, senescence, layered allocation, per-species spread, seed bank, age -- runs inside the resident loop on the steps the
+reference's day accumulator names (qd_step_n bit9, at the top of the step; qingdai_amd/ecology.py PopulationDaily), spans are no
+longer cut at day boundaries, and each chunk's `[Ecology] daily:` lines are printed after it from the device log (QD_ECO_DIAG=1).
+QD_ECO_MUT_RATE > 0 is refused with it; IndividualPool.step_daily, genes export and ecology.nc stay out.
 Not carried over (out of the hot path): genes / diversity, plankton.json, matplotlib panels (a note is
 printed instead of a plot).
 
@@ -195,6 +200,17 @@ class Simulation:
                 lai = f"LAI mean {self.eco.pop.summary()['LAI_mean']:.2f}" if self.eco.pop is not None else "no population (M1)"
                 print(f"[Ecology] device sub-step: NB={self.eco.bands.nbands}, alpha_leaf={self.eco.alpha_leaf_scalar:.3f}, "
                       f"{lai}, individuals {self.indiv.n_indiv if self.indiv else 0}")
+        # QD_ECO_DAILY=1: the daily population step as a span lane (no caller hook: a hook keeps precedence and today's behaviour)
+        self.eco_daily = None
+        if eco_on and self.eco.pop is not None and daily_hook is None and eco_daily_enabled(env):
+            from .ecology import PopulationDaily
+            self.eco_daily = PopulationDaily(self.eco.pop, day_seconds=self.day_seconds)
+            self.eco_diag = int(env.get("QD_ECO_DIAG", "1")) == 1
+            if not quiet:
+                print(f"[Ecology] daily step on the device: K={self.eco.pop.K}, Ns={self.eco.pop.Ns}, "
+                      f"spread {'on' if self.eco_daily.params.spread else 'off'}")
+                if self.indiv is not None:
+                    print("[Ecology] note: IndividualPool.step_daily is not run by the device daily step.")
         # phytoplankton tracers (run_simulation.py:1346-1364): their transport by the currents (needs the ocean), and under
         # QD_PHYTO_DAILY=1 the daily growth / optics step with its ocean-colour albedo, which the reference runs with or without the
         # ocean or the transport
@@ -341,15 +357,21 @@ class Simulation:
         stars = self.forcing.star_table(times)
         routing = getattr(self, "routing", None)
         daily = self.phyto_daily
+        eco_daily = self.eco_daily if self.daily_hook is None else None
         self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
                         with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto_transport,
-                        routing=routing, phyto_daily=daily, t0=self.t)
+                        routing=routing, phyto_daily=daily, t0=self.t, eco_daily=eco_daily)
         self.t = float(times[-1] + self.dt)
         self._step_index += n
         if daily is not None:
             daily.print_diag(self.dev.phyto_daily_log())      # the span's [PhytoDiag] lines, oldest first
         if routing is not None:
             routing.take_events(self.dev.route_events())      # the span's events, oldest first
+        if eco_daily is not None:
+            from .ecology import eco_daily_line
+            for rec in self.dev.eco_daily_log():               # the span's firings, oldest first (adapter.py:434-436)
+                if self.eco_diag:
+                    print(eco_daily_line(rec))
 
     def enable_routing(self, env=None):
         """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
@@ -413,6 +435,21 @@ def hydro_env(env):
     with the reference's defaults (run_simulation.py:1297-1314)."""
     return (int(env.get("QD_HYDRO_ENABLE", "1")) == 1, env.get("QD_HYDRO_NETCDF", "data/hydrology.nc"),
             float(env.get("QD_HYDRO_DT_HOURS", "6")), int(env.get("QD_HYDRO_DIAG", "1")) == 1)
+
+
+def eco_daily_enabled(env):
+    """QD_ECO_DAILY (default 0): 1 runs the daily population step on the device.  Refuses QD_ECO_MUT_RATE > 0: the reference's
+    speciation draws from the global NumPy generator after every daily step, which the device step does not restate."""
+    if int(env.get("QD_ECO_DAILY", "0")) != 1:
+        return False
+    try:
+        mut = float(env.get("QD_ECO_MUT_RATE", "0.0"))
+    except ValueError:
+        mut = 0.0
+    if mut > 0.0:
+        raise ValueError(f"QD_ECO_DAILY=1 does not support QD_ECO_MUT_RATE > 0 (got {mut:g}): stochastic speciation is host code "
+                         "outside the device daily step; unset one of the two")
+    return True
 
 
 def hydro_autogen(env):

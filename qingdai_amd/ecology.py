@@ -10,9 +10,12 @@ Mirrors, with the reference's names and call signatures, the part of pygcm/ecolo
   IndividualPool(grid, land_mask, eco).try_substep(isr_A, isr_B, eco, soil, dt, day)   individuals.py:37-191
 
 State lives in the grid's Device (qd_eco_* / qd_indiv_* of include/qingdai_hip.h); inside a fused loop
-(`Device.step_n(..., ecology=True)`) none of these methods is called at all.  The daily population dynamics
-(PopulationManager.step_daily, spread, genes, IndividualPool.step_daily) are host code that runs once per planet-day and is
-NOT part of this package: `Simulation` hands `E_day` to a caller-supplied daily hook and takes the new LAI layers back.
+(`Device.step_n(..., ecology=True)`) none of these methods is called at all.  The deterministic, grid-shaped part of the daily
+population dynamics (PopulationManager.step_daily with its spread, seed bank and age, population.py:389-828) runs on the device
+too: `PopulationDaily` configures it from the reference's environment variables, `PopulationCanopy.step_daily` is its class
+seam, and `Device.step_n(..., eco_daily=...)` fires it inside a span (QD_ECO_DAILY=1 in the driver).  Mutation, genes and
+IndividualPool.step_daily are host code outside this package: `Simulation` hands `E_day` to a caller-supplied daily hook and
+takes the new LAI layers back.
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import spectral as sp
-from ._lib import qd_eco_params
+from ._lib import qd_eco_params, qd_eco_daily_params
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -86,9 +89,24 @@ class PopulationCanopy:
             for k in range(self.K):
                 self.LAI_layers_SK[s, k] = float(self.species_weights[s]) * (lai0 / float(self.K))
         self._species_R_leaf = None
+        self.daily = None                  # a PopulationDaily once the daily step runs on the device
         self.push_layers(init=True)
 
     # -- LAI
+    @property
+    def LAI_layers_SK(self):
+        """[S, K, lat, lon]; with a device daily step the resident stack is the truth and is downloaded."""
+        if getattr(self, "daily", None) is not None:
+            fired = self._dev.eco_daily_firings()              # the device's own count: firings of a span or of a direct call alike
+            if fired != self._layers_at:
+                self._layers, self._layers_at = self._dev.eco_daily_get_layers(self.Ns, self.K), fired
+        return self._layers
+
+    @LAI_layers_SK.setter
+    def LAI_layers_SK(self, layers):
+        self._layers = layers
+        self._layers_at = self._dev.eco_daily_firings() if getattr(self, "daily", None) is not None else 0
+
     def push_layers(self, layers=None, init=False):
         """Hand the (changed) [S, K, lat, lon] stack to the device: what the daily step does once per planet-day."""
         if layers is not None:
@@ -98,6 +116,44 @@ class PopulationCanopy:
             raise ValueError(f"LAI layers: expected [..., {self.shape[0]}, {self.shape[1]}], got {a.shape}")
         n = int(np.prod(a.shape[:-2]))
         self._dev._chk(self._dev.lib.qd_eco_set_lai_layers(self._dev.h, a.ctypes.data, n, 1 if init else 0), "qd_eco_set_lai_layers")
+        if self.daily is not None:
+            self._dev.eco_daily_set_layers(a.reshape((-1,) + self.shape))
+
+    # -- daily step (population.py:389-596) on the device
+    def step_daily(self, soil_water_index):
+        """One firing of the device daily step with the reference's argument: None = dry (zeros), a scalar, or a [lat, lon] map
+        (any other shape falls back to its nanmean, population.py:408-416)."""
+        if self.daily is None:
+            PopulationDaily(self)
+        if soil_water_index is None:
+            soil = np.zeros(self.shape)
+        elif np.isscalar(soil_water_index):
+            soil = np.full(self.shape, float(soil_water_index))
+        else:
+            soil = np.asarray(soil_water_index, dtype=float)
+            if soil.shape != self.shape:
+                soil = np.full(self.shape, float(np.nanmean(soil)))
+        self._dev.eco_daily_step(soil)
+        self.daily._fired(1)
+
+    @property
+    def age_days(self):
+        self._dev._host.pop("ECO_AGE", None)
+        return self._dev.get("ECO_AGE").copy()
+
+    @property
+    def seed_bank(self):
+        self._dev._host.pop("ECO_SEEDBANK", None)
+        return self._dev.get("ECO_SEEDBANK").copy()
+
+    @seed_bank.setter
+    def seed_bank(self, arr):
+        self._dev.upload_now("ECO_SEEDBANK", np.broadcast_to(np.asarray(arr, dtype=np.float64), self.shape))
+
+    @property
+    def _spread_gate(self):
+        self._dev._host.pop("ECO_GATE", None)
+        return self._dev.get("ECO_GATE").copy()
 
     def total_LAI(self):
         self._dev._host.pop("ECO_LAI", None)
@@ -147,6 +203,155 @@ class PopulationCanopy:
         if L.size == 0:
             return {"LAI_min": 0.0, "LAI_mean": 0.0, "LAI_max": 0.0}
         return {"LAI_min": float(np.min(L)), "LAI_mean": float(np.mean(L)), "LAI_max": float(np.max(L))}
+
+
+def _envf_any(name, default):
+    """float(os.getenv(name, default)) with the reference's `except Exception` fallback to the default."""
+    try:
+        return float(os.getenv(name, str(default)))
+    except Exception:      # noqa: BLE001
+        return float(default)
+
+
+def species_modes_from_env(n_species, species_weights, weights_from_env):
+    """PopulationManager._init_species_modes (population.py:177-229): QD_ECO_SPECIES_{i}_MODE where it names 'seed' or 'diffusion';
+    the rest from np.random.default_rng(QD_ECO_RAND_SEED) -- with QD_ECO_SPECIES_WEIGHTS set ONE draw by weight picks the single
+    seed species, otherwise one uniform draw per unspecified species in index order (< 0.5 = seed).  Same generator calls in the
+    same order as the reference, so a given seed yields its modes."""
+    S = int(n_species)
+    modes = []
+    for i in range(S):
+        m = os.getenv(f"QD_ECO_SPECIES_{i}_MODE", "").strip().lower()
+        modes.append(m if m in ("seed", "diffusion") else "")
+    try:
+        seed_val = os.getenv("QD_ECO_RAND_SEED")
+        rng = np.random.default_rng(int(seed_val)) if seed_val not in (None, "") else np.random.default_rng()
+    except Exception:      # noqa: BLE001
+        rng = np.random.default_rng()
+    unspec = [i for i in range(S) if modes[i] == ""]
+    if not unspec:
+        return modes
+    if weights_from_env:
+        try:
+            w = np.clip(np.asarray(species_weights, dtype=float), 0.0, None)
+            w = w / (np.sum(w) + 1e-12)
+            chosen = int(rng.choice(np.arange(S), p=w))
+        except Exception:      # noqa: BLE001
+            chosen = 1 if S > 1 else 0
+        for i in unspec:
+            modes[i] = "seed" if i == chosen else "diffusion"
+    else:
+        for i in unspec:
+            modes[i] = "seed" if rng.random() < 0.5 else "diffusion"
+    return modes
+
+
+def daily_counts(accum, dt, n, day):
+    """The reference's day accumulator over n steps (run_simulation.py:1784-1789, float64): accum += dt; while accum >= day:
+    accum -= day, one firing -> (firings per step [n] int32, the accumulator afterwards)."""
+    fire = np.zeros(int(n), dtype=np.int32)
+    a, dt, day = np.float64(accum), np.float64(dt), np.float64(day)
+    for s in range(int(n)):
+        a = a + dt
+        while a >= day:
+            a = a - day
+            fire[s] += 1
+    return fire, float(a)
+
+
+def eco_daily_line(rec):
+    """The adapter's diagnostic line (adapter.py:434-436) from a record {firings, LAI_min, LAI_mean, LAI_max}."""
+    return f"[Ecology] daily: LAI(min/mean/max)={rec[1]:.2f}/{rec[2]:.2f}/{rec[3]:.2f}"
+
+
+class PopulationDaily:
+    """The device daily step of a PopulationCanopy: parameters from the reference's environment variables with its defaults and
+    parse fallbacks (LAIParams.from_env, QD_ECO_SPREAD_*, QD_ECO_REPRO_FRACTION, QD_ECO_SEED_*, QD_ECO_SEEDLING_LAI,
+    QD_ECO_LAYER_UPFRAC, QD_ECO_SOIL_WATER_CAP), the per-species spread modes, and the span participant of Device.step_n: a day
+    accumulator on the host names the firing steps, rolled back when the span does not run."""
+
+    def __init__(self, pop, day_seconds=None, species_modes=None):
+        self.pop, self.dev = pop, pop._dev
+        self.shape = pop.shape
+        from .forcing import PLANET_OMEGA
+        self.day_seconds = float(day_seconds) if day_seconds else 2 * np.pi / PLANET_OMEGA
+        self.accum_day = 0.0
+        self.n_firings = 0
+        try:
+            enable = int(os.getenv("QD_ECO_SPREAD_ENABLE", "0")) == 1
+        except Exception:      # noqa: BLE001
+            enable = False
+        self.spread_enable = enable
+        self.spread_rate = _envf_any("QD_ECO_SPREAD_RATE", 0.0)
+        self.spread_neighbors = os.getenv("QD_ECO_SPREAD_NEIGHBORS", "vonNeumann").strip().lower()
+        self.repro_fraction = _envf_any("QD_ECO_REPRO_FRACTION", 0.2)
+        gate_soil, soil_exp = 1, 1.0
+        try:                               # population.py:423-431: any parse failure here means the land-mask gate
+            gate_soil = 1 if int(os.getenv("QD_ECO_SPREAD_GATE_SOIL", "1")) == 1 else 0
+            if gate_soil:
+                soil_exp = float(os.getenv("QD_ECO_SPREAD_SOIL_EXP", "1.0"))
+        except Exception:      # noqa: BLE001
+            gate_soil = 0
+        cap_env = os.getenv("QD_ECO_SOIL_WATER_CAP")
+        try:
+            soil_cap = float(cap_env) if cap_env is not None else 50.0
+        except Exception:      # noqa: BLE001
+            soil_cap = 50.0
+        self.species_modes = list(species_modes) if species_modes is not None else species_modes_from_env(
+            pop.Ns, pop.species_weights, bool(os.getenv("QD_ECO_SPECIES_WEIGHTS", "").strip()))
+        rate = float(max(0.0, min(0.5, self.spread_rate)))
+        self.params = qd_eco_daily_params(
+            n_species=pop.Ns, n_layers=pop.K, spread=1 if (self.spread_enable and self.spread_rate > 0.0) else 0,
+            moore=1 if self.spread_neighbors in ("moore", "8", "8n") else 0, gate_soil=gate_soil, reserved=0,
+            lai_max=_envf_any("QD_ECO_LAI_MAX", 5.0), k_canopy=_envf_any("QD_ECO_LAI_K", 0.5),
+            growth_per_j=_envf_any("QD_ECO_LAI_GROWTH", 2.0e-5), senesce_per_day=_envf_any("QD_ECO_LAI_SENESCENCE", 0.01),
+            stress_thresh=_envf_any("QD_ECO_SOIL_STRESS_THRESH", 0.3), stress_strength=_envf_any("QD_ECO_SOIL_STRESS_GAIN", 1.0),
+            soil_cap=soil_cap, repro_frac=float(np.clip(self.repro_fraction, 0.0, 0.95)), spread_rate=rate, soil_exp=soil_exp,
+            upfrac=_envf_any("QD_ECO_LAYER_UPFRAC", 0.1), dlai_max=_envf_any("QD_ECO_SPREAD_DLAI_MAX", 0.02),
+            seed_energy=float(max(1e-12, _envf_any("QD_ECO_SEED_ENERGY", 1.0))),
+            seed_scale=float(max(1e-12, _envf_any("QD_ECO_SEED_SCALE", 1.0))),
+            seedling_lai=_envf_any("QD_ECO_SEEDLING_LAI", 0.02), retain=_envf_any("QD_ECO_SEED_BANK_RETAIN", 0.2),
+            bank_max=_envf_any("QD_ECO_SEED_BANK_MAX", 1000.0), seed_dlai_max=_envf_any("QD_ECO_SEED_DLAI_MAX", 0.01),
+            germ_frac=_envf_any("QD_ECO_SEED_GERMINATE_FRAC", 0.10), bank_decay=_envf_any("QD_ECO_SEED_BANK_DECAY", 0.02))
+        self.configure()
+
+    def configure(self):
+        """(Re)configure the device: parameters, modes, weights, the current layers; age, seed bank, log and firing count to zero."""
+        pop = self.pop
+        layers = np.ascontiguousarray(pop.LAI_layers_SK, dtype=np.float64)
+        w = np.asarray(pop.species_weights, dtype=float)
+        w = w / (np.sum(w) + 1e-12)                                                     # population.py:571-572
+        mode = [1 if str(m).lower() == "seed" else 0 for m in self.species_modes]
+        self.dev.eco_daily_configure(self.params, mode, w)
+        self.n_firings = 0
+        pop.daily = self
+        pop.LAI_layers_SK = layers
+        self.dev.eco_daily_set_layers(layers.reshape((-1,) + self.shape))
+        self.dev.upload_now("ECO_GATE", pop.land.astype(float))                         # population.py:171
+
+    def _fired(self, n):
+        self.n_firings += int(n)
+
+    def schedule(self, dt, n):
+        fire, self.accum_day = daily_counts(self.accum_day, dt, n, self.day_seconds)
+        return fire
+
+    # ---- span participant (Device.step_n)
+    def span_clock(self):
+        return self.accum_day
+
+    def span_schedule(self, t0, dt, n):
+        fire = self.schedule(dt, n)
+        self.dev.eco_daily_schedule(fire)
+        return int(fire.sum())
+
+    def span_restore(self, clock):
+        self.accum_day = clock
+
+    def log(self):
+        """Drain the device log -> list of summary() dicts, oldest first."""
+        return [{"step": int(r[0]), "LAI_min": float(r[1]), "LAI_mean": float(r[2]), "LAI_max": float(r[3])}
+                for r in self.dev.eco_daily_log()]
 
 
 @dataclass
