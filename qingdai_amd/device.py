@@ -135,7 +135,7 @@ class Device:
         scalars from ThermalForcing.star_table().  `routing`: a RiverRouting on this handle -- bit7, after the
         hydrology commit (which it needs); the host's t_accum schedule names the event steps, and the span's
         event records stay in the device log (route_events) until the caller drains them.  `phyto_daily`: a phyto.PhytoDaily on
-        this handle -- bit8; its firing clock turns the span's times t0 + dt * arange(n) into the schedule, and the span's
+        this handle -- bit8; its firing clock turns the span's times (t0 + dt * arange(n), or t0 itself when it is the n times) into the schedule, and the span's
         [PhytoDiag] records stay in the device log (phyto_daily_log) until the caller drains them.  `eco_daily`: an
         ecology.PopulationDaily on this handle -- bit9 (needs `ecology`); its day accumulator names the firing steps, and the span's
         LAI summaries stay in the device log (eco_daily_log) until the caller drains them."""

@@ -352,16 +352,42 @@ class Simulation:
             return
         self._run_chunk(n)
 
+    @property
+    def t(self):
+        """Model time in seconds.  Assigning it (a restart, an epoch) makes the value the origin the following steps count from."""
+        return self._t
+
+    @t.setter
+    def t(self, value):
+        self._t = float(value)
+        self._t_origin = (self._t, 0, None)                    # (t0, steps since, their dt)
+
+    def _span_times(self, n):
+        """The times of the next n steps as the reference's `np.arange(t0, t0 + duration, dt)` holds them (run_simulation.py:1639):
+        t0 + i * ((t0 + dt) - t0) with i counted from the origin, not from the span -- so that the insolation and the phytoplankton
+        firing test see the same float64 times however the run is cut into spans -> (times [n], the time after them)."""
+        t0, k, dt = self._t_origin
+        if dt is not None and dt != float(self.dt):            # the step changed: count afresh from where the clock stands
+            t0, k = self._t, 0
+        delta = (t0 + float(self.dt)) - t0
+        self._t_origin = (t0, k + n, float(self.dt))
+        return t0 + (k + np.arange(n)) * delta, float(t0 + (k + n) * delta)
+
     def _run_chunk(self, n, energy_diag=False):
-        times = self.t + self.dt * np.arange(n)
+        origin = self._t_origin
+        times, t_next = self._span_times(n)
         stars = self.forcing.star_table(times)
         routing = getattr(self, "routing", None)
         daily = self.phyto_daily
         eco_daily = self.eco_daily if self.daily_hook is None else None
-        self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
-                        with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto_transport,
-                        routing=routing, phyto_daily=daily, t0=self.t, eco_daily=eco_daily)
-        self.t = float(times[-1] + self.dt)
+        try:
+            self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
+                            with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto_transport,
+                            routing=routing, phyto_daily=daily, t0=times, eco_daily=eco_daily)
+        except Exception:
+            self._t_origin = origin                            # nothing ran: the clock stays where it was, like the lanes' clocks
+            raise
+        self._t = t_next
         self._step_index += n
         if daily is not None:
             daily.print_diag(self.dev.phyto_daily_log())      # the span's [PhytoDiag] lines, oldest first

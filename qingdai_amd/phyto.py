@@ -271,9 +271,15 @@ def daily_device_tables(t):
 
 
 def daily_schedule(next_time, t0, dt, n, day_seconds):
-    """The reference driver's firing clock (run_simulation.py:1738,2052-2061) over the span t = t0 + dt * arange(n):
+    """The reference driver's firing clock (run_simulation.py:1738,2052-2061) over the span t = t0 + dt * arange(n), or over the n
+    times themselves when t0 is an array (the driver's, which count from the run's origin):
     -> (int32 [n] 1 = the step fires, the clock after the span).  Same float64 comparisons as the reference."""
-    times = t0 + dt * np.arange(n)
+    if np.ndim(t0):
+        times = np.asarray(t0, dtype=np.float64)
+        if times.shape != (n,):
+            raise ValueError(f"daily_schedule: {n} steps but times of shape {times.shape}")
+    else:
+        times = t0 + dt * np.arange(n)
     fire = np.zeros(n, dtype=np.int32)
     nt = float(next_time)
     for k in range(n):
@@ -362,7 +368,7 @@ class PhytoDaily:
         return self.phyto_next_time
 
     def span_schedule(self, t0, dt, n):
-        fire = self.schedule(float(t0), dt, n)
+        fire = self.schedule(t0, dt, n)
         self.dev.phyto_daily_schedule(fire)
         return int(fire.sum())                 # -> the span's daily steps, for _fired once the span has run
 

@@ -33,8 +33,23 @@ def land_mask(rng, poles):
     return m
 
 
-def inputs(rng, S, K, land, e_scale):
-    L0 = rng.uniform(0.0, 0.6, (S, K, NLAT, NLON)) * (land == 1)
+def seam_mask(rng):
+    """Land on both sides of the east-west seam: columns 0 and NLON-1 on the same rows, among them both pole rows (so the four
+    corners are land and each corner's Moore neighbourhood wraps both axes at once), with ocean columns next to them on some rows."""
+    m = (rng.uniform(size=(NLAT, NLON)) < 0.45).astype(np.uint8)
+    m[:, 12:20] = 0                                 # the ocean basin sits mid-grid: the seam itself is a continent
+    rows = [0, 1, 4, 5, 9, 13, 14, NLAT - 2, NLAT - 1]
+    m[rows, 0] = 1
+    m[rows, -1] = 1
+    m[[4, 13], 1] = 0                               # land on the seam whose only east-west land neighbour is across it
+    m[[4, 13], -2] = 0
+    m[[0, NLAT - 1], 1:4] = 1                       # pole rows: land runs up to the corners from both sides
+    m[[0, NLAT - 1], -4:-1] = 1
+    return m
+
+
+def inputs(rng, S, K, land, e_scale, l_max=0.6):
+    L0 = rng.uniform(0.0, l_max, (S, K, NLAT, NLON)) * (land == 1)
     L0[:, :, 4:6, 10:14] = 0.0                      # bare land: LAI exactly 0 (the equal splits)
     E = rng.uniform(0.2, 1.0, (DAYS, NLAT, NLON)) * e_scale
     E[:, 10:12, 0:8] = 0.0                          # no light: cap_sum exactly 0
@@ -61,6 +76,11 @@ CASES = {
     "rate_clipped": dict(env={"QD_ECO_SPECIES_WEIGHTS": "0.1,0.6,0.3", "QD_ECO_COHORT_K": "1", "QD_ECO_SPREAD_ENABLE": "1",
                               "QD_ECO_SPREAD_RATE": "0.9", "QD_ECO_SEED_ENERGY": "1000", "QD_ECO_RAND_SEED": "4",
                               "QD_ECO_SPECIES_0_MODE": "diffusion"}, poles=True, e_scale=2.0e4),
+    # land on both sides of the longitude seam, at both pole rows and the four corners; Moore, the deepest stack (K = 8)
+    "seam": dict(env={"QD_ECO_NS": "2", "QD_ECO_COHORT_K": "8", "QD_ECO_SPREAD_ENABLE": "1", "QD_ECO_SPREAD_RATE": "0.15",
+                      "QD_ECO_SPREAD_NEIGHBORS": "moore", "QD_ECO_SPREAD_GATE_SOIL": "0", "QD_ECO_SEED_ENERGY": "400",
+                      "QD_ECO_SPECIES_0_MODE": "diffusion", "QD_ECO_SPECIES_1_MODE": "seed"}, mask="seam", e_scale=2.0e4, bank=1.0,
+                 l_max=0.15),
 }
 
 
@@ -76,10 +96,10 @@ def run_case(name, spec, PopulationManager, ref):
         del os.environ[k]
     os.environ.update(spec["env"])
     rng = np.random.default_rng(sum(map(ord, name)))
-    land = land_mask(rng, spec["poles"])
+    land = seam_mask(rng) if spec.get("mask") == "seam" else land_mask(rng, spec["poles"])
     pop = PopulationManager(land.astype(int), diag=False)
     S, K = pop.LAI_layers_SK.shape[:2]
-    L0, E, W, glacier = inputs(rng, S, K, land, spec["e_scale"])
+    L0, E, W, glacier = inputs(rng, S, K, land, spec["e_scale"], spec.get("l_max", 0.6))
     bank0 = rng.uniform(0.0, spec.get("bank", 0.0), (NLAT, NLON)) * (land == 1) if spec.get("bank") else np.zeros((NLAT, NLON))
     cap = float(os.environ.get("QD_ECO_SOIL_WATER_CAP", "50.0"))
     soil = np.stack([ref.soil_index(W[d], glacier, cap) for d in range(DAYS)])

@@ -17,7 +17,7 @@ from qingdai_amd.device import Device
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDENS = sorted(glob.glob(os.path.join(HERE, "golden", "eco_daily_*_19x36.npz")))
-CASES = ["defaults", "layers", "rate_clipped", "spread_moore", "spread_vn"]
+CASES = ["defaults", "layers", "rate_clipped", "seam", "spread_moore", "spread_vn"]
 OUT_KEYS = ("LAI_layers_SK", "total_LAI", "age_days", "seed_bank", "spread_gate", "E_day")
 
 
@@ -73,6 +73,67 @@ def test_goldens_cover_what_they_claim_cpu():
     m = z["spread_moore"]
     assert m["bank0"].max() > 0 and np.isclose(m["first_seed_bank"].max(), 2.0 * 0.75 * 0.9)      # QD_ECO_SEED_BANK_MAX reached
     assert float(_env_of(z["rate_clipped"])["QD_ECO_SPREAD_RATE"]) == 0.9
+
+
+def test_seam_golden_has_land_on_both_sides_of_the_longitude_seam_cpu(monkeypatch):
+    """The other five goldens hold no land in the last column.  This one has land in column 0 and in column nlon-1 on the same rows,
+    both pole rows and the four corners among them, the Moore neighbourhood, the deepest stack and both spread modes -- and its
+    expected values depend on the wrap: a restatement whose east-west shift does not wrap misses them in the seam columns."""
+    z = np.load(os.path.join(HERE, "golden", "eco_daily_seam_19x36.npz"))
+    land = z["land_mask"] == 1
+    both = land[:, 0] & land[:, -1]
+    assert both[0] and both[-1] and both.sum() >= 6 and land[0, 0] and land[0, -1] and land[-1, 0] and land[-1, -1]
+    assert (both & ~land[:, 1] & ~land[:, -2]).any()            # seam cells whose only east-west land neighbour is across the seam
+    env = _env_of(z)
+    assert z["L0"].shape[:2] == (2, 8) and env["QD_ECO_SPREAD_NEIGHBORS"] == "moore" and int(z["n_days"]) == 3
+    assert sorted(map(str, z["modes"])) == ["diffusion", "seed"] and z["bank0"].max() > 0
+    cfg = ref.Cfg.from_env(env, z["modes"], z["species_weights"])
+
+    def run():
+        st = ref.State(land, z["L0"].copy(), z["E_days"][0].copy(), np.zeros(land.shape), z["bank0"].copy(), land.astype(float))
+        return ref.step_daily(st, cfg, z["soil"][0]).layers
+
+    assert np.array_equal(run(), z["first_LAI_layers_SK"])
+    roll = np.roll
+
+    def no_wrap(x, shift, axis):                                # np.roll whose longitude shift brings zeros in, not the far column
+        out = roll(x, shift=shift, axis=axis)
+        dx = shift[1]
+        if dx > 0:
+            out[..., :dx] = 0
+        elif dx < 0:
+            out[..., dx:] = 0
+        return out
+
+    monkeypatch.setattr(np, "roll", no_wrap)
+    broken = run()
+    monkeypatch.undo()
+    diff = np.any(broken != z["first_LAI_layers_SK"], axis=(0, 1))
+    assert diff[:, 0].any() and diff[:, -1].any() and diff[0, 0] and diff[-1, -1] and not diff[:, 3:-3].any()
+
+
+def test_two_and_more_firings_in_one_step_cpu():
+    """dt = 2.5 days: the reference's literal `while accum >= day` loop (run_simulation.py:1785-1789) fires 2, 3, 2, 3 ... times per
+    step; daily_counts gives the same counts and the same accumulator for any cut of the steps."""
+    from qingdai_amd.ecology import daily_counts
+    day = 2 * np.pi / 8.726646259971648e-5
+    dt = 2.5 * day
+    accum, fired = 0.0, []
+    for _ in range(41):
+        accum += dt
+        k = 0
+        while accum >= day:
+            accum -= day
+            k += 1
+        fired.append(k)
+    assert set(fired) == {2, 3} and sum(fired) in (102, 103)
+    for cuts in ([41], [1] * 41, [2, 3, 36], [40, 1]):
+        a, got = 0.0, []
+        for n in cuts:
+            f, a = daily_counts(a, dt, n, day)
+            assert f.dtype == np.int32
+            got += [int(x) for x in f]
+        assert got == fired and a == accum, cuts
 
 
 @pytest.mark.parametrize("path", GOLDENS, ids=lambda p: os.path.basename(p)[10:-10])
