@@ -70,7 +70,10 @@ enum qd_field {
     QD_F_PHYTO_N, QD_F_KD490,
     QD_F_COUNT_F64,
     /* uint8 masks */
-    QD_F_LAND_MASK = 100, QD_F_ICE_MASK = 101
+    QD_F_LAND_MASK = 100, QD_F_ICE_MASK = 101,
+    /* results of the last qd_eco_diversity call, read with qd_eco_diversity_download (not slabs: no qd_upload / qd_download):
+     * L_s [n_species][n_lat][n_lon], alpha map, local Bray-Curtis map [n_lat][n_lon], {alpha_mean, gamma_eff, beta_whittaker} */
+    QD_F_ECO_DIV_LS = 110, QD_F_ECO_DIV_ALPHA = 111, QD_F_ECO_DIV_BC = 112, QD_F_ECO_DIV_SUMMARY = 113
 };
 
 /* Every env-derived scalar the reference reads inside the step,
@@ -321,6 +324,27 @@ int qd_eco_daily_step(qd_handle h, const double* soil_index);
 int qd_eco_daily_schedule(qd_handle h, int n, const int32_t* fire);   /* the next qd_step_n span: firings at the top of each step */
 int qd_eco_daily_log(qd_handle h, double* out, int max, int* n);      /* drains the log: *n records of 4 doubles */
 int qd_eco_daily_state(qd_handle h, int64_t* n_firings);              /* firings since the configure */
+
+/* ---- diversity diagnostics (pygcm/ecology/diversity.py:8-135; scripts/run_simulation.py:2406-2414), whole-globe handles ------
+ * From a [n_species][n_layers][n_lat][n_lon] LAI stack and the ecology's land mask (land == 1), f64 in the reference's operation
+ * order: L_s = sum_k max(stack, 0) (plane after plane), the alpha map exp(-sum_s p log(p + 1e-15)) with p = L_s / (L_tot + 1e-15)
+ * on land with L_tot > 0 (NaN elsewhere), the mean Bray-Curtis dissimilarity to the up / down / west / east neighbours that are land
+ * (rows clipped at the poles, columns periodic; NaN off land), and the Whittaker summary {alpha_mean, gamma_eff, beta_whittaker}
+ * from nansum(alpha w_norm) and nansum(L_s w_norm) over land.  w_norm_row [n_lat] is the reference's
+ * max(cos(deg2rad(lat)), 0) / (sum over land + 1e-15), computed by the caller.  layers NULL: the resident stack of
+ * qd_eco_daily_configure (n_species / n_layers must be its); else a host stack, uploaded to a scratch buffer allocated on first
+ * use.  L_s and the Bray-Curtis map equal NumPy's bit for bit; alpha and the summary differ by the device log / exp and by the
+ * blocked order of the two global sums (per-workgroup partials, one-workgroup finish, fixed order, no atomics).  The results stay
+ * resident until the next call (qd_eco_diversity_download); summary3 (may be NULL) also receives the three doubles.  The call
+ * changes nothing else: no field, no canopy version, no snapshot, no clock, no lane log.  Refused: latitude bands, n_species
+ * outside 1..64, n_layers outside 1..QD_ECO_DAILY_MAX_K, layers NULL without a configured stack of that shape. */
+int qd_eco_diversity(qd_handle h, const double* layers, int n_species, int n_layers, const double* w_norm_row, double* summary3);
+/* the same kernels on a grid and land mask of the caller's (host [n_lat][n_lon] uint8, land == 1; layers a host stack): a saved
+ * community at another resolution.  n_lat >= 2, n_lon >= 3.  The handle lends its device and stream. */
+int qd_eco_diversity_on(qd_handle h, int n_lat, int n_lon, const uint8_t* land_mask, const double* layers, int n_species,
+                        int n_layers, const double* w_norm_row, double* summary3);
+/* field: QD_F_ECO_DIV_LS (n = n_species * cells), _ALPHA, _BC (n = cells), _SUMMARY (n = 3) of the last call on this handle */
+int qd_eco_diversity_download(qd_handle h, int field, double* host, size_t n);
 
 /* ---- river routing (P014, pygcm/routing.py), whole-globe handles ----------------------------------
  * The host plans the network once (qingdai_amd/routing.py: build_plan): per cell a target code (>= 0 a live edge to that

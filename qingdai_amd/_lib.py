@@ -25,6 +25,8 @@ FIELDS = ["U", "V", "H", "TS", "Q", "CLOUD", "HICE", "ISR", "ISR_A", "ISR_B", "T
 F = {n: i for i, n in enumerate(FIELDS)}
 F["LAND_MASK"] = 100
 F["ICE_MASK"] = 101
+# results of the last qd_eco_diversity call (qd_eco_diversity_download; ids behind the masks, the f64 slab list above is unchanged)
+F.update({"ECO_DIV_LS": 110, "ECO_DIV_ALPHA": 111, "ECO_DIV_BC": 112, "ECO_DIV_SUMMARY": 113})
 R_SUM, R_COSMEAN, R_MAX, R_MIN, R_MAXABS = 0, 1, 2, 3, 4
 
 # every symbol include/qingdai_hip.h declares
@@ -45,6 +47,7 @@ SYMBOLS = [
     "qd_phyto_daily_state", "qd_phyto_daily_insolation",
     "qd_eco_daily_configure", "qd_eco_daily_set_layers", "qd_eco_daily_get_layers", "qd_eco_daily_step", "qd_eco_daily_schedule",
     "qd_eco_daily_log", "qd_eco_daily_state",
+    "qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
     "qd_hydronet_build", "qd_hydronet_sweeps",
@@ -180,6 +183,9 @@ def load():
     lib.qd_eco_daily_schedule.argtypes = [vp, i32, ip]
     lib.qd_eco_daily_log.argtypes = [vp, dp, i32, ip]
     lib.qd_eco_daily_state.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.qd_eco_diversity.argtypes = [vp, vp, i32, i32, dp, dp]
+    lib.qd_eco_diversity_on.argtypes = [vp, i32, i32, u8p, vp, i32, i32, dp, dp]
+    lib.qd_eco_diversity_download.argtypes = [vp, i32, dp, sz]
     lib.qd_comm_unique_id.argtypes = [vp, sz]
     lib.qd_comm_init.argtypes = [vp, vp, sz]
     lib.qd_comm_barrier.argtypes = [vp]

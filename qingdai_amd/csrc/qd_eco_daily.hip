@@ -303,6 +303,13 @@ void qd_eco_daily_release(qd_ctx* c) {
     c->edaily = nullptr;
 }
 
+bool qd_eco_daily_stack(const qd_ctx* c, const double** L, int* n_species, int* n_layers) {
+    const QdEcoDaily* d = c->edaily;
+    if (!d || !d->L) return false;
+    *L = d->L; *n_species = d->p.n_species; *n_layers = d->p.n_layers;
+    return true;
+}
+
 static bool ed_whole_globe(const qd_ctx* c) { return c->geo.full && c->desc.world <= 1; }
 
 extern "C" int qd_eco_daily_configure(qd_handle c, const qd_eco_daily_params* p, size_t sz, const int32_t* mode, const double* w) {

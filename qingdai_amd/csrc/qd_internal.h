@@ -206,6 +206,7 @@ struct qd_ctx {
     struct QdRoute* route = nullptr; // river routing network, buffer and event log (qd_route.hip), whole-globe handles
     struct QdPhytoDaily* pdaily = nullptr;   // daily phytoplankton step: tables, band stack, schedule, diagnostic log (qd_phyto_daily.hip)
     struct QdEcoDaily* edaily = nullptr;     // daily vegetation step: LAI stack, share plane, schedule, log (qd_eco_daily.hip)
+    struct QdEcoDiv* ediv = nullptr;         // diversity diagnostics: L_s, the two maps, partials, summary (qd_eco_div.hip)
     int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
     double* zonal_tw = nullptr;      // [2][nlon] cos / sin(2 pi m / nlon) of the zonal spectral filter
     double* sel_cand = nullptr;      // [2][cells] candidates of the two middle ranks after two radix passes (whole-globe handles)
@@ -453,6 +454,8 @@ void qd_phyto_daily_release(qd_ctx* c);
 struct QdSpanLane* qd_eco_daily_span_begin(qd_ctx* c, int n, int with_eco);      // qd_eco_daily.hip
 int  qd_eco_daily_step_impl(qd_ctx* c, const double* soil_dev);
 void qd_eco_daily_release(qd_ctx* c);
+bool qd_eco_daily_stack(const qd_ctx* c, const double** L, int* n_species, int* n_layers);   // the resident LAI stack, when configured
+void qd_eco_div_release(qd_ctx* c);                                              // qd_eco_div.hip
 bool qd_phyto_daily_couples(const qd_ctx* c);                               // the albedo launches blend WATER_ALPHA into the ocean
 bool qd_eco_is_f32(const qd_ctx* c, int field);                             // qd_eco.hip: slab stored as f32 (qd_eco_params.map_f32)
 void qd_eco_convert_slab(qd_ctx* c, const double* src, int src_f32, double* dst, int dst_f32);

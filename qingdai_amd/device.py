@@ -295,6 +295,47 @@ class Device:
         self._chk(self.lib.qd_eco_daily_state(self.h, ctypes.byref(n)), "qd_eco_daily_state")
         return int(n.value)
 
+    # ---- diversity diagnostics (qd_eco_div.hip)
+    def eco_diversity(self, w_norm_row, layers=None, n_species=None, n_layers=None, land_mask=None):
+        """pygcm/ecology/diversity.py on the device -> {alpha_mean, gamma_eff, beta_whittaker}; the maps stay resident
+        (eco_diversity_get).  layers None: the resident stack of eco_daily_configure (n_species, n_layers name its shape); else a host
+        [S, K, lat, lon] stack.  land_mask None: the ecology's land mask on the handle's grid; else the caller's mask, whose shape
+        is the grid of the call (layers is then required)."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        w = _c(w_norm_row)
+        out = (ctypes.c_double * 3)()
+        a = None
+        if layers is not None:
+            a = _c(layers)
+            if a.ndim != 4:
+                raise ValueError(f"eco_diversity: layers must be [S, K, lat, lon], got {a.shape}")
+            n_species, n_layers = a.shape[:2]
+        if land_mask is not None:
+            m = _c(land_mask, np.uint8)
+            if a is None or a.shape[2:] != m.shape or w.shape != (m.shape[0],):
+                raise ValueError("eco_diversity: a land mask of the caller's needs a host stack and a weight row of its shape")
+            self._chk(self.lib.qd_eco_diversity_on(self.h, m.shape[0], m.shape[1], m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                   a.ctypes.data, int(n_species), int(n_layers), w.ctypes.data_as(dp), out),
+                      "qd_eco_diversity_on")
+            self._div_shape = (int(n_species),) + m.shape
+        else:
+            if w.shape != (self.shape[0],) or (a is not None and a.shape[2:] != self.shape):
+                raise ValueError(f"eco_diversity: expected [S, K, {self.shape[0]}, {self.shape[1]}] layers and {self.shape[0]} row weights")
+            self._chk(self.lib.qd_eco_diversity(self.h, None if a is None else a.ctypes.data, int(n_species), int(n_layers),
+                                                w.ctypes.data_as(dp), out), "qd_eco_diversity")
+            self._div_shape = (int(n_species),) + self.shape
+        return {"alpha_mean": float(out[0]), "gamma_eff": float(out[1]), "beta_whittaker": float(out[2])}
+
+    def eco_diversity_get(self, name):
+        """A result of the last eco_diversity call: "ECO_DIV_LS" [S, lat, lon], "ECO_DIV_ALPHA", "ECO_DIV_BC" [lat, lon],
+        "ECO_DIV_SUMMARY" [3]."""
+        shp = getattr(self, "_div_shape", None)
+        shape = (3,) if name == "ECO_DIV_SUMMARY" else (None if shp is None else (shp if name == "ECO_DIV_LS" else shp[1:]))
+        out = np.empty(shape if shape is not None else (1,), dtype=np.float64)
+        self._chk(self.lib.qd_eco_diversity_download(self.h, F[name], out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.size),
+                  "qd_eco_diversity_download")
+        return out
+
     # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident
     def phyto_configure(self, n_species, K_h, adv_alpha):
         self._chk(self.lib.qd_phyto_configure(self.h, int(n_species), float(K_h), float(adv_alpha)), "qd_phyto_configure")

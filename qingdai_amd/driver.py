@@ -33,8 +33,15 @@ growth, senescence, layered allocation, per-species spread, seed bank, age -- ru
 reference's day accumulator names (qd_step_n bit9, at the top of the step; qingdai_amd/ecology.py PopulationDaily), spans are no
 longer cut at day boundaries, and each chunk's `[Ecology] daily:` lines are printed after it from the device log (QD_ECO_DIAG=1).
 QD_ECO_MUT_RATE > 0 is refused with it; IndividualPool.step_daily, genes export and ecology.nc stay out.
-Not carried over (out of the hot path): genes / diversity, plankton.json, matplotlib panels (a note is
-printed instead of a plot).
+Diversity diagnostics (QD_ECO_DIVERSITY_ENABLE=1, default 0; QD_ECO_DIVERSITY_EVERY_DAYS, default 10; run_simulation.py:2406-2414,
+pygcm/ecology/diversity.py): on the reference's clock -- the step whose start time t_i satisfies t_i / day >= next fires at its end
+and sets next = t_i / day + every, so the first step always fires -- the alpha map, the local Bray-Curtis map and the Whittaker
+summary are computed on the device from the LAI stack (the resident one under QD_ECO_DAILY=1; PopulationCanopy.diversity), a chunk
+ends with the firing step, and the reference's files go to <QD_OUTPUT_DIR, default output>/ecology/ named by t_i / day:
+diversity_summary_day_*.txt and community_day_*.npz as the reference writes them, diversity_maps_day_*.npz (alpha_map, bc_local)
+in place of its two PNG maps.  QD_ECO_DIAG=1 prints one [Diversity] line per firing.
+Not carried over (out of the hot path): genes, plankton.json, matplotlib panels (a note is printed instead of
+a plot; the diversity annotation of the plot panel, run_simulation.py:1025-1052, goes with them).
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -211,6 +218,13 @@ class Simulation:
                       f"spread {'on' if self.eco_daily.params.spread else 'off'}")
                 if self.indiv is not None:
                     print("[Ecology] note: IndividualPool.step_daily is not run by the device daily step.")
+        # diversity diagnostics (run_simulation.py:1425-1429, 1741): the switch, the cadence, the clock's threshold in days
+        self.diversity_on, self.diversity_every = False, 10.0
+        self.diversity_next_day = 0.0
+        self._diversity_failed = False
+        if self.eco is not None and self.eco.pop is not None:
+            from .ecology import diversity_env
+            self.diversity_on, self.diversity_every = diversity_env(env)
         # phytoplankton tracers (run_simulation.py:1346-1364): their transport by the currents (needs the ocean), and under
         # QD_PHYTO_DAILY=1 the daily growth / optics step with its ocean-colour albedo, which the reference runs with or without the
         # ocean or the transport
@@ -362,16 +376,49 @@ class Simulation:
         self._t = float(value)
         self._t_origin = (self._t, 0, None)                    # (t0, steps since, their dt)
 
-    def _span_times(self, n):
+    def _span_times(self, n, advance=True):
         """The times of the next n steps as the reference's `np.arange(t0, t0 + duration, dt)` holds them (run_simulation.py:1639):
         t0 + i * ((t0 + dt) - t0) with i counted from the origin, not from the span -- so that the insolation and the phytoplankton
-        firing test see the same float64 times however the run is cut into spans -> (times [n], the time after them)."""
+        firing test see the same float64 times however the run is cut into spans -> (times [n], the time after them).
+        advance=False only looks ahead: the origin stays where it is."""
         t0, k, dt = self._t_origin
         if dt is not None and dt != float(self.dt):            # the step changed: count afresh from where the clock stands
             t0, k = self._t, 0
         delta = (t0 + float(self.dt)) - t0
-        self._t_origin = (t0, k + n, float(self.dt))
+        if advance:
+            self._t_origin = (t0, k + n, float(self.dt))
         return t0 + (k + np.arange(n)) * delta, float(t0 + (k + n) * delta)
+
+    # -- diversity diagnostics (run_simulation.py:2404-2414)
+    def diversity_due(self, n_max):
+        """Looks at the next n_max steps with the reference's clock -> (steps up to and including the first firing step, that
+        step's start time in days), or (None, None) when none of them fires or the diagnostics are off."""
+        if not self.diversity_on or n_max <= 0:
+            return None, None
+        from .ecology import diversity_firings
+        times, _ = self._span_times(int(n_max), advance=False)
+        fired, _ = diversity_firings(times, self.day_seconds, self.diversity_next_day, self.diversity_every)
+        if not fired:
+            return None, None
+        return fired[0] + 1, float(times[fired[0]]) / self.day_seconds
+
+    def run_diversity(self, t_days, output_dir=None):
+        """One firing on the state as it stands (the end of the firing step): the device diagnostics, the reference's files under
+        <output_dir>/ecology/ named by t_days, the clock's next threshold.  A failure is reported once and never stops the run."""
+        from .ecology import write_diversity_files, diversity_line
+        self.diversity_next_day = t_days + self.diversity_every
+        try:
+            alpha_map, bc_local, L_s, summary = self.eco.pop.diversity()
+            out = output_dir if output_dir is not None else os.environ.get("QD_OUTPUT_DIR", "output")
+            write_diversity_files(out, t_days, alpha_map, bc_local, L_s, summary, self.land_mask)
+            if int(os.environ.get("QD_ECO_DIAG", "1")) == 1:
+                print(diversity_line(t_days, summary))
+            return summary
+        except Exception as e:      # noqa: BLE001  (non-fatal, like the reference)
+            if not self._diversity_failed and int(os.environ.get("QD_ECO_DIAG", "1")) == 1:
+                print(f"[Diversity] diagnostics skipped: {e}")
+            self._diversity_failed = True
+            return None
 
     def _run_chunk(self, n, energy_diag=False):
         origin = self._t_origin
@@ -483,15 +530,18 @@ def hydro_autogen(env):
     return int(env.get("QD_HYDRO_AUTOGEN", "0")) == 1
 
 
-def chunk_until(t, dt, next_autosave_t, remaining, max_chunk=200):
+def chunk_until(t, dt, next_autosave_t, remaining, max_chunk=200, fire_in=None):
     """Steps to hand to the device loop in one go: at most `max_chunk`, at most `remaining`, and -- when a periodic autosave is
     pending -- exactly up to the step whose END reaches the threshold (the reference tests `t >= next_autosave_t` at the top of the
-    following step, run_simulation.py:1762), at least one."""
+    following step, run_simulation.py:1762), at least one.  fire_in (Simulation.diversity_due): the chunk ends no later than the
+    step that fires the diversity diagnostics, which run on the state after that step."""
     n = min(max_chunk, remaining)
     if next_autosave_t is not None:
         to_thr = int(np.ceil((next_autosave_t - t) / dt - 1e-9))
         if to_thr > 0:
             n = max(1, min(n, to_thr))
+    if fire_in is not None and fire_in >= 1:
+        n = min(n, int(fire_in))
     return n
 
 
@@ -588,9 +638,12 @@ def main(argv=None):
     done = 0
     wall0 = time.perf_counter()
     while done < n_total:
-        n = chunk_until(sim.t, sim.dt, next_autosave_t if autosave_on else None, n_total - done)
+        fire_in, fire_day = sim.diversity_due(min(200, n_total - done))
+        n = chunk_until(sim.t, sim.dt, next_autosave_t if autosave_on else None, n_total - done, fire_in=fire_in)
         sim.run_steps(n)
         done += n
+        if fire_in is not None and n == fire_in:               # the chunk ended with the firing step
+            sim.run_diversity(fire_day)
         if int(env.get("QD_DYN_DIAG_PRINT", "1")) == 1:
             dg = sim.diagnostics()
             el = time.perf_counter() - wall0

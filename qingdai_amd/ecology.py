@@ -13,7 +13,9 @@ State lives in the grid's Device (qd_eco_* / qd_indiv_* of include/qingdai_hip.h
 (`Device.step_n(..., ecology=True)`) none of these methods is called at all.  The deterministic, grid-shaped part of the daily
 population dynamics (PopulationManager.step_daily with its spread, seed bank and age, population.py:389-828) runs on the device
 too: `PopulationDaily` configures it from the reference's environment variables, `PopulationCanopy.step_daily` is its class
-seam, and `Device.step_n(..., eco_daily=...)` fires it inside a span (QD_ECO_DAILY=1 in the driver).  Mutation, genes and
+seam, and `Device.step_n(..., eco_daily=...)` fires it inside a span (QD_ECO_DAILY=1 in the driver).  The diversity diagnostics
+(pygcm/ecology/diversity.py) run on the device as well: `PopulationCanopy.diversity()` (qd_eco_diversity) with the clock, the line
+and the file writer the driver uses under QD_ECO_DIVERSITY_ENABLE=1.  Mutation, genes and
 IndividualPool.step_daily are host code outside this package: `Simulation` hands `E_day` to a caller-supplied daily hook and
 takes the new LAI layers back.
 """
@@ -192,6 +194,19 @@ class PopulationCanopy:
         w = self.species_weights if self.species_weights.size == R.shape[0] else np.full((R.shape[0],), 1.0 / max(1, R.shape[0]))
         return np.clip(np.tensordot(w, R, axes=(0, 0)), 0.0, 1.0)
 
+    # -- diversity diagnostics (pygcm/ecology/diversity.py) on the device
+    def diversity(self):
+        """compute_alpha_eff_map, compute_local_bray_curtis and compute_whittaker_beta of the current community ->
+        (alpha_map, bc_local, L_s [S, lat, lon], {alpha_mean, gamma_eff, beta_whittaker}).  With a device daily step the
+        resident stack is used where it lies; otherwise the host LAI_layers_SK is handed over.  Changes no state."""
+        d = self._dev
+        w_row = diversity_weights(d.grid.lat_mesh, self.land)
+        if self.daily is not None:
+            summary = d.eco_diversity(w_row, n_species=self.Ns, n_layers=self.K)
+        else:
+            summary = d.eco_diversity(w_row, layers=np.asarray(self.LAI_layers_SK, dtype=np.float64))
+        return d.eco_diversity_get("ECO_DIV_ALPHA"), d.eco_diversity_get("ECO_DIV_BC"), d.eco_diversity_get("ECO_DIV_LS"), summary
+
     def state(self):
         out = (ctypes.c_double * 5)()
         self._dev._chk(self._dev.lib.qd_eco_get_state(self._dev.h, out), "qd_eco_get_state")
@@ -203,6 +218,70 @@ class PopulationCanopy:
         if L.size == 0:
             return {"LAI_min": 0.0, "LAI_mean": 0.0, "LAI_max": 0.0}
         return {"LAI_min": float(np.min(L)), "LAI_mean": float(np.mean(L)), "LAI_max": float(np.max(L))}
+
+
+def diversity_weights(lat_mesh, land):
+    """The static factor of compute_whittaker_beta (diversity.py:28-31,69-72): w_norm = max(cos(deg2rad(lat)), 0) / (its sum over
+    land + 1e-15), evaluated on the mesh as the reference does -> the per-row table [n_lat] the device takes."""
+    w = np.maximum(np.cos(np.deg2rad(np.asarray(lat_mesh, dtype=float))), 0.0)
+    w_sum_land = float(np.sum(w[np.asarray(land, dtype=bool)])) + 1e-15
+    return np.ascontiguousarray((w / w_sum_land)[:, 0])
+
+
+def diversity_env(env):
+    """-> (enabled, every_days) from QD_ECO_DIVERSITY_ENABLE (default 0) and QD_ECO_DIVERSITY_EVERY_DAYS (default 10, and 10 on a
+    parse error; run_simulation.py reads them the same way)."""
+    try:
+        enabled = int(env.get("QD_ECO_DIVERSITY_ENABLE", "0")) == 1
+    except ValueError:
+        enabled = False
+    try:
+        every = float(env.get("QD_ECO_DIVERSITY_EVERY_DAYS", "10"))
+    except ValueError:
+        every = 10.0
+    return enabled, every
+
+
+def diversity_firings(times, day_seconds, next_day, every_days):
+    """The reference's clock (run_simulation.py:2404-2411) over the step START times `times` (float64, as Simulation._span_times
+    holds them): the step whose t / day >= next fires and sets next = t / day + every -> (indices of the firing steps, next)."""
+    fired = []
+    for i, t in enumerate(np.asarray(times, dtype=np.float64)):
+        t_days = float(t) / day_seconds
+        if t_days >= next_day:
+            fired.append(i)
+            next_day = t_days + every_days
+    return fired, next_day
+
+
+def diversity_summary_text(t_days, summary):
+    """The four lines of diversity_summary_day_*.txt (diversity.py:168-172), character for character."""
+    return (f"Day: {t_days:.2f}\n"
+            f"Whittaker beta (\u03b2 = \u03b3/\u03b1\u0304): {summary['beta_whittaker']:.4f}\n"
+            f"  alpha_mean (\u03b1\u0304): {summary['alpha_mean']:.4f}\n"
+            f"  gamma_eff  (\u03b3 ): {summary['gamma_eff']:.4f}\n")
+
+
+def diversity_line(t_days, summary):
+    """The driver's line per firing under QD_ECO_DIAG=1."""
+    return (f"[Diversity] day {t_days:.2f}: alpha_mean={summary['alpha_mean']:.4f} gamma_eff={summary['gamma_eff']:.4f} "
+            f"beta_whittaker={summary['beta_whittaker']:.4f}")
+
+
+def write_diversity_files(base_output_dir, t_days, alpha_map, bc_local, L_s, summary, land_mask):
+    """The reference's files under <base_output_dir>/ecology/ (diversity.py:138-186, 197): the text summary and
+    community_day_*.npz (L_s as float32, land_mask as int8) as they are; the two PNG maps become diversity_maps_day_*.npz with
+    alpha_map and bc_local (no matplotlib here) -> the three paths."""
+    outdir = os.path.join(base_output_dir, "ecology")
+    os.makedirs(outdir, exist_ok=True)
+    tag = f"{t_days:05.1f}"
+    paths = (os.path.join(outdir, f"diversity_summary_day_{tag}.txt"), os.path.join(outdir, f"community_day_{tag}.npz"),
+             os.path.join(outdir, f"diversity_maps_day_{tag}.npz"))
+    with open(paths[0], "w", encoding="utf-8") as f:
+        f.write(diversity_summary_text(t_days, summary))
+    np.savez(paths[1], L_s=np.asarray(L_s).astype(np.float32), land_mask=np.asarray(land_mask).astype(np.int8))
+    np.savez(paths[2], alpha_map=np.asarray(alpha_map), bc_local=np.asarray(bc_local))
+    return paths
 
 
 def _envf_any(name, default):
