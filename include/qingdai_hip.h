@@ -346,6 +346,48 @@ int qd_eco_diversity_on(qd_handle h, int n_lat, int n_lon, const uint8_t* land_m
 /* field: QD_F_ECO_DIV_LS (n = n_species * cells), _ALPHA, _BC (n = cells), _SUMMARY (n = 3) of the last call on this handle */
 int qd_eco_diversity_download(qd_handle h, int field, double* host, size_t n);
 
+/* ---- true-colour frame (scripts/run_simulation.py:539-778, plot_true_color), whole-globe handles ----------------------------
+ * The reference's rgb_map[n_lat][n_lon][3] and the two numbers of its [TrueColor] line, composed in one launch from the resident
+ * HICE, C_SNOW, CLOUD, TS, ISR, ISR_A, ISR_B, ECO_F, the land mask, the phytoplankton band stack and the routing flow map, f64 in
+ * the reference's operation order: base colours -> sea ice (1 - exp(-max(h_ice, 0) / max(1e-6, h_ice_ref)) >= ice_frac_thr on the
+ * ocean) -> land snow blend -> vegetation overlay -> ocean-colour overlay (open ocean only) -> snow by T_s -> clouds -> rivers ->
+ * lakes -> clip.  The per-band irradiance of the two overlays is recomputed per cell from ISR_A / ISR_B with the rule of
+ * qd_band_insolation; no [NB]-plane stack of it is read.  The only operations that are not exactly NumPy's are exp and pow. */
+#define QD_TRUECOLOR_MAX_BANDS 16
+typedef struct qd_truecolor_params {
+    int32_t snow_by_swe;              /* QD_TRUECOLOR_SNOW_BY_SWE == 1 */
+    int32_t veg;                      /* QD_ECO_TRUECOLOR_VEG == 1 and an ecology adapter exists */
+    int32_t veg_f_one;                /* no population (QD_ECO_USE_LAI=0): f = 1 on land, R_eff = R_leaf */
+    int32_t oceancolor;               /* QD_PLOT_OCEANCOLOR == 1 and a daily phytoplankton manager exists */
+    int32_t snow_by_ts;               /* QD_TRUECOLOR_SNOW_BY_TS == 1 */
+    int32_t rivers;                   /* routing exists and QD_PLOT_RIVERS == 1 */
+    int32_t lakes;                    /* routing exists and its lake mask has a set cell */
+    int32_t nb_eco, nb_phyto;         /* bands of the two overlays, 0..QD_TRUECOLOR_MAX_BANDS */
+    int32_t reserved;
+    double h_ice_ref, ice_frac_thr;   /* QD_HICE_REF, QD_TRUECOLOR_ICE_FRAC */
+    double snow_cover_frac, snow_vis_alpha;   /* QD_SNOW_COVER_FRAC, QD_SNOW_VIS_ALPHA */
+    double veg_gamma, veg_sat, soil_ref;      /* QD_ECO_TRUECOLOR_GAMMA, QD_ECO_TRUECOLOR_SAT, QD_ECO_SOIL_REFLECT */
+    double oc_gamma, oc_blend;        /* QD_OC_GAMMA, QD_OC_BLEND */
+    double snow_thresh;               /* QD_SNOW_THRESH */
+    double cloud_alpha, cloud_white;  /* QD_TRUECOLOR_CLOUD_ALPHA, QD_TRUECOLOR_CLOUD_WHITE */
+    double river_min, river_alpha, lake_alpha;   /* QD_RIVER_MIN_KGPS, QD_RIVER_ALPHA, QD_LAKE_ALPHA */
+} qd_truecolor_params;
+/* eco_tab [7][nb_eco]: R_eff, the channel weights wr, wg, wb, the star spectra specA, specB and the Rayleigh factor T_ray of the
+ * ecology's bands (NULL when nb_eco == 0); phyto_tab [6][nb_phyto]: wr, wg, wb, specA, specB, T_ray of the phytoplankton's bands.
+ * phyto_bands: NULL = the resident band stack of the daily phytoplankton step (the overlay is skipped until its first step has
+ * run, as the reference skips it while alpha_water_bands is None); else a host [nb_phyto][n_lat][n_lon] stack, kept in a buffer of
+ * the renderer's.  lake_mask: host [n_lat][n_lon] uint8 or NULL.  Refused on latitude bands. */
+int qd_truecolor_configure(qd_handle h, const qd_truecolor_params* p, size_t sizeof_params, const double* eco_tab,
+                           const double* phyto_tab, const double* phyto_bands, const uint8_t* lake_mask);
+/* One frame from the state as it stands.  flow: NULL = the routing state's flow map; else a host [n_lat][n_lon] map (kg/s).
+ * want_f64 != 0 also keeps the unquantised rgb.  out2 (may be NULL) = {sea_ice_area, mean_h_ice}: sum(w mask) / (sum(w) + 1e-15)
+ * with w = max(cos lat, 0), and the mean of h_ice over the sea-ice mask (0 for an empty mask), from per-workgroup partials combined
+ * in a fixed order.  Reads the state and changes none of it. */
+int qd_truecolor_render(qd_handle h, int want_f64, const double* flow, double* out2);
+/* which 0: the u8 image [n_lat][n_lon][3], northernmost row first, min(255, floor(x * 255 + 0.5)), NaN -> 0 (n = bytes);
+ * which 1: the f64 rgb [n_lat][n_lon][3] in grid order of a render with want_f64 (n = doubles) */
+int qd_truecolor_download(qd_handle h, int which, void* host, size_t n);
+
 /* ---- river routing (P014, pygcm/routing.py), whole-globe handles ----------------------------------
  * The host plans the network once (qingdai_amd/routing.py: build_plan): per cell a target code (>= 0 a live edge to that
  * cell; -1 ocean, -2 void, -3 residual, -4 never processed, -5 - k lake storage k) and the reference's sequential loop cut into

@@ -48,6 +48,7 @@ SYMBOLS = [
     "qd_eco_daily_configure", "qd_eco_daily_set_layers", "qd_eco_daily_get_layers", "qd_eco_daily_step", "qd_eco_daily_schedule",
     "qd_eco_daily_log", "qd_eco_daily_state",
     "qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download",
+    "qd_truecolor_configure", "qd_truecolor_render", "qd_truecolor_download",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
     "qd_hydronet_build", "qd_hydronet_sweeps",
@@ -77,6 +78,17 @@ class qd_eco_daily_params(ctypes.Structure):
                                                  "seed_scale", "seedling_lai", "retain", "bank_max", "seed_dlai_max", "germ_frac",
                                                  "bank_decay")])
 
+
+class qd_truecolor_params(ctypes.Structure):
+    """include/qingdai_hip.h: qd_truecolor_params"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("snow_by_swe", "veg", "veg_f_one", "oceancolor", "snow_by_ts", "rivers", "lakes", "nb_eco",
+                                                "nb_phyto", "reserved")] +
+                [(n, ctypes.c_double) for n in ("h_ice_ref", "ice_frac_thr", "snow_cover_frac", "snow_vis_alpha", "veg_gamma", "veg_sat",
+                                                 "soil_ref", "oc_gamma", "oc_blend", "snow_thresh", "cloud_alpha", "cloud_white",
+                                                 "river_min", "river_alpha", "lake_alpha")])
+
+
+TRUECOLOR_MAX_BANDS = 16     # QD_TRUECOLOR_MAX_BANDS
 
 SPAN_LOG_CAP = 4096          # records a span lane's device log holds between two drains (csrc/qd_span.h: QD_SPAN_LOG_CAP is the same number)
 PHYTO_DAILY_LOG_W = 4        # doubles per [PhytoDiag] record
@@ -186,6 +198,9 @@ def load():
     lib.qd_eco_diversity.argtypes = [vp, vp, i32, i32, dp, dp]
     lib.qd_eco_diversity_on.argtypes = [vp, i32, i32, u8p, vp, i32, i32, dp, dp]
     lib.qd_eco_diversity_download.argtypes = [vp, i32, dp, sz]
+    lib.qd_truecolor_configure.argtypes = [vp, ctypes.POINTER(qd_truecolor_params), sz, dp, dp, dp, u8p]
+    lib.qd_truecolor_render.argtypes = [vp, i32, dp, dp]
+    lib.qd_truecolor_download.argtypes = [vp, i32, vp, sz]
     lib.qd_comm_unique_id.argtypes = [vp, sz]
     lib.qd_comm_init.argtypes = [vp, vp, sz]
     lib.qd_comm_barrier.argtypes = [vp]

@@ -207,6 +207,7 @@ struct qd_ctx {
     struct QdPhytoDaily* pdaily = nullptr;   // daily phytoplankton step: tables, band stack, schedule, diagnostic log (qd_phyto_daily.hip)
     struct QdEcoDaily* edaily = nullptr;     // daily vegetation step: LAI stack, share plane, schedule, log (qd_eco_daily.hip)
     struct QdEcoDiv* ediv = nullptr;         // diversity diagnostics: L_s, the two maps, partials, summary (qd_eco_div.hip)
+    struct QdTrueColor* tcol = nullptr;      // true-colour frame: parameters, band tables, image, partials (qd_truecolor.hip)
     int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
     double* zonal_tw = nullptr;      // [2][nlon] cos / sin(2 pi m / nlon) of the zonal spectral filter
     double* sel_cand = nullptr;      // [2][cells] candidates of the two middle ranks after two radix passes (whole-globe handles)
@@ -456,6 +457,9 @@ int  qd_eco_daily_step_impl(qd_ctx* c, const double* soil_dev);
 void qd_eco_daily_release(qd_ctx* c);
 bool qd_eco_daily_stack(const qd_ctx* c, const double** L, int* n_species, int* n_layers);   // the resident LAI stack, when configured
 void qd_eco_div_release(qd_ctx* c);                                              // qd_eco_div.hip
+void qd_truecolor_release(qd_ctx* c);                                            // qd_truecolor.hip
+const double* qd_route_flow(const qd_ctx* c);                                    // qd_route.hip: the resident flow map [cells], or nullptr
+bool qd_phyto_daily_bands(const qd_ctx* c, const double** bands, int* n_bands, int64_t* n_steps);   // qd_phyto_daily.hip: the resident band stack, when configured
 bool qd_phyto_daily_couples(const qd_ctx* c);                               // the albedo launches blend WATER_ALPHA into the ocean
 bool qd_eco_is_f32(const qd_ctx* c, int field);                             // qd_eco.hip: slab stored as f32 (qd_eco_params.map_f32)
 void qd_eco_convert_slab(qd_ctx* c, const double* src, int src_f32, double* dst, int dst_f32);

@@ -356,6 +356,13 @@ extern "C" int qd_phyto_daily_log(qd_handle c, double* out, int max, int* n) {
     return d->lane.drain(c, "qd_phyto_daily_log", out, max, n);
 }
 
+bool qd_phyto_daily_bands(const qd_ctx* c, const double** bands, int* n_bands, int64_t* n_steps) {
+    const QdPhytoDaily* d = c->pdaily;
+    if (!d || !d->bands) return false;
+    *bands = d->bands; *n_bands = d->nb_alloc; *n_steps = d->n_steps;
+    return true;
+}
+
 extern "C" int qd_phyto_daily_download_bands(qd_handle c, double* host, size_t n) {
     if (!c || !host) return -1;
     QdPhytoDaily* d = c->pdaily;

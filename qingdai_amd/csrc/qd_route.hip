@@ -386,6 +386,8 @@ int qd_route_step_impl(qd_ctx* c, double dt, int s) {
     return ev != 0.0 ? qr_event(c, ev, 1) : 0;
 }
 
+const double* qd_route_flow(const qd_ctx* c) { return c->route ? c->route->flow : nullptr; }
+
 extern "C" int qd_route_download(qd_handle c, int which, double* host, size_t n) {
     if (!c || !host) return -1;
     QdRoute* r = c->route;

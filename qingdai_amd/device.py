@@ -336,6 +336,48 @@ class Device:
                   "qd_eco_diversity_download")
         return out
 
+    # ---- true-colour frame (qd_truecolor.hip)
+    def truecolor_configure(self, params, eco_tab=None, phyto_tab=None, phyto_bands=None, lake_mask=None):
+        """params: a _lib.qd_truecolor_params; eco_tab [7, nb_eco], phyto_tab [6, nb_phyto] (include/qingdai_hip.h); phyto_bands None =
+        the resident stack of the daily phytoplankton step, else a host [nb_phyto, lat, lon] stack; lake_mask [lat, lon] or None."""
+        dp, u8p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint8)
+        e = None if eco_tab is None else _c(eco_tab)
+        t = None if phyto_tab is None else _c(phyto_tab)
+        b = None if phyto_bands is None else _c(phyto_bands)
+        m = None if lake_mask is None else _c(lake_mask, np.uint8)
+        if e is not None and e.shape != (7, params.nb_eco) or t is not None and t.shape != (6, params.nb_phyto):
+            raise ValueError("truecolor_configure: eco_tab must be [7, nb_eco] and phyto_tab [6, nb_phyto]")
+        if b is not None and b.shape != (params.nb_phyto,) + self.shape or m is not None and m.shape != self.shape:
+            raise ValueError("truecolor_configure: phyto_bands must be [nb_phyto, lat, lon] and lake_mask [lat, lon]")
+        self._chk(self.lib.qd_truecolor_configure(self.h, ctypes.byref(params), ctypes.sizeof(params),
+                                                  None if e is None else e.ctypes.data_as(dp), None if t is None else t.ctypes.data_as(dp),
+                                                  None if b is None else b.ctypes.data_as(dp), None if m is None else m.ctypes.data_as(u8p)),
+                  "qd_truecolor_configure")
+
+    def truecolor_render(self, want_f64=False, flow=None):
+        """One frame from the resident state -> (sea_ice_area, mean_h_ice); the image stays resident (truecolor_image / truecolor_rgb).
+        flow None: the routing state's flow map; else a host [lat, lon] map."""
+        self.flush()
+        f = None if flow is None else _c(flow)
+        if f is not None and f.shape != self.shape:
+            raise ValueError(f"truecolor_render: flow must be {self.shape}, got {f.shape}")
+        out = (ctypes.c_double * 2)()
+        self._chk(self.lib.qd_truecolor_render(self.h, 1 if want_f64 else 0,
+                                               None if f is None else f.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out), "qd_truecolor_render")
+        return float(out[0]), float(out[1])
+
+    def truecolor_image(self):
+        """The u8 image [lat, lon, 3] of the last render, northernmost row first."""
+        out = np.empty(self.shape + (3,), dtype=np.uint8)
+        self._chk(self.lib.qd_truecolor_download(self.h, 0, out.ctypes.data, out.size), "qd_truecolor_download")
+        return out
+
+    def truecolor_rgb(self):
+        """The unquantised f64 rgb [lat, lon, 3] in grid order of the last render (want_f64=True)."""
+        out = np.empty(self.shape + (3,), dtype=np.float64)
+        self._chk(self.lib.qd_truecolor_download(self.h, 1, out.ctypes.data, out.size), "qd_truecolor_download")
+        return out
+
     # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident
     def phyto_configure(self, n_species, K_h, adv_alpha):
         self._chk(self.lib.qd_phyto_configure(self.h, int(n_species), float(K_h), float(adv_alpha)), "qd_phyto_configure")

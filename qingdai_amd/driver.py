@@ -40,8 +40,15 @@ summary are computed on the device from the LAI stack (the resident one under QD
 ends with the firing step, and the reference's files go to <QD_OUTPUT_DIR, default output>/ecology/ named by t_i / day:
 diversity_summary_day_*.txt and community_day_*.npz as the reference writes them, diversity_maps_day_*.npz (alpha_map, bc_local)
 in place of its two PNG maps.  QD_ECO_DIAG=1 prints one [Diversity] line per firing.
-Not carried over (out of the hot path): genes, plankton.json, matplotlib panels (a note is printed instead of
-a plot; the diversity annotation of the plot panel, run_simulation.py:1025-1052, goes with them).
+True-colour frames (QD_TRUECOLOR=1, default 0; QD_PLOT_EVERY_DAYS, default 10; plot_true_color, run_simulation.py:539-778,
+2426-2429): on the reference's plot clock -- the step with run-local index i % plot_interval_steps == 0 fires at its end, labelled
+by its start time t_i / day -- the frame is composed on the device from the resident state (qingdai_amd/truecolor.py,
+qd_truecolor_*), a chunk ends with the firing step, and each firing writes <QD_OUTPUT_DIR, default output>/true_color_day_*.png
+(n_lat x n_lon pixels, no axes) and prints the reference's [TrueColor] sea-ice line.  This replaces the earlier claim that the
+device driver produces no plots: with the switch on, the true-colour frame is produced; the other panels are not.
+Not carried over (out of the hot path): genes, plankton.json, the other matplotlib panels (plot_state, ocean,
+ecology, plankton, ISR; a note is printed instead; the diversity annotation of the plot panel, run_simulation.py:1025-1052, goes
+with them).
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -420,6 +427,43 @@ class Simulation:
             self._diversity_failed = True
             return None
 
+    # -- true-colour frames (run_simulation.py:1649-1651, 2426-2429)
+    def enable_truecolor(self, env=None):
+        """QD_TRUECOLOR=1: the renderer on this run's device and the reference's plot interval -> the TrueColor or None."""
+        env = os.environ if env is None else env
+        self.truecolor = None
+        if int(env.get("QD_TRUECOLOR", "0")) == 1:
+            from .truecolor import TrueColor, plot_interval_steps
+            self.truecolor = TrueColor(self)
+            self.truecolor_every = plot_interval_steps(env, self.dt)
+            self._truecolor_failed = False
+        return self.truecolor
+
+    def truecolor_due(self, i0, n_max):
+        """Looks at the next n_max steps, the first of which has the run-local index i0 -> (steps up to and including the first
+        firing step, that step's start time in days), or (None, None)."""
+        if getattr(self, "truecolor", None) is None or n_max <= 0:
+            return None, None
+        from .truecolor import firing_steps
+        fired = firing_steps(i0, n_max, self.truecolor_every)
+        if not fired:
+            return None, None
+        times, _ = self._span_times(fired[0] + 1, advance=False)
+        return fired[0] + 1, float(times[fired[0]]) / self.day_seconds
+
+    def run_truecolor(self, t_days, output_dir=None):
+        """One firing on the state as it stands (the end of the firing step): the frame file and the [TrueColor] line.  A failure
+        is reported and never stops the run, like the reference's plotting."""
+        try:
+            path, line = self.truecolor.write_frame(t_days, output_dir)
+            print(line)
+            return path
+        except Exception as e:      # noqa: BLE001
+            if not self._truecolor_failed:
+                print(f"[TrueColor] frame skipped: {e}")
+            self._truecolor_failed = True
+            return None
+
     def _run_chunk(self, n, energy_diag=False):
         origin = self._t_origin
         times, t_next = self._span_times(n)
@@ -601,7 +645,11 @@ def main(argv=None):
     n_total = len(np.arange(t0, t0 + duration, sim.dt))
     print(f"Grid resolution: {sim.grid.n_lat} lat x {sim.grid.n_lon} lon | dt = {sim.dt} s | "
           f"{duration / day:.1f} planetary days | {n_total} steps")
-    print("[Plots] matplotlib panels are not produced by the device driver (out of the hot path).")
+    if sim.enable_truecolor(env) is None:
+        print("[Plots] matplotlib panels are not produced by the device driver (out of the hot path).")
+    else:
+        print(f"[Plots] only the true-colour frame is produced by the device driver, every {sim.truecolor_every} steps; "
+              "the matplotlib panels are not.")
 
     autosave_on = int(env.get("QD_AUTOSAVE_ENABLE", "1")) == 1
     restart_out = env.get("QD_RESTART_OUT") or os.path.join("data", "restart_autosave.nc")
@@ -639,11 +687,15 @@ def main(argv=None):
     wall0 = time.perf_counter()
     while done < n_total:
         fire_in, fire_day = sim.diversity_due(min(200, n_total - done))
-        n = chunk_until(sim.t, sim.dt, next_autosave_t if autosave_on else None, n_total - done, fire_in=fire_in)
+        frame_in, frame_day = sim.truecolor_due(done, min(200, n_total - done))
+        n = chunk_until(sim.t, sim.dt, next_autosave_t if autosave_on else None, n_total - done,
+                        fire_in=min((k for k in (fire_in, frame_in) if k is not None), default=None))
         sim.run_steps(n)
         done += n
         if fire_in is not None and n == fire_in:               # the chunk ended with the firing step
             sim.run_diversity(fire_day)
+        if frame_in is not None and n == frame_in:             # (both cadences may fall on one step: diversity first, as in the reference)
+            sim.run_truecolor(frame_day)
         if int(env.get("QD_DYN_DIAG_PRINT", "1")) == 1:
             dg = sim.diagnostics()
             el = time.perf_counter() - wall0
