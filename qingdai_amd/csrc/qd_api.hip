@@ -637,39 +637,27 @@ extern "C" int qd_simple_albedo(qd_handle c, double ocean_albedo) {
 extern "C" int qd_atmos_step(qd_handle c, double dt, int has_albedo) {
     if (!c) return -1;
     hipSetDevice(c->desc.device);
-    int rc = qd_atmos_step_impl(c, dt, has_albedo);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_atmos_step: launch", e);
-    return 0;
+    if (int rc = qd_atmos_step_impl(c, dt, has_albedo)) return rc;
+    return qd_launch_check(c, "qd_atmos_step");
 }
 extern "C" int qd_ocean_step(qd_handle c, double dt, int compute_qnet, int use_ice_mask, int inject_sst) {
     if (!c) return -1;
     hipSetDevice(c->desc.device);
-    int rc = qd_ocean_step_impl(c, dt, compute_qnet, use_ice_mask, inject_sst);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_ocean_step: launch", e);
-    return 0;
+    if (int rc = qd_ocean_step_impl(c, dt, compute_qnet, use_ice_mask, inject_sst)) return rc;
+    return qd_launch_check(c, "qd_ocean_step");
 }
 extern "C" int qd_driver_physics(qd_handle c, double dt) {
     if (!c) return -1;
     hipSetDevice(c->desc.device);
-    int rc = qd_driver_physics_impl(c, dt);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_driver_physics: launch", e);
-    return 0;
+    if (int rc = qd_driver_physics_impl(c, dt)) return rc;
+    return qd_launch_check(c, "qd_driver_physics");
 }
 
 extern "C" int qd_hydrology_commit(qd_handle c, double dt) {
     if (!c) return -1;
     hipSetDevice(c->desc.device);
-    int rc = qd_hydrology_commit_impl(c, dt);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_hydrology_commit: launch", e);
-    return 0;
+    if (int rc = qd_hydrology_commit_impl(c, dt)) return rc;
+    return qd_launch_check(c, "qd_hydrology_commit");
 }
 
 int qd_side_join(qd_ctx* c) {
@@ -692,27 +680,27 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     if (with_route && !with_hydro) return qd_fail(c, "qd_step_n: river routing (bit7) needs the hydrology commit (bit3)");
     // whatever way this call ends: a lane's schedule was for this span only, and once the loop has begun the per-span switches are
     // back to what a stand-alone qd_* call expects
-    struct SpanGuard { qd_ctx* c; QdSpanLane* route = nullptr; QdSpanLane* daily = nullptr; QdSpanLane* edaily = nullptr; bool begun = false; ~SpanGuard() {
-        for (QdSpanLane* l : {route, daily, edaily}) if (l) l->clear_schedule();
+    struct SpanGuard { qd_ctx* c; QdSpanLane* lane[QD_N_LANES] = {}; bool begun = false; ~SpanGuard() {
+        for (QdSpanLane* l : lane) if (l) l->clear_schedule();
         if (begun) { c->diag_write = 1; c->want_pcond_ahead = 0; c->pcond_ahead = 0; c->defer_final = 0; c->final_pending.on = 0; qd_saf_drop(c); }
     } } span{c};
-    if (with_route && !(span.route = qd_route_span_begin(c, n))) return -1;
+    if (with_route && !(span.lane[QD_LANE_ROUTE] = qd_route_span_begin(c, n))) return -1;
     const int with_pdaily = flags & 256;
-    if (with_pdaily && !(span.daily = qd_phyto_daily_span_begin(c, n, with_phys))) return -1;
+    if (with_pdaily && !(span.lane[QD_LANE_PHYTO_DAILY] = qd_phyto_daily_span_begin(c, n, with_phys))) return -1;
     const int with_edaily = flags & 512;
-    if (with_edaily && !(span.edaily = qd_eco_daily_span_begin(c, n, with_eco))) return -1;
+    if (with_edaily && !(span.lane[QD_LANE_ECO_DAILY] = qd_eco_daily_span_begin(c, n, with_eco))) return -1;
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
         int rc;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
-        if (with_pdaily && span.daily->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
+        if (with_pdaily && span.lane[QD_LANE_PHYTO_DAILY]->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
         // PopulationManager.step_daily (run_simulation.py:1786-1810) reads W_LAND, GLACIER and E_day as the previous step left them and
         // writes the LAI stack, ECO_LAI and E_day before this step's canopy test and E_day accumulation; dt > day fires more than once.
         // The hoisted precipitation block of this step (part 1) reads and writes none of these, so it stays hoisted on firing steps
         if (with_edaily)
-            for (int r = (int)span.edaily->at(s); r > 0; --r) if ((rc = qd_eco_daily_step_impl(c, nullptr))) return rc;
+            for (int r = (int)span.lane[QD_LANE_ECO_DAILY]->at(s); r > 0; --r) if ((rc = qd_eco_daily_step_impl(c, nullptr))) return rc;
         // EcologyAdapter.step_subdaily sits between the glacier mask and the base-albedo blend (run_simulation.py:2075-2104):
         // its clock / canopy / alpha part runs before the albedo kernel, its E_day += isr dt rides on this step's forcing launch
         if (with_eco && c->eco.p.albedo_couple) { if ((rc = qd_eco_canopy_impl(c, dt))) return rc; c->eco.eday_dt = c->eco.p.use_lai ? dt : 0.0; }
@@ -745,7 +733,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // nothing the ocean step, the tracers, the individuals or the bucket touch, and writes only what the rest of step s + 1's
         // driver physics reads: it is queued inside the ocean step, between the stress kernel and the host's wait for the CFL maxima.
         // (not on a routing event step: the event reads this step's PRECIP, which the hoisted block would overwrite)
-        if (with_ocean && with_phys && c->geo.full && c->hoist_precip && s + 1 < n && !(with_route && span.route->at(s) != 0.0))
+        if (with_ocean && with_phys && c->geo.full && c->hoist_precip && s + 1 < n && !(with_route && span.lane[QD_LANE_ROUTE]->at(s) != 0.0))
             c->before_cfl_wait = [c, dt]() { const int r = qd_driver_physics_impl(c, dt, nullptr, 1); if (!r) c->precip_done = 1; return r; };
         if (with_ocean) { rc = qd_ocean_step_impl(c, dt, 1, 1, 1); c->before_cfl_wait = nullptr; if (rc) return rc; }
         if (with_phyto && (rc = qd_phyto_step_impl(c, dt))) return rc;      // run_simulation.py:2254-2258
@@ -755,9 +743,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (with_route && (rc = qd_route_step_impl(c, dt, s))) return rc;           // run_simulation.py:2342-2348
     }
     c->diag_write = 1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_step_n: launch", e);
-    return 0;
+    return qd_launch_check(c, "qd_step_n");
 }
 
 // ------------------------------------------------------------------ operator seam

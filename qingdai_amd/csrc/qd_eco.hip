@@ -13,6 +13,7 @@
 // forcing kernel plus one extra read in the albedo kernel.  The individuals never see a [NB][lat][lon] band stack: each
 // thread evaluates the band split at its own sampled cell.  All of it is HBM-bound pointwise work.
 #include "qd_internal.h"
+#include "qd_blockred.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -100,11 +101,6 @@ k_eco_banded(size_t n, QdBandR W, const double* __restrict__ f, const uint8_t* _
     qd_mst(out, o, f32, qd_clip(acc, 0.0, 1.0));
 }
 
-__device__ __forceinline__ double qd_eco_wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
 // four row partials of lai_delta_ratio (population.py:903-907): sum |now - snap| and count over non-NaN, sum max(snap, 1e-6)
 // and count over non-NaN
 __global__ void __launch_bounds__(QD_BLOCK)
@@ -119,7 +115,7 @@ k_eco_ratio_rows(QdGeom G, const double* __restrict__ lai, const double* __restr
         const double m = qd_max(s, 1e-6);
         if (m == m) { a2 += m; a3 += 1.0; }
     }
-    a0 = qd_eco_wsum(a0); a1 = qd_eco_wsum(a1); a2 = qd_eco_wsum(a2); a3 = qd_eco_wsum(a3);
+    a0 = qd_wave_sum(a0); a1 = qd_wave_sum(a1); a2 = qd_wave_sum(a2); a3 = qd_wave_sum(a3);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) { sm[0][wv] = a0; sm[1][wv] = a1; sm[2][wv] = a2; sm[3][wv] = a3; }
     __syncthreads();
@@ -135,7 +131,7 @@ k_eco_ratio_finish(const double* __restrict__ partial, int nrows, double* __rest
     for (int q = 0; q < 4; ++q) {
         double a = 0.0;
         for (int k = threadIdx.x; k < nrows; k += QD_BLOCK) a += partial[(size_t)q * nrows + k];
-        a = qd_eco_wsum(a);
+        a = qd_wave_sum(a);
         __syncthreads();
         if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = a;
         __syncthreads();
@@ -235,9 +231,7 @@ extern "C" int qd_eco_set_lai_layers(qd_handle c, const double* layers, int n_pl
         E.snap_version = E.lai_version;
     }
     qd_mark(c, {lai, c->f[QD_F_ECO_LAI_SNAP]}, c->geo.halo);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_eco_set_lai_layers: launch", e);
-    return 0;
+    return qd_launch_check(c, "qd_eco_set_lai_layers");
 }
 
 // lai_delta_ratio (population.py:903-907); synchronises -- only called on steps after the layers changed
@@ -310,9 +304,7 @@ extern "C" int qd_eco_substep(qd_handle c, double dt) {
     if (!c->eco.configured) return qd_fail(c, "qd_eco_substep: qd_eco_configure has not been called");
     if (c->eco.p.use_lai && qd_eco_eday_impl(c, dt)) return -1; // pop.step_subdaily first (adapter.py:151-155)
     if (qd_eco_canopy_impl(c, dt)) return -1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_eco_substep: launch", e);
-    return 0;
+    return qd_launch_check(c, "qd_eco_substep");
 }
 
 extern "C" int qd_eco_banded_alpha(qd_handle c, int nb, const double* r_eff, const double* w_b) {
@@ -333,9 +325,7 @@ extern "C" int qd_eco_banded_alpha(qd_handle c, int nb, const double* r_eff, con
                        c->f[QD_F_ECO_ALPHA_BANDED], E.p.map_f32 ? 1 : 0);
     qd_mark(c, {c->f[QD_F_ECO_ALPHA_BANDED], c->f[QD_F_ECO_F]}, c->geo.halo);
     E.banded_valid = 1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_eco_banded_alpha: launch", e);
-    return 0;
+    return qd_launch_check(c, "qd_eco_banded_alpha");
 }
 
 extern "C" int qd_eco_get_state(qd_handle c, double* out) {
@@ -422,9 +412,7 @@ extern "C" int qd_indiv_substep(qd_handle c, double dt, int* fired) {
     if (!c) return -1;
     hipSetDevice(c->desc.device);
     if (qd_indiv_substep_impl(c, dt, fired)) return -1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_indiv_substep: launch", e);
-    return 0;
+    return qd_launch_check(c, "qd_indiv_substep");
 }
 
 extern "C" int qd_indiv_download(qd_handle c, double* E_day, double* stress) {

@@ -16,6 +16,7 @@
 //            k_ecod_final reduces them in a fixed order into the lane's record {firings, LAI_min, LAI_mean, LAI_max}.
 // All pointwise or 5 / 9-point, row-major coalesced, HBM-bound; f64 throughout, contraction off (Makefile), no atomics.
 #include "qd_span.h"
+#include "qd_blockred.h"
 #include <algorithm>
 
 struct QdEcoDaily {
@@ -25,8 +26,7 @@ struct QdEcoDaily {
     double* L = nullptr;              // [S * K][cells] LAI_layers_SK
     int planes = 0;
     double* share = nullptr;          // [cells] per-neighbour share of the species being spread (and the staged soil index of a seam call)
-    double* partial = nullptr;        // [4][nblk]
-    int nblk = 0;
+    QdPartials partial;               // [4][nblk]: sum, count, min, max of the land LAI
     int64_t n_fired = 0;
     QdSpanLane lane;                  // qd_eco_daily_schedule: firings per step of the next span; the summary log
 };
@@ -43,25 +43,7 @@ struct QdEDArgs {
     int lai_f32;
 };
 
-__device__ __forceinline__ double qd_ed_wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ double qd_ed_wmin(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmin(x, __shfl_down(x, o, 64));
-    return x;
-}
-__device__ __forceinline__ double qd_ed_wmax(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_down(x, o, 64));
-    return x;
-}
-// x ** e as NumPy evaluates it for a scalar exponent: 1, 2 and 0.5 take its exact fast paths
-__device__ __forceinline__ double qd_ed_pow(double x, double e) {
-    return e == 1.0 ? x : (e == 2.0 ? x * x : (e == 0.5 ? sqrt(x) : pow(x, e)));
-}
+__constant__ const QdRedOp qd_ed_ops[4] = {QD_RED_SUM, QD_RED_SUM, QD_RED_MIN, QD_RED_MAX};
 
 // ------------------------------------------------------------------ front: soil, gate, growth / senescence into the layers
 __global__ void __launch_bounds__(QD_BLOCK)
@@ -78,7 +60,7 @@ k_ecod_front(QdEDArgs A, const double* __restrict__ soil_in) {
     const double E = qd_nn(A.eday[o]);
     const double growth = land ? P.growth_per_j * ((1.0 - P.repro_frac) * E) : 0.0;
     const double sen = land ? (P.senesce_per_day * P.stress_strength) * qd_max(0.0, P.stress_thresh - sc) : 0.0;
-    A.gate[o] = land ? (P.gate_soil ? qd_ed_pow(sc, P.soil_exp) : 1.0) : 0.0;
+    A.gate[o] = land ? (P.gate_soil ? qd_pow_np(sc, P.soil_exp) : 1.0) : 0.0;
     const int S = P.n_species, K = P.n_layers;
     if (K <= 1) return;                                        // population.py:499-501: only the aggregate moves, and it is overwritten
 
@@ -234,9 +216,8 @@ k_ecod_apply(QdEDArgs A, int s, int seed) {
 // ------------------------------------------------------------------ finish: age, germination, bank decay, ECO_LAI, E_day, partials
 __global__ void __launch_bounds__(QD_BLOCK)
 k_ecod_finish(QdEDArgs A) {
-    __shared__ double sm[4][QD_BLOCK / 64];
     const int j = blockIdx.x * QD_BLOCK + threadIdx.x;
-    double d_sum = 0.0, d_cnt = 0.0, d_min = INFINITY, d_max = -INFINITY;
+    double d[4] = {0.0, 0.0, INFINITY, -INFINITY};             // sum, count, min, max
     if (j < A.nlon) {
         const size_t o = (size_t)blockIdx.y * A.nlon + j;
         const qd_eco_daily_params& P = A.p;
@@ -259,35 +240,19 @@ k_ecod_finish(QdEDArgs A) {
         A.bank[o] = qd_max(0.0, bank - germ) * qd_max(0.0, 1.0 - P.bank_decay);
         if (A.lai_f32) reinterpret_cast<float*>(A.lai)[o] = (float)post; else A.lai[o] = post;
         A.eday[o] = 0.0;
-        if (land) { d_sum = post; d_cnt = 1.0; d_min = post; d_max = post; }
+        if (land) { d[0] = post; d[1] = 1.0; d[2] = post; d[3] = post; }
     }
-    d_sum = qd_ed_wsum(d_sum); d_cnt = qd_ed_wsum(d_cnt); d_min = qd_ed_wmin(d_min); d_max = qd_ed_wmax(d_max);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { sm[0][wv] = d_sum; sm[1][wv] = d_cnt; sm[2][wv] = d_min; sm[3][wv] = d_max; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = sm[0][0], n = sm[1][0], lo = sm[2][0], hi = sm[3][0];
-        for (int k = 1; k < QD_BLOCK / 64; ++k) { a += sm[0][k]; n += sm[1][k]; lo = fmin(lo, sm[2][k]); hi = fmax(hi, sm[3][k]); }
-        const size_t nblk = (size_t)gridDim.x * gridDim.y, b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        A.partial[b] = a; A.partial[nblk + b] = n; A.partial[2 * nblk + b] = lo; A.partial[3 * nblk + b] = hi;
-    }
+    qd_block_partials(d, 4, qd_ed_ops, A.partial, (size_t)gridDim.x * gridDim.y, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // one workgroup: the block partials in a fixed order -> {firings, LAI_min, LAI_mean, LAI_max} (zeros without land)
 __global__ void __launch_bounds__(QD_BLOCK)
 k_ecod_final(const double* __restrict__ partial, int nblk, double seq, double* __restrict__ rec) {
-    __shared__ double sm[4][QD_BLOCK / 64];
-    double a = 0.0, n = 0.0, lo = INFINITY, hi = -INFINITY;
-    for (int k = threadIdx.x; k < nblk; k += QD_BLOCK) {
-        a += partial[k]; n += partial[(size_t)nblk + k];
-        lo = fmin(lo, partial[(size_t)2 * nblk + k]); hi = fmax(hi, partial[(size_t)3 * nblk + k]);
-    }
-    a = qd_ed_wsum(a); n = qd_ed_wsum(n); lo = qd_ed_wmin(lo); hi = qd_ed_wmax(hi);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { sm[0][wv] = a; sm[1][wv] = n; sm[2][wv] = lo; sm[3][wv] = hi; }
-    __syncthreads();
+    double t[4];
+    qd_planes_strided(partial, nblk, 4, qd_ed_ops, t);
+    qd_block_totals(t, qd_ed_ops);
     if (threadIdx.x == 0) {
-        for (int k = 1; k < QD_BLOCK / 64; ++k) { a += sm[0][k]; n += sm[1][k]; lo = fmin(lo, sm[2][k]); hi = fmax(hi, sm[3][k]); }
+        const double a = t[0], n = t[1], lo = t[2], hi = t[3];
         rec[0] = seq;
         rec[1] = n > 0.0 ? lo : 0.0; rec[2] = n > 0.0 ? a / n : 0.0; rec[3] = n > 0.0 ? hi : 0.0;
     }
@@ -297,7 +262,7 @@ k_ecod_final(const double* __restrict__ partial, int nblk, double seq, double* _
 void qd_eco_daily_release(qd_ctx* c) {
     QdEcoDaily* d = c->edaily;
     if (!d) return;
-    void* p[] = {d->w, d->L, d->share, d->partial, d->lane.log};
+    void* p[] = {d->w, d->L, d->share, d->partial.p, d->lane.log};
     for (void* q : p) if (q) hipFree(q);
     delete d;
     c->edaily = nullptr;
@@ -310,12 +275,10 @@ bool qd_eco_daily_stack(const qd_ctx* c, const double** L, int* n_species, int* 
     return true;
 }
 
-static bool ed_whole_globe(const qd_ctx* c) { return c->geo.full && c->desc.world <= 1; }
-
 extern "C" int qd_eco_daily_configure(qd_handle c, const qd_eco_daily_params* p, size_t sz, const int32_t* mode, const double* w) {
     if (!c || !p || !mode || !w) return -1;
     if (sz != sizeof(qd_eco_daily_params)) return qd_fail(c, "qd_eco_daily_configure: struct size mismatch (ABI)");
-    if (!ed_whole_globe(c))
+    if (!qd_whole_globe(c))
         return qd_fail(c, "qd_eco_daily_configure: the daily vegetation step needs a whole-globe handle (world == 1, n_rows == n_lat); "
                           "latitude bands are not supported");
     const int S = p->n_species, K = p->n_layers;
@@ -338,13 +301,9 @@ extern "C" int qd_eco_daily_configure(qd_handle c, const qd_eco_daily_params* p,
     QD_HIP(c, hipMalloc(&d->w, (size_t)S * sizeof(double)));
     QD_HIP(c, hipMemcpy(d->w, w, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
     if (!d->share) QD_HIP(c, hipMalloc(&d->share, cells * sizeof(double)));
-    const int nblk = ((c->geo.nlon + QD_BLOCK - 1) / QD_BLOCK) * c->geo.nrows;
-    if (!d->partial || d->nblk != nblk) {
-        if (d->partial) { hipFree(d->partial); d->partial = nullptr; }
-        QD_HIP(c, hipMalloc(&d->partial, (size_t)4 * nblk * sizeof(double)));
-        d->nblk = nblk;
-    }
+    if (int rc = d->partial.ensure(c, 4, ((c->geo.nlon + QD_BLOCK - 1) / QD_BLOCK) * c->geo.nrows)) return rc;
     d->lane.width = QD_ECO_DAILY_LOG_W;
+    d->lane.counts = true;                                      // a step may fire more than once (dt > day)
     if (!d->lane.log) QD_HIP(c, hipMalloc(&d->lane.log, d->lane.log_doubles() * sizeof(double)));
     d->lane.reset();
     QD_HIP(c, hipMemsetAsync(c->f[QD_F_ECO_AGE], 0, cells * sizeof(double), c->stream));
@@ -391,7 +350,7 @@ int qd_eco_daily_step_impl(qd_ctx* c, const double* soil_dev) {
     A.eday = c->f[QD_F_ECO_EDAY]; A.age = c->f[QD_F_ECO_AGE]; A.bank = c->f[QD_F_ECO_SEEDBANK]; A.gate = c->f[QD_F_ECO_GATE];
     A.share = d->share; A.lai = c->f[QD_F_ECO_LAI];
     A.wland = c->f[QD_F_W_LAND]; A.glacier = c->f[QD_F_GLACIER];
-    A.partial = d->partial;
+    A.partial = d->partial.p;
     A.lai_f32 = c->eco.p.map_f32 ? 1 : 0;
     const dim3 grid((A.nlon + QD_BLOCK - 1) / QD_BLOCK, A.nlat), block(QD_BLOCK);
     hipLaunchKernelGGL(k_ecod_front, grid, block, 0, c->stream, A, soil_dev);
@@ -402,7 +361,7 @@ int qd_eco_daily_step_impl(qd_ctx* c, const double* soil_dev) {
         }
     hipLaunchKernelGGL(k_ecod_finish, grid, block, 0, c->stream, A);
     d->n_fired += 1;
-    hipLaunchKernelGGL(k_ecod_final, dim3(1), block, 0, c->stream, d->partial, (int)(grid.x * grid.y), (double)d->n_fired, d->lane.next());
+    hipLaunchKernelGGL(k_ecod_final, dim3(1), block, 0, c->stream, d->partial.p, (int)(grid.x * grid.y), (double)d->n_fired, d->lane.next());
     // the canopy state of qd_eco_set_lai_layers(h, layers, n, 0): new layers, snapshot and recompute clock untouched
     c->eco.have_lai = 1; c->eco.lai_version++;
     qd_mark(c, {c->f[QD_F_ECO_LAI], c->f[QD_F_ECO_EDAY], c->f[QD_F_ECO_AGE], c->f[QD_F_ECO_SEEDBANK], c->f[QD_F_ECO_GATE]}, 0);
@@ -411,7 +370,7 @@ int qd_eco_daily_step_impl(qd_ctx* c, const double* soil_dev) {
 
 extern "C" int qd_eco_daily_step(qd_handle c, const double* soil_index) {
     if (!c) return -1;
-    if (!ed_whole_globe(c)) return qd_fail(c, "qd_eco_daily_step: the daily vegetation step needs a whole-globe handle; latitude bands are not supported");
+    if (!qd_whole_globe(c)) return qd_fail(c, "qd_eco_daily_step: the daily vegetation step needs a whole-globe handle; latitude bands are not supported");
     QdEcoDaily* d = c->edaily;
     if (!d) return qd_fail(c, "qd_eco_daily_step: qd_eco_daily_configure has not been called");
     hipSetDevice(c->desc.device);
@@ -420,40 +379,28 @@ extern "C" int qd_eco_daily_step(qd_handle c, const double* soil_index) {
         QD_HIP(c, hipStreamSynchronize(c->stream));             // the host buffer is only borrowed for the call
     }
     if (int rc = qd_eco_daily_step_impl(c, soil_index ? d->share : nullptr)) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_eco_daily_step: launch", e);
-    return 0;
+    return qd_launch_check(c, "qd_eco_daily_step");
 }
 
+static QdSpanLane* ed_lane(qd_ctx* c) { return c && c->edaily ? &c->edaily->lane : nullptr; }
+static const char* const ED_MISSING = "qd_eco_daily_configure has not been called";
+
 extern "C" int qd_eco_daily_schedule(qd_handle c, int n, const int32_t* fire) {
-    if (!c || n < 0 || (n && !fire)) return -1;
-    if (!c->edaily) return qd_fail(c, "qd_eco_daily_schedule: qd_eco_daily_configure has not been called");
-    for (int s = 0; s < n; ++s) if (fire[s] < 0) return qd_fail(c, "qd_eco_daily_schedule: negative firing count");
-    c->edaily->lane.set(fire, n);
-    return 0;
+    return qd_lane_schedule(c, ed_lane(c), n, fire, "qd_eco_daily_schedule", ED_MISSING);
 }
 
 QdSpanLane* qd_eco_daily_span_begin(qd_ctx* c, int n, int with_eco) {
-    const char* why = nullptr;
-    QdEcoDaily* d = c->edaily;
-    if (!ed_whole_globe(c)) why = "qd_step_n: the daily vegetation step (bit9) needs a whole-globe handle; latitude bands are not supported";
-    else if (!d) why = "qd_step_n: bit9 set but qd_eco_daily_configure has not been called";
-    else if (!with_eco) why = "qd_step_n: the daily vegetation step (bit9) needs the ecology sub-step (bit5)";
-    else if (!d->lane.scheduled(n)) why = "qd_step_n: bit9 needs a qd_eco_daily_schedule of exactly n steps before the span";
-    else {
-        double firings = 0.0;                                   // a step may fire more than once (dt > day): count them all
-        for (double x : d->lane.sched) firings += x;
-        if (d->lane.n + firings > QD_SPAN_LOG_CAP) why = "qd_step_n: the span's daily vegetation steps would overflow the summary log (drain it first)";
-    }
-    if (why) qd_fail(c, why);
-    return why ? nullptr : &d->lane;
+    static const QdSpanTexts T = {
+        "qd_step_n: the daily vegetation step (bit9) needs a whole-globe handle; latitude bands are not supported",
+        "qd_step_n: bit9 set but qd_eco_daily_configure has not been called",
+        "qd_step_n: bit9 needs a qd_eco_daily_schedule of exactly n steps before the span",
+        "qd_step_n: the span's daily vegetation steps would overflow the summary log (drain it first)"};
+    return qd_lane_span_begin(c, ed_lane(c), n, T,
+                              with_eco ? nullptr : "qd_step_n: the daily vegetation step (bit9) needs the ecology sub-step (bit5)");
 }
 
 extern "C" int qd_eco_daily_log(qd_handle c, double* out, int max, int* n) {
-    if (!c || !n) return -1;
-    QdEcoDaily* d = c->edaily;
-    if (!d) return qd_fail(c, "qd_eco_daily_log: qd_eco_daily_configure has not been called");
-    return d->lane.drain(c, "qd_eco_daily_log", out, max, n);
+    return qd_lane_drain(c, ed_lane(c), out, max, n, "qd_eco_daily_log", ED_MISSING);
 }
 
 extern "C" int qd_eco_daily_state(qd_handle c, int64_t* n_firings) {

@@ -24,6 +24,7 @@
 // atomics.  No transcendental touches L_s or the Bray-Curtis map: both equal NumPy's bit for bit.
 #include "qd_internal.h"
 #include "qd_wave.h"
+#include "qd_blockred.h"
 #include <algorithm>
 
 #define QD_DIV_R 4                // rows per thread of k_div_alpha
@@ -38,7 +39,7 @@ struct QdEcoDiv {
     double* stage = nullptr; size_t stage_cap = 0;    // a host-passed stack
     uint8_t* land = nullptr; size_t land_cap = 0;     // a caller's land mask (qd_eco_diversity_on)
     double* wrow = nullptr; int wrow_cap = 0;         // [nlat]
-    double* partial = nullptr; size_t partial_cap = 0;   // [S + 1][nblk]
+    QdPartials partial;                               // [1 + S][nblk]: alpha, then L_s
     double* out3 = nullptr;                           // device {alpha_mean, gamma_eff, beta_whittaker}
     double summary[3] = {0, 0, 0};
 };
@@ -52,11 +53,6 @@ struct QdDivArgs {
     double* partial;
 };
 
-__device__ __forceinline__ double qd_dv_wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
 __device__ __forceinline__ int qd_dv_east_i(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x130, 0xf, 0xf, true); }   // lane + 1
 __device__ __forceinline__ int qd_dv_west_i(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x138, 0xf, 0xf, true); }   // lane - 1
 
@@ -64,13 +60,11 @@ __device__ __forceinline__ int qd_dv_west_i(int x) { return __builtin_amdgcn_upd
 template <int SMAX>
 __global__ void __launch_bounds__(QD_BLOCK)
 k_div_alpha(QdDivArgs A) {
-    __shared__ double sm[SMAX + 1][QD_BLOCK / 64];
     const int j = blockIdx.x * QD_BLOCK + threadIdx.x;
     const int S = A.S, K = A.K;
-    double acc[SMAX];
-    double acc_a = 0.0;
+    double acc[SMAX + 1];                                      // [0] alpha, [1 + s] L_s
 #pragma unroll
-    for (int s = 0; s < SMAX; ++s) acc[s] = 0.0;
+    for (int s = 0; s <= SMAX; ++s) acc[s] = 0.0;
     if (j < A.nlon) {
         for (int rr = 0; rr < QD_DIV_R; ++rr) {
             const int row = blockIdx.y * QD_DIV_R + rr;
@@ -122,32 +116,17 @@ k_div_alpha(QdDivArgs A) {
             A.alpha[o] = alpha;
             if (land) {                                        // np.nansum: NaN terms count as 0
                 const double ta = alpha * wn;
-                if (ta == ta) acc_a += ta;
+                if (ta == ta) acc[0] += ta;
 #pragma unroll
                 for (int s = 0; s < SMAX; ++s)
                     if (s < S) {
                         const double t = ls[s] * wn;
-                        if (t == t) acc[s] += t;
+                        if (t == t) acc[s + 1] += t;
                     }
             }
         }
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    acc_a = qd_dv_wsum(acc_a);
-    if (lane == 0) sm[0][wv] = acc_a;
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s)
-        if (s < S) {
-            const double t = qd_dv_wsum(acc[s]);
-            if (lane == 0) sm[s + 1][wv] = t;
-        }
-    __syncthreads();
-    if ((int)threadIdx.x <= S) {
-        double t = sm[threadIdx.x][0];
-        for (int k = 1; k < QD_BLOCK / 64; ++k) t += sm[threadIdx.x][k];
-        const size_t nblk = (size_t)gridDim.x * gridDim.y, b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        A.partial[(size_t)threadIdx.x * nblk + b] = t;
-    }
+    qd_block_partials(acc, S + 1, nullptr, A.partial, (size_t)gridDim.x * gridDim.y, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // ------------------------------------------------------------------ local Bray-Curtis map
@@ -211,14 +190,7 @@ k_div_bc(QdDivArgs A, int ncs, int nstrips) {
 __global__ void __launch_bounds__(QD_BLOCK)
 k_div_final(const double* __restrict__ partial, int nblk, int S, double* __restrict__ out3) {
     __shared__ double tot[QD_MAX_SPECIES + 1];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int q = wv; q <= S; q += QD_BLOCK / 64) {            // one wave per quantity, lanes strided over the workgroups' partials
-        double a = 0.0;
-        for (int k = lane; k < nblk; k += 64) a += partial[(size_t)q * nblk + k];
-        a = qd_dv_wsum(a);
-        if (lane == 0) tot[q] = a;
-    }
-    __syncthreads();
+    qd_planes_by_wave(partial, nblk, S + 1, tot);
     if (threadIdx.x == 0) {
         const double alpha_mean = tot[0];
         double tsum = 0.0;
@@ -240,7 +212,7 @@ k_div_final(const double* __restrict__ partial, int nblk, int S, double* __restr
 void qd_eco_div_release(qd_ctx* c) {
     QdEcoDiv* d = c->ediv;
     if (!d) return;
-    void* p[] = {d->Ls, d->alpha, d->bc, d->lpair, d->stage, d->land, d->wrow, d->partial, d->out3};
+    void* p[] = {d->Ls, d->alpha, d->bc, d->lpair, d->stage, d->land, d->wrow, d->partial.p, d->out3};
     for (void* q : p) if (q) hipFree(q);
     delete d;
     c->ediv = nullptr;
@@ -276,8 +248,7 @@ static int div_run(qd_ctx* c, const char* who, int nlat, int nlon, const uint8_t
     }
     { size_t cap = (size_t)d->wrow_cap; QD_HIP(c, div_grow(&d->wrow, &cap, (size_t)nlat)); d->wrow_cap = (int)cap; }
     const dim3 grid_a((nlon + QD_BLOCK - 1) / QD_BLOCK, (nlat + QD_DIV_R - 1) / QD_DIV_R), block(QD_BLOCK);
-    const size_t nblk = (size_t)grid_a.x * grid_a.y;
-    QD_HIP(c, div_grow(&d->partial, &d->partial_cap, (size_t)(S + 1) * nblk));
+    if (int rc = d->partial.ensure(c, S + 1, (int)(grid_a.x * grid_a.y))) return rc;
     if (!d->out3) QD_HIP(c, hipMalloc(&d->out3, 3 * sizeof(double)));
     if (layers_host) {
         QD_HIP(c, div_grow(&d->stage, &d->stage_cap, (size_t)S * K * cells));
@@ -295,7 +266,7 @@ static int div_run(qd_ctx* c, const char* who, int nlat, int nlon, const uint8_t
     QdDivArgs A;
     A.nlat = nlat; A.nlon = nlon; A.S = S; A.K = K;
     A.L = L_dev; A.plane = cells; A.land = land; A.wrow = d->wrow;
-    A.Ls = d->Ls; A.alpha = d->alpha; A.bc = d->bc; A.lpair = d->lpair; A.partial = d->partial;
+    A.Ls = d->Ls; A.alpha = d->alpha; A.bc = d->bc; A.lpair = d->lpair; A.partial = d->partial.p;
     {
         QdScope sc(c, "eco_diversity");
         if (S <= 8) hipLaunchKernelGGL(k_div_alpha<8>, grid_a, block, 0, c->stream, A);
@@ -304,7 +275,7 @@ static int div_run(qd_ctx* c, const char* who, int nlat, int nlon, const uint8_t
         const int ncs = (nlon + QD_DIV_TC - 1) / QD_DIV_TC, nrs = (nlat + QD_DIV_RS - 1) / QD_DIV_RS;
         const int nstrips = ncs * nrs, wpb = QD_BLOCK / 64;
         hipLaunchKernelGGL(k_div_bc, dim3((nstrips + wpb - 1) / wpb), block, 0, c->stream, A, ncs, nstrips);
-        hipLaunchKernelGGL(k_div_final, dim3(1), block, 0, c->stream, d->partial, (int)nblk, S, d->out3);
+        hipLaunchKernelGGL(k_div_final, dim3(1), block, 0, c->stream, d->partial.p, d->partial.nblk, S, d->out3);
     }
     QD_HIP(c, hipMemcpyAsync(d->summary, d->out3, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     QD_HIP(c, hipStreamSynchronize(c->stream));
@@ -324,7 +295,7 @@ static int div_sizes(qd_ctx* c, const char* who, int S, int K) {
 extern "C" int qd_eco_diversity(qd_handle c, const double* layers, int n_species, int n_layers, const double* w_norm_row, double* summary3) {
     if (!c || !w_norm_row) return -1;
     const char* who = "qd_eco_diversity";
-    if (!(c->geo.full && c->desc.world <= 1))
+    if (!qd_whole_globe(c))
         return qd_fail(c, "qd_eco_diversity: the diversity diagnostics need a whole-globe handle (world == 1, n_rows == n_lat); "
                           "latitude bands are not supported");
     if (int rc = div_sizes(c, who, n_species, n_layers)) return rc;

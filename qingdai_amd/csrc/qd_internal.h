@@ -339,6 +339,29 @@ extern thread_local std::string g_qd_create_err;
 
 int qd_fail(qd_ctx* c, const char* what, hipError_t e = hipSuccess);
 #define QD_HIP(c, call) do { hipError_t _e = (call); if (_e != hipSuccess) return qd_fail((c), #call, _e); } while (0)
+// the epilogue of an extern "C" wrapper that launched kernels: a refused launch becomes "<who>: launch: <hip error>"
+inline int qd_launch_check(qd_ctx* c, const char* who) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : qd_fail(c, (std::string(who) + ": launch").c_str(), e);
+}
+// the band is the whole globe on one device (qd_create refuses such a handle with a halo): what the global-network and
+// one-thread-per-cell feature modules need
+inline bool qd_whole_globe(const qd_ctx* c) { return c->geo.full && c->desc.world <= 1; }
+// per-workgroup partials of a two-stage reduction (qd_blockred.h), [planes][nblk] on the device; grows, never shrinks
+struct QdPartials {
+    double* p = nullptr; int nblk = 0, planes = 0; size_t cap = 0;
+    int ensure(qd_ctx* c, int planes_, int nblk_) {          // the caller has synchronised the stream
+        const size_t n = (size_t)planes_ * (size_t)nblk_;
+        if (!p || cap < n) {
+            free();
+            QD_HIP(c, hipMalloc(&p, n * sizeof(double)));
+            cap = n;
+        }
+        planes = planes_; nblk = nblk_;
+        return 0;
+    }
+    void free() { if (p) hipFree(p); p = nullptr; cap = 0; }
+};
 
 struct QdScope {               // optional per-kernel-group timing with hipEvents on the handle's stream
     qd_ctx* c; const char* name; hipEvent_t e0 = nullptr, e1 = nullptr; bool on = false, attach = false;

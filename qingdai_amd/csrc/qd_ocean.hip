@@ -22,6 +22,7 @@
 #include "qd_fused.h"
 #include "qd_ocntail.h"
 #include "qd_band.h"
+#include "qd_blockred.h"
 
 QdColP qd_make_colp(const qd_ctx* c, double dt);   // qd_atmos.hip
 
@@ -43,8 +44,6 @@ k_qnet(QdGeom G, QdColP P, const double* __restrict__ isr, const double* __restr
     qnet[o] = F.SW_sfc - F.LW_sfc - F.SH - LH[o];
     icemask[o] = (hi > 0.0) ? 1 : 0;
 }
-
-__device__ __forceinline__ double qd_wave_sum_d(double x);
 
 // ------------------------------------------------------------------ energy budget means (energy.py:494-538)
 // cos-weighted row sums of the ten budget terms, from the same flux function as k_qnet:
@@ -75,7 +74,7 @@ k_energy_diag(QdGeom G, QdTabs T, QdColP P, const double* __restrict__ isr, cons
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < QD_NDIAG; ++k) { const double s = qd_wave_sum_d(acc[k]); if (lane == 0) sm[k][wv] = s; }
+    for (int k = 0; k < QD_NDIAG; ++k) { const double s = qd_wave_sum(acc[k]); if (lane == 0) sm[k][wv] = s; }
     __syncthreads();
     if (threadIdx.x < QD_NDIAG) {
         double r = sm[threadIdx.x][0];
@@ -89,7 +88,7 @@ k_energy_diag_finish(const double* __restrict__ partial, int nrows, double* __re
     for (int q = 0; q < QD_NDIAG; ++q) {
         double a = 0.0;
         for (int k = threadIdx.x; k < nrows; k += QD_BLOCK) a += partial[(size_t)q * nrows + k];
-        a = qd_wave_sum_d(a);
+        a = qd_wave_sum(a);
         __syncthreads();
         if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = a;
         __syncthreads();
@@ -125,12 +124,6 @@ int qd_energy_diag_impl(qd_ctx* c, double* host_out) {
 }
 
 // ------------------------------------------------------------------ wind stress + CFL maxima
-__device__ __forceinline__ double qd_wave_max_d(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { double y = __shfl_down(x, o, 64); x = (y > x) ? y : x; }
-    return x;
-}
-
 __global__ void __launch_bounds__(QD_BLOCK)
 k_stress_max(QdGeom G, const double* __restrict__ ua, const double* __restrict__ va,
              const double* __restrict__ uo, const double* __restrict__ vo, double vcap, double rhoCD, double tau_scale,
@@ -151,7 +144,7 @@ k_stress_max(QdGeom G, const double* __restrict__ ua, const double* __restrict__
         mVa = Va > mVa ? Va : mVa;        // NaN never wins, like np.max on nan_to_num'd data
         mUo = so > mUo ? so : mUo;
     }
-    mVa = qd_wave_max_d(mVa); mUo = qd_wave_max_d(mUo);
+    mVa = qd_wave_max(mVa); mUo = qd_wave_max(mUo);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { sm[0][w] = mVa; sm[1][w] = mUo; }
     __syncthreads();
@@ -222,7 +215,7 @@ k_final_qnet_stress(QdGeom G, QdColP P, QdFqsArgs A) {
         A.icemask[o] = (hi > 0.0) ? 1 : 0;
     }
     double mVa = Va > 0.0 ? Va : 0.0, mUo = so > 0.0 ? so : 0.0;           // NaN never wins (k_stress_max: replaced only by something greater than 0)
-    mVa = qd_wave_max_d(mVa); mUo = qd_wave_max_d(mUo);
+    mVa = qd_wave_max(mVa); mUo = qd_wave_max(mUo);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { sm[0][w] = mVa; sm[1][w] = mUo; }
     __syncthreads();
@@ -240,7 +233,7 @@ k_max2_publish(const double* __restrict__ wgmax, int n, double* host2, unsigned 
     __shared__ double sm[2][16];
     double a = 0.0, b = 0.0;
     for (int k = threadIdx.x; k < n; k += 1024) { const double x = wgmax[k], y = wgmax[n + k]; a = x > a ? x : a; b = y > b ? y : b; }
-    a = qd_wave_max_d(a); b = qd_wave_max_d(b);
+    a = qd_wave_max(a); b = qd_wave_max(b);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { sm[0][w] = a; sm[1][w] = b; }
     __syncthreads();
@@ -267,7 +260,7 @@ k_max2_finish(const double* __restrict__ partial, int n, double* __restrict__ ou
     __shared__ double sm[2][QD_BLOCK / 64];
     double a = 0.0, b = 0.0;
     for (int k = threadIdx.x; k < n; k += QD_BLOCK) { a = partial[k] > a ? partial[k] : a; b = partial[n + k] > b ? partial[n + k] : b; }
-    a = qd_wave_max_d(a); b = qd_wave_max_d(b);
+    a = qd_wave_max(a); b = qd_wave_max(b);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { sm[0][w] = a; sm[1][w] = b; }
     __syncthreads();
@@ -310,12 +303,6 @@ k_ocean_momentum(QdGeom G, QdTabs T, QdOcnP P, const double* __restrict__ eta, c
 }
 
 // ------------------------------------------------------------------ continuity: ocean.py:365-374
-__device__ __forceinline__ double qd_wave_sum_d(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
-
 __global__ void __launch_bounds__(QD_BLOCK)
 k_continuity(QdGeom G, QdTabs T, double a, double dlat, double dlon, double msdtH, const double* __restrict__ uo,
              const double* __restrict__ vo, const uint8_t* __restrict__ land, double* __restrict__ eta,
@@ -334,7 +321,7 @@ k_continuity(QdGeom G, QdTabs T, double a, double dlat, double dlon, double msdt
         eta[o] = e;
         acc += e * (island ? 0.0 : w);          // eta * (w * ocean_mask)
     }
-    acc = qd_wave_sum_d(acc);
+    acc = qd_wave_sum(acc);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) sm[wv] = acc;
     __syncthreads();
@@ -350,7 +337,7 @@ k_eta_mean(const double* __restrict__ partial, int n, double wsum, double* __res
     __shared__ double sm[QD_BLOCK / 64];
     double acc = 0.0;
     for (int k = threadIdx.x; k < n; k += QD_BLOCK) acc += partial[k];
-    acc = qd_wave_sum_d(acc);
+    acc = qd_wave_sum(acc);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) sm[wv] = acc;
     __syncthreads();
@@ -395,7 +382,7 @@ k_cont_sstadv(QdGeom G, QdTabs T, double a, double dlat, double dlon, double msd
         const QdBilin bl = qd_departure(G, i, j, uo[o], vo[o], sub_dt, a, cosl, dlat, dlon);
         Ts_out[o] = (1.0 - alpha) * Ts[o] + alpha * qd_gather(Ts, G, bl);
     }
-    acc = qd_wave_sum_d(acc);
+    acc = qd_wave_sum(acc);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) sm[wv] = acc;
     __syncthreads();
@@ -418,7 +405,7 @@ k_cont_sstadv(QdGeom G, QdTabs T, double a, double dlat, double dlon, double msd
     double a2 = 0.0;
     for (int k = threadIdx.x; k < pcount; k += QD_BLOCK)
         a2 += __hip_atomic_load(&partial[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a2 = qd_wave_sum_d(a2);
+    a2 = qd_wave_sum(a2);
     __syncthreads();
     if (lane == 0) sm[wv] = a2;
     __syncthreads();
@@ -520,7 +507,7 @@ k_sst_outlier_fused(QdGeom G, QdTabs T, double dlat, double dlon, double a, QdHe
         __shared__ double smm[QD_BLOCK / 64];
         double acc = 0.0;
         for (int k = threadIdx.x; k < pcount; k += QD_BLOCK) acc += partial[k];
-        acc = qd_wave_sum_d(acc);
+        acc = qd_wave_sum(acc);
         if ((threadIdx.x & 63) == 0) smm[threadIdx.x >> 6] = acc;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -576,7 +563,7 @@ k_sst_outlier_fused(QdGeom G, QdTabs T, double dlat, double dlon, double a, QdHe
 // ------------------------------------------------------------------ polar ring fills: ocean.py:197-262
 // one workgroup per pole row; fixed-order tree sums (deterministic)
 __device__ __forceinline__ double qd_block_sum_ocn(double x, double* sm) {
-    x = qd_wave_sum_d(x);
+    x = qd_wave_sum(x);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     __syncthreads();
     if (lane == 0) sm[wv] = x;
@@ -696,7 +683,7 @@ k_polar_clamp_inject(QdGeom G, QdTabs T, double* __restrict__ sst, double* __res
             s0 += (-sl_[k]) * u_[k] + nx * v_[k];
             s1 += cl_[k] * u_[k] + ny * v_[k];
         }
-        cnt = qd_wave_sum_d(cnt); sT = qd_wave_sum_d(sT); s0 = qd_wave_sum_d(s0); s1 = qd_wave_sum_d(s1);
+        cnt = qd_wave_sum(cnt); sT = qd_wave_sum(sT); s0 = qd_wave_sum(s0); s1 = qd_wave_sum(s1);
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
         if (lane == 0) { sm[0][wv] = cnt; sm[1][wv] = sT; sm[2][wv] = s0; sm[3][wv] = s1; }
         __syncthreads();

@@ -15,6 +15,7 @@
 #include "qd_wave.h"
 #include "qd_ocntail.h"
 #include "qd_stream.h"
+#include "qd_blockred.h"
 #include <cstdlib>
 #include <cstdio>
 #include <vector>
@@ -81,11 +82,6 @@ __device__ __forceinline__ double qt_div_point(const QdGeom& G, const QdTabs& T,
     return T.inv_acos6[i] * (dp + dq);
 }
 
-__device__ __forceinline__ double qt_wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
 
 // =========================================================================================
 // row-streaming form of the same sub-step tail (default): no LDS, no barrier
@@ -377,7 +373,7 @@ k_ocn_tail_stream(QdGeom G, QdTabs T, QdTailArgs P) {
     }
     double acc = qt_currents_wave(T, P, W);
     QT_STAMP(2);
-    acc = qt_wave_sum(acc);
+    acc = qd_wave_sum(acc);
     if (W.lane == 0) __hip_atomic_store(P.partial + w, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // coherent: the finisher may read it
     if (P.acc) {                                             // eta mean inside this launch: the last workgroup to arrive finishes it
         const bool last = W.lane == 0 && qd_acc_arrive(P.acc, w, gridDim.x, acc);
@@ -715,7 +711,7 @@ k_ocn_tail_fast(QdGeom G, QdTabs T, QdTailArgs P) {
     if (FIX) qt_fix_flush(FX);
     QT_STAMP(2);
     if (FIX) __syncthreads();
-    acc = qt_wave_sum(acc);
+    acc = qd_wave_sum(acc);
     if (W.lane == 0) __hip_atomic_store(P.partial + w, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // coherent: the finisher may read it
     if (P.acc) {                                             // eta mean inside this launch: the last workgroup to arrive finishes it
         const bool last = W.lane == 0 && qd_acc_arrive(P.acc, w, gridDim.x, acc);
@@ -977,7 +973,7 @@ k_ocn_fused(QsOcnArgs A, QdTabs T, QdTailArgs P, QfuArgs F) {
         }
     }
     if (wv != 3) return;
-    acc = qt_wave_sum(acc);
+    acc = qd_wave_sum(acc);
     if (lane == 0) __hip_atomic_store(P.partial + w, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (P.acc) {
         const bool last = lane == 0 && qd_acc_arrive(P.acc, w, gridDim.x, acc);

@@ -18,13 +18,9 @@
 #include "qd_device.h"
 #include "qd_saf.h"
 #include "qd_fluxes.h"
+#include "qd_blockred.h"
 QdColP qd_make_colp(const qd_ctx* c, double dt);   // qd_atmos.hip
 
-__device__ __forceinline__ double qd_wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
 
 // one workgroup per row: P_raw and the two weighted row sums (num = sum Pq w, den = sum P_raw w)
 __global__ void __launch_bounds__(QD_BLOCK)
@@ -53,7 +49,7 @@ k_precip_raw(QdGeom G, QdTabs T, const double* __restrict__ u, const double* __r
         s_num += Pq * w;
         s_den += pr * w;
     }
-    s_num = qd_wsum(s_num); s_den = qd_wsum(s_den);
+    s_num = qd_wave_sum(s_num); s_den = qd_wave_sum(s_den);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) { sm[0][wv] = s_num; sm[1][wv] = s_den; }
     __syncthreads();
@@ -93,7 +89,7 @@ k_precip_scalars(const double* __restrict__ partial, int n, double wsum, double 
     __shared__ double sm[2][QD_BLOCK / 64];
     double a = 0.0, b = 0.0;
     for (int k = threadIdx.x; k < n; k += QD_BLOCK) { a += partial[k]; b += partial[n + k]; }
-    a = qd_wsum(a); b = qd_wsum(b);
+    a = qd_wave_sum(a); b = qd_wave_sum(b);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) { sm[0][wv] = a; sm[1][wv] = b; }
     __syncthreads();
@@ -247,7 +243,7 @@ k_precip_rawsums(const double* __restrict__ partial, int n, double* __restrict__
     __shared__ double sm[2][QD_BLOCK / 64];
     double a = 0.0, b = 0.0;
     for (int k = threadIdx.x; k < n; k += QD_BLOCK) { a += partial[k]; b += partial[n + k]; }
-    a = qd_wsum(a); b = qd_wsum(b);
+    a = qd_wave_sum(a); b = qd_wave_sum(b);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) { sm[0][wv] = a; sm[1][wv] = b; }
     __syncthreads();

@@ -162,9 +162,6 @@ extern "C" int qd_phyto_advect_diffuse(qd_handle c, double dt) {
     if (!c) return -1;
     if (c->phyto.S == 0) return qd_fail(c, "qd_phyto_advect_diffuse: no tracers (qd_phyto_configure first)");
     hipSetDevice(c->desc.device);
-    int rc = qd_phyto_step_impl(c, dt);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_phyto_advect_diffuse: launch", e);
-    return 0;
+    if (int rc = qd_phyto_step_impl(c, dt)) return rc;
+    return qd_launch_check(c, "qd_phyto_advect_diffuse");
 }

@@ -17,6 +17,7 @@
 // the [PhytoDiag] line are finished by one workgroup into a device log the host drains after the span.
 #include "qd_span.h"
 #include "qd_pointwise.h"
+#include "qd_blockred.h"
 #include <algorithm>
 
 struct QdPhytoDaily {
@@ -24,8 +25,7 @@ struct QdPhytoDaily {
     double* tab = nullptr;            // band_tab [8][NB] | species_tab [6][S] | shape [S][NB]
     double* bands = nullptr;          // [NB][cells] alpha_water_bands
     int nb_alloc = 0;
-    double* partial = nullptr;        // [3][nblk]
-    int nblk = 0;
+    QdPartials partial;               // [3][nblk]
     int64_t n_steps = 0;
     QdSpanLane lane;                  // qd_phyto_daily_schedule: 1 per firing step of the next span; the [PhytoDiag] log
 };
@@ -44,21 +44,14 @@ struct QdPDArgs {
 // NumPy calls, and several times cheaper than a general f64 pow
 __device__ __forceinline__ double qd_pd_pow(double x, double p) { return p == 0.5 ? sqrt(x) : pow(x, p); }
 
-__device__ __forceinline__ double qd_pd_wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
-
 template <int NBR>
 __global__ void __launch_bounds__(QD_BLOCK)
 k_phyto_daily(QdPDArgs K) {
-    __shared__ double sm[3][QD_BLOCK / 64];
     const QdGeom& G = K.G;
     const qd_phyto_daily_params& P = K.p;
     const int j = blockIdx.x * QD_BLOCK + threadIdx.x;
     const int i = G.row0 + blockIdx.y;
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+    double d[3] = {0.0, 0.0, 0.0};
     if (j < G.nlon) {
         const size_t o = (size_t)qd_lrow(G, i) * G.nlon + j;
         const int NB = P.n_bands, S = P.n_species;
@@ -162,39 +155,20 @@ k_phyto_daily(QdPDArgs K) {
 
         // 9) the [PhytoDiag] sums: nan_to_num(x) max(cos lat, 0)
         const double w = K.T.warea[i];
-        d0 = qd_nn(Cnow) * w; d1 = qd_nn(kd490) * w; d2 = qd_nn(as) * w;
+        d[0] = qd_nn(Cnow) * w; d[1] = qd_nn(kd490) * w; d[2] = qd_nn(as) * w;
     }
-    d0 = qd_pd_wsum(d0); d1 = qd_pd_wsum(d1); d2 = qd_pd_wsum(d2);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { sm[0][wv] = d0; sm[1][wv] = d1; sm[2][wv] = d2; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double r = sm[threadIdx.x][0];
-        for (int k = 1; k < QD_BLOCK / 64; ++k) r += sm[threadIdx.x][k];
-        const size_t nblk = (size_t)gridDim.x * gridDim.y;
-        K.partial[(size_t)threadIdx.x * nblk + blockIdx.y * gridDim.x + blockIdx.x] = r;
-    }
+    qd_block_partials(d, 3, nullptr, K.partial, (size_t)gridDim.x * gridDim.y, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // one workgroup: the three weighted sums over the blocks in a fixed order, divided by sum(max(cos lat, 0)) + 1e-15
 __global__ void __launch_bounds__(QD_BLOCK)
 k_phyto_daily_finish(const double* __restrict__ partial, int nblk, const double* __restrict__ warea, int nlat, int nlon, double seq,
                      double* __restrict__ rec) {
-    __shared__ double sm[4][QD_BLOCK / 64];
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < 3; ++q)
-        for (int k = threadIdx.x; k < nblk; k += QD_BLOCK) a[q] += partial[(size_t)q * nblk + k];
-    for (int r = threadIdx.x; r < nlat; r += QD_BLOCK) a[3] += warea[r] * (double)nlon;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        a[q] = qd_pd_wsum(a[q]);
-        if (lane == 0) sm[q][wv] = a[q];
-    }
-    __syncthreads();
+    double t[4] = {0.0, 0.0, 0.0, 0.0};
+    qd_planes_strided(partial, nblk, 3, nullptr, t);
+    for (int r = threadIdx.x; r < nlat; r += QD_BLOCK) t[3] += warea[r] * (double)nlon;
+    qd_block_totals(t, nullptr);
     if (threadIdx.x == 0) {
-        double t[4];
-        for (int q = 0; q < 4; ++q) { t[q] = sm[q][0]; for (int k = 1; k < QD_BLOCK / 64; ++k) t[q] += sm[q][k]; }
         const double ws = t[3] + 1e-15;
         rec[0] = seq; rec[1] = t[0] / ws; rec[2] = t[1] / ws; rec[3] = t[2] / ws;
     }
@@ -216,7 +190,7 @@ k_phyto_daily_insolation(QdGeom G, QdTabs T, QdStar A, QdStar B, double theta, d
 // ------------------------------------------------------------------ host side
 static void pd_free(QdPhytoDaily* d) {
     if (!d) return;
-    void* p[] = {d->tab, d->bands, d->partial, d->lane.log};
+    void* p[] = {d->tab, d->bands, d->partial.p, d->lane.log};
     for (void* q : p) if (q) hipFree(q);
     delete d;
 }
@@ -224,12 +198,11 @@ void qd_phyto_daily_release(qd_ctx* c) { pd_free(c->pdaily); c->pdaily = nullptr
 
 bool qd_phyto_daily_couples(const qd_ctx* c) { return c->pdaily && c->pdaily->p.couple && c->pdaily->n_steps > 0; }
 
-static bool pd_whole_globe(const qd_ctx* c) { return c->geo.full && c->desc.world <= 1; }
 static QdStar pd_star(const double* s) { return QdStar{s[0], std::sin(s[1]), std::cos(s[1]), s[2]}; }   // as qd_forcing_impl
 
 extern "C" int qd_phyto_daily_insolation(qd_handle c, const double* st, double* insA, double* insB) {
     if (!c || !st || !insA || !insB) return -1;
-    if (!pd_whole_globe(c)) return qd_fail(c, "qd_phyto_daily_insolation: needs a whole-globe handle");
+    if (!qd_whole_globe(c)) return qd_fail(c, "qd_phyto_daily_insolation: needs a whole-globe handle");
     hipSetDevice(c->desc.device);
     const QdGeom G = qd_segments(c, 0).g[0];
     const dim3 grid((G.nlon + QD_BLOCK - 1) / QD_BLOCK, G.nrows);
@@ -246,7 +219,7 @@ extern "C" int qd_phyto_daily_configure(qd_handle c, const qd_phyto_daily_params
                                         const double* species_tab, const double* shape) {
     if (!c || !p || !band_tab || !species_tab || !shape) return -1;
     if (sz != sizeof(qd_phyto_daily_params)) return qd_fail(c, "qd_phyto_daily_configure: struct size mismatch (ABI)");
-    if (!pd_whole_globe(c))
+    if (!qd_whole_globe(c))
         return qd_fail(c, "qd_phyto_daily_configure: the daily phytoplankton step needs a whole-globe handle (world == 1, n_rows == n_lat); "
                           "latitude bands are not supported");
     const int S = p->n_species, NB = p->n_bands;
@@ -276,12 +249,7 @@ extern "C" int qd_phyto_daily_configure(qd_handle c, const qd_phyto_daily_params
         d->nb_alloc = NB;
         d->n_steps = 0;
     }
-    const int nblk = ((c->geo.nlon + QD_BLOCK - 1) / QD_BLOCK) * c->geo.nrows;
-    if (!d->partial || d->nblk != nblk) {
-        if (d->partial) hipFree(d->partial);
-        QD_HIP(c, hipMalloc(&d->partial, (size_t)3 * nblk * sizeof(double)));
-        d->nblk = nblk;
-    }
+    if (int rc = d->partial.ensure(c, 3, ((c->geo.nlon + QD_BLOCK - 1) / QD_BLOCK) * c->geo.nrows)) return rc;
     d->lane.width = QD_PHYTO_DAILY_LOG_W;
     if (!d->lane.log) QD_HIP(c, hipMalloc(&d->lane.log, d->lane.log_doubles() * sizeof(double)));
     d->p = *p;
@@ -305,12 +273,12 @@ int qd_phyto_daily_step_impl(qd_ctx* c, const double* st, int use_sst) {
     K.C = c->phyto.stack[0]; K.stride = c->phyto.stride;
     K.N = c->f[QD_F_PHYTO_N]; K.Tw = use_sst ? c->f[QD_F_SST] : c->f[QD_F_TS]; K.land = c->land;
     K.kd490 = c->f[QD_F_KD490]; K.walpha = c->f[QD_F_WATER_ALPHA]; K.bands = d->bands; K.plane = c->geo.cells();
-    K.partial = d->partial;
+    K.partial = d->partial.p;
     const dim3 grid((K.G.nlon + QD_BLOCK - 1) / QD_BLOCK, K.G.nrows);
     if (d->p.n_bands <= 16) hipLaunchKernelGGL(k_phyto_daily<16>, grid, dim3(QD_BLOCK), 0, c->stream, K);
     else hipLaunchKernelGGL(k_phyto_daily<32>, grid, dim3(QD_BLOCK), 0, c->stream, K);
     d->n_steps += 1;
-    hipLaunchKernelGGL(k_phyto_daily_finish, dim3(1), dim3(QD_BLOCK), 0, c->stream, d->partial, (int)(grid.x * grid.y), c->tabs.warea,
+    hipLaunchKernelGGL(k_phyto_daily_finish, dim3(1), dim3(QD_BLOCK), 0, c->stream, d->partial.p, (int)(grid.x * grid.y), c->tabs.warea,
                        c->geo.nlat, c->geo.nlon, (double)d->n_steps, d->lane.next());
     for (int k = 0; k < c->phyto.S; ++k) qd_mark(c, {c->phyto.cur[k]}, 0);
     qd_mark(c, {c->f[QD_F_PHYTO_N], c->f[QD_F_KD490], c->f[QD_F_WATER_ALPHA]}, 0);
@@ -319,41 +287,34 @@ int qd_phyto_daily_step_impl(qd_ctx* c, const double* st, int use_sst) {
 
 extern "C" int qd_phyto_daily(qd_handle c, const double* star_row, int use_sst) {
     if (!c || !star_row) return -1;
-    if (!pd_whole_globe(c)) return qd_fail(c, "qd_phyto_daily: the daily phytoplankton step needs a whole-globe handle; latitude bands are not supported");
+    if (!qd_whole_globe(c)) return qd_fail(c, "qd_phyto_daily: the daily phytoplankton step needs a whole-globe handle; latitude bands are not supported");
     if (!c->pdaily) return qd_fail(c, "qd_phyto_daily: qd_phyto_daily_configure has not been called");
     hipSetDevice(c->desc.device);
-    int rc = qd_phyto_daily_step_impl(c, star_row, use_sst ? 1 : 0);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_phyto_daily: launch", e);
-    return 0;
+    if (int rc = qd_phyto_daily_step_impl(c, star_row, use_sst ? 1 : 0)) return rc;
+    return qd_launch_check(c, "qd_phyto_daily");
 }
 
+static QdSpanLane* pd_lane(qd_ctx* c) { return c && c->pdaily ? &c->pdaily->lane : nullptr; }
+static const char* const PD_MISSING = "qd_phyto_daily_configure has not been called";
+
 extern "C" int qd_phyto_daily_schedule(qd_handle c, int n, const int32_t* fire) {
-    if (!c || n < 0 || (n && !fire)) return -1;
-    if (!c->pdaily) return qd_fail(c, "qd_phyto_daily_schedule: qd_phyto_daily_configure has not been called");
-    c->pdaily->lane.set(fire, n);
-    return 0;
+    return qd_lane_schedule(c, pd_lane(c), n, fire, "qd_phyto_daily_schedule", PD_MISSING);
 }
 
 QdSpanLane* qd_phyto_daily_span_begin(qd_ctx* c, int n, int with_phys) {
-    const char* why = nullptr;
-    QdPhytoDaily* d = c->pdaily;
-    if (!pd_whole_globe(c)) why = "qd_step_n: the daily phytoplankton step (bit8) needs a whole-globe handle; latitude bands are not supported";
-    else if (!d) why = "qd_step_n: bit8 set but qd_phyto_daily_configure has not been called";
-    else if (!with_phys) why = "qd_step_n: the daily phytoplankton step (bit8) needs the driver physics (bit1)";
-    else if (!d->lane.scheduled(n)) why = "qd_step_n: bit8 needs a qd_phyto_daily_schedule of exactly n steps before the span";
-    else if (c->phyto.S != d->p.n_species) why = "qd_step_n: the resident tracers changed their species count since qd_phyto_daily_configure";
-    else if (!d->lane.fits()) why = "qd_step_n: the span's daily steps would overflow the diagnostic log (drain it first)";
-    if (why) qd_fail(c, why);
-    return why ? nullptr : &d->lane;
+    static const QdSpanTexts T = {
+        "qd_step_n: the daily phytoplankton step (bit8) needs a whole-globe handle; latitude bands are not supported",
+        "qd_step_n: bit8 set but qd_phyto_daily_configure has not been called",
+        "qd_step_n: bit8 needs a qd_phyto_daily_schedule of exactly n steps before the span",
+        "qd_step_n: the span's daily steps would overflow the diagnostic log (drain it first)"};
+    const bool stale = c->pdaily && c->phyto.S != c->pdaily->p.n_species;
+    return qd_lane_span_begin(c, pd_lane(c), n, T,
+                              with_phys ? nullptr : "qd_step_n: the daily phytoplankton step (bit8) needs the driver physics (bit1)",
+                              stale ? "qd_step_n: the resident tracers changed their species count since qd_phyto_daily_configure" : nullptr);
 }
 
 extern "C" int qd_phyto_daily_log(qd_handle c, double* out, int max, int* n) {
-    if (!c || !n) return -1;
-    QdPhytoDaily* d = c->pdaily;
-    if (!d) return qd_fail(c, "qd_phyto_daily_log: qd_phyto_daily_configure has not been called");
-    return d->lane.drain(c, "qd_phyto_daily_log", out, max, n);
+    return qd_lane_drain(c, pd_lane(c), out, max, n, "qd_phyto_daily_log", PD_MISSING);
 }
 
 bool qd_phyto_daily_bands(const qd_ctx* c, const double** bands, int* n_bands, int64_t* n_steps) {

@@ -12,19 +12,9 @@
 #include "qd_internal.h"
 #include "qd_band.h"
 #include "qd_fluxes.h"
+#include "qd_blockred.h"
 #include <algorithm>
 #include <cstdlib>
-
-__device__ __forceinline__ double qd_wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ double qd_wave_max(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { double y = __shfl_down(x, o, 64); x = (y > x) ? y : x; }
-    return x;
-}
 
 // block-level reduce of (sum | max); result valid in thread 0
 template <int OP>

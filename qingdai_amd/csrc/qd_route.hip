@@ -253,7 +253,7 @@ static const char* qr_check(const qd_route_plan* p, size_t cells) {
 extern "C" int qd_route_configure(qd_handle c, const qd_route_plan* p, size_t plan_bytes) {
     if (!c || !p) return -1;
     if (plan_bytes != sizeof(qd_route_plan)) return qd_fail(c, "qd_route_configure: plan struct size mismatch");
-    if (!c->geo.full || c->desc.world > 1)
+    if (!qd_whole_globe(c))
         return qd_fail(c, "qd_route_configure: river routing needs a whole-globe handle (world == 1, n_rows == n_lat); "
                           "routing across latitude bands is not supported");
     const size_t cells = (size_t)c->geo.nlat * c->geo.nlon;
@@ -346,38 +346,30 @@ extern "C" int qd_route_accumulate(qd_handle c, double dt) {
     if (!c->route) return qd_fail(c, "qd_route_accumulate: no network configured (qd_route_configure first)");
     hipSetDevice(c->desc.device);
     qr_accumulate(c, dt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_route_accumulate: launch", e);
-    return 0;
+    return qd_launch_check(c, "qd_route_accumulate");
 }
 
 extern "C" int qd_route_event(qd_handle c, double event_dt, int with_pe) {
     if (!c) return -1;
     if (!c->route) return qd_fail(c, "qd_route_event: no network configured (qd_route_configure first)");
     hipSetDevice(c->desc.device);
-    int rc = qr_event(c, event_dt, with_pe);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qd_fail(c, "qd_route_event: launch", e);
-    return 0;
+    if (int rc = qr_event(c, event_dt, with_pe)) return rc;
+    return qd_launch_check(c, "qd_route_event");
 }
 
+static QdSpanLane* qr_lane(qd_ctx* c) { return c && c->route ? &c->route->lane : nullptr; }
+
 extern "C" int qd_route_schedule(qd_handle c, int n, const double* event_dt) {
-    if (!c || n < 0 || (n && !event_dt)) return -1;
-    if (!c->route) return qd_fail(c, "qd_route_schedule: no network configured (qd_route_configure first)");
-    c->route->lane.set(event_dt, n);
-    return 0;
+    return qd_lane_schedule(c, qr_lane(c), n, event_dt, "qd_route_schedule", "no network configured (qd_route_configure first)");
 }
 
 QdSpanLane* qd_route_span_begin(qd_ctx* c, int n) {
-    const char* why = nullptr;
-    QdRoute* r = c->route;
-    if (!c->geo.full || c->desc.world > 1) why = "qd_step_n: river routing (bit7) needs a whole-globe handle; routing across latitude bands is not supported";
-    else if (!r) why = "qd_step_n: bit7 set but qd_route_configure has not been called";
-    else if (!r->lane.scheduled(n)) why = "qd_step_n: bit7 needs a qd_route_schedule of exactly n steps before the span";
-    else if (!r->lane.fits()) why = "qd_step_n: the span's routing events would overflow the event log (drain it first)";
-    if (why) qd_fail(c, why);
-    return why ? nullptr : &r->lane;
+    static const QdSpanTexts T = {
+        "qd_step_n: river routing (bit7) needs a whole-globe handle; routing across latitude bands is not supported",
+        "qd_step_n: bit7 set but qd_route_configure has not been called",
+        "qd_step_n: bit7 needs a qd_route_schedule of exactly n steps before the span",
+        "qd_step_n: the span's routing events would overflow the event log (drain it first)"};
+    return qd_lane_span_begin(c, qr_lane(c), n, T);
 }
 
 int qd_route_step_impl(qd_ctx* c, double dt, int s) {
@@ -403,8 +395,5 @@ extern "C" int qd_route_download(qd_handle c, int which, double* host, size_t n)
 }
 
 extern "C" int qd_route_events(qd_handle c, double* out, int max, int* n) {
-    if (!c || !n) return -1;
-    QdRoute* r = c->route;
-    if (!r) return qd_fail(c, "qd_route_events: no network configured");
-    return r->lane.drain(c, "qd_route_events", out, max, n);
+    return qd_lane_drain(c, qr_lane(c), out, max, n, "qd_route_events", "no network configured");
 }

@@ -20,6 +20,7 @@
 // shortcuts (e == 1: x, e == 0.5: sqrt, e == 2: x x), else pow.  f64, contraction off (Makefile), no atomics, vector stores only.
 // exp and pow are the only operations whose rounding may differ from NumPy's.
 #include "qd_internal.h"
+#include "qd_blockred.h"
 #include <algorithm>
 
 #define QD_TC_NB QD_TRUECOLOR_MAX_BANDS
@@ -33,7 +34,7 @@ struct QdTrueColor {
     size_t cells = 0;
     uint8_t* img = nullptr;            // [nlat][nlon][3], row-flipped
     double* rgb = nullptr;             // [nlat][nlon][3], allocated by the first render that wants it
-    double* partial = nullptr; int nblk = 0;   // [4][nblk]
+    QdPartials partial;                // [4][nblk]
     double* out2 = nullptr;            // device {sea_ice_area, mean_h_ice}
     double* pbands = nullptr; int pbands_nb = 0;   // a caller's phytoplankton band stack (qd_truecolor_configure)
     double* flow = nullptr;            // a caller's flow map (qd_truecolor_render)
@@ -54,20 +55,6 @@ struct QdTcArgs {
     QdTcTab eco, ph;
     uint8_t* img; double* rgb; double* partial;
 };
-
-__device__ __forceinline__ double qd_tc_wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
-}
-
-// x ** e for an array x and a Python float e, x in [0, 1] or NaN
-__device__ __forceinline__ double qd_tc_pow(double x, double e) {
-    if (e == 1.0) return x;
-    if (e == 0.5) return sqrt(x);
-    if (e == 2.0) return x * x;
-    return pow(x, e);
-}
 
 // w_rel[b] = I_b / (I_tot + 1e-12) of one cell (run_simulation.py:610-620 over spectral.py:397-426)
 __device__ __forceinline__ void qd_tc_wrel(const QdTcTab& T, int nb, double A, double B, double isr, double* wrel) {
@@ -98,10 +85,9 @@ __device__ __forceinline__ void qd_tc_add(double& acc, int b, double t) {      /
 template <bool WANT64>
 __global__ void __launch_bounds__(QD_BLOCK)
 k_truecolor(QdTcArgs K) {
-    __shared__ double sm[4][QD_BLOCK / 64];
     const qd_truecolor_params& P = K.p;
     const int o = blockIdx.x * QD_BLOCK + threadIdx.x;
-    double a_wm = 0.0, a_w = 0.0, a_hm = 0.0, a_m = 0.0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};                      // w mask, w, h_ice mask, mask
     if (o < K.cells) {
         const int row = o / K.nlon, col = o - row * K.nlon;
         const uint8_t lm = K.land[o];
@@ -117,8 +103,8 @@ k_truecolor(QdTcArgs K) {
         const bool sea_ice = ocean && (ice_frac >= P.ice_frac_thr);
         if (sea_ice) { r = ice_r; g = ice_g; b = ice_b; }
         const double w = K.warea[row];
-        a_w = w;
-        if (sea_ice) { a_wm = w; a_hm = h; a_m = 1.0; }
+        acc[1] = w;
+        if (sea_ice) { acc[0] = w; acc[2] = h; acc[3] = 1.0; }
         // land snow from the cover fraction
         if (P.snow_by_swe) {
             const double C = qd_nn(K.csnow[o]);
@@ -150,7 +136,7 @@ k_truecolor(QdTcArgs K) {
             double vr = qd_clip(Rr, 0.0, 1.0), vg = qd_clip(Rg, 0.0, 1.0), vb = qd_clip(Rb, 0.0, 1.0);
             if (P.veg_gamma > 0.0) {
                 const double e = 1.0 / P.veg_gamma;
-                vr = qd_tc_pow(vr, e); vg = qd_tc_pow(vg, e); vb = qd_tc_pow(vb, e);
+                vr = qd_pow_np(vr, e); vg = qd_pow_np(vg, e); vb = qd_pow_np(vb, e);
             }
             if (P.veg_sat != 1.0) {
                 const double m = ((vr + vg) + vb) / 3.0;
@@ -181,7 +167,7 @@ k_truecolor(QdTcArgs K) {
             double vr = qd_clip(Rr, 0.0, 1.0), vg = qd_clip(Rg, 0.0, 1.0), vb = qd_clip(Rb, 0.0, 1.0);
             if (P.oc_gamma > 0.0) {
                 const double e = 1.0 / P.oc_gamma;
-                vr = qd_tc_pow(vr, e); vg = qd_tc_pow(vg, e); vb = qd_tc_pow(vb, e);
+                vr = qd_pow_np(vr, e); vg = qd_pow_np(vg, e); vb = qd_pow_np(vb, e);
             }
             r = r * (1.0 - P.oc_blend) + vr * P.oc_blend;
             g = g * (1.0 - P.oc_blend) + vg * P.oc_blend;
@@ -222,44 +208,28 @@ k_truecolor(QdTcArgs K) {
         q8[1] = (g == g) ? (uint8_t)(qg > 255.0 ? 255.0 : qg) : (uint8_t)0;
         q8[2] = (b == b) ? (uint8_t)(qb > 255.0 ? 255.0 : qb) : (uint8_t)0;
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    a_wm = qd_tc_wsum(a_wm); a_w = qd_tc_wsum(a_w); a_hm = qd_tc_wsum(a_hm); a_m = qd_tc_wsum(a_m);
-    if (lane == 0) { sm[0][wv] = a_wm; sm[1][wv] = a_w; sm[2][wv] = a_hm; sm[3][wv] = a_m; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double t = sm[threadIdx.x][0];
-        for (int k = 1; k < QD_BLOCK / 64; ++k) t += sm[threadIdx.x][k];
-        K.partial[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = t;
-    }
+    qd_block_partials(acc, 4, nullptr, K.partial, (size_t)gridDim.x, (size_t)blockIdx.x);
 }
 
 __global__ void __launch_bounds__(QD_BLOCK)
 k_truecolor_final(const double* __restrict__ partial, int nblk, double* __restrict__ out2) {
     __shared__ double tot[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;                 // QD_BLOCK / 64 == 4 waves: one per quantity
-    double a = 0.0;
-    for (int k = lane; k < nblk; k += 64) a += partial[(size_t)wv * nblk + k];
-    a = qd_tc_wsum(a);
-    if (lane == 0) tot[wv] = a;
-    __syncthreads();
+    qd_planes_by_wave(partial, nblk, 4, tot);
     if (threadIdx.x == 0) {
         out2[0] = tot[0] / (tot[1] + 1e-15);
         out2[1] = tot[3] > 0.0 ? tot[2] / tot[3] : 0.0;
     }
 }
-static_assert(QD_BLOCK / 64 == 4, "k_truecolor_final maps one wave to each of the four sums");
 
 // ------------------------------------------------------------------ host side
 void qd_truecolor_release(qd_ctx* c) {
     QdTrueColor* d = c->tcol;
     if (!d) return;
-    void* p[] = {d->img, d->rgb, d->partial, d->out2, d->pbands, d->flow, d->lake};
+    void* p[] = {d->img, d->rgb, d->partial.p, d->out2, d->pbands, d->flow, d->lake};
     for (void* q : p) if (q) hipFree(q);
     delete d;
     c->tcol = nullptr;
 }
-
-static bool tc_whole_globe(const qd_ctx* c) { return c->geo.full && c->desc.world <= 1 && c->geo.halo == 0; }
 
 static void tc_fill(double* dst, const double* src, int nb) {
     for (int b = 0; b < QD_TC_NB; ++b) dst[b] = b < nb ? src[b] : 0.0;
@@ -269,7 +239,7 @@ extern "C" int qd_truecolor_configure(qd_handle c, const qd_truecolor_params* p,
                                       const double* phyto_tab, const double* phyto_bands, const uint8_t* lake_mask) {
     if (!c || !p) return -1;
     if (sz != sizeof(qd_truecolor_params)) return qd_fail(c, "qd_truecolor_configure: struct size mismatch (ABI)");
-    if (!tc_whole_globe(c))
+    if (!qd_whole_globe(c))
         return qd_fail(c, "qd_truecolor_configure: the true-colour frame needs a whole-globe handle (world == 1, n_rows == n_lat); "
                           "latitude bands are not supported");
     if (p->nb_eco < 0 || p->nb_eco > QD_TC_NB || p->nb_phyto < 0 || p->nb_phyto > QD_TC_NB)
@@ -286,8 +256,7 @@ extern "C" int qd_truecolor_configure(qd_handle c, const qd_truecolor_params* p,
     const size_t cells = (size_t)c->geo.nlat * c->geo.nlon;
     d->cells = cells;
     if (!d->img) QD_HIP(c, hipMalloc(&d->img, cells * 3));
-    const int nblk = (int)((cells + QD_BLOCK - 1) / QD_BLOCK);
-    if (!d->partial) { QD_HIP(c, hipMalloc(&d->partial, (size_t)4 * nblk * sizeof(double))); d->nblk = nblk; }
+    if (int rc = d->partial.ensure(c, 4, (int)((cells + QD_BLOCK - 1) / QD_BLOCK))) return rc;
     if (!d->out2) QD_HIP(c, hipMalloc(&d->out2, 2 * sizeof(double)));
     d->eco = QdTcTab{}; d->ph = QdTcTab{};
     if (eco_tab && p->nb_eco > 0) {
@@ -318,7 +287,7 @@ extern "C" int qd_truecolor_configure(qd_handle c, const qd_truecolor_params* p,
 
 extern "C" int qd_truecolor_render(qd_handle c, int want_f64, const double* flow, double* out2) {
     if (!c) return -1;
-    if (!tc_whole_globe(c))
+    if (!qd_whole_globe(c))
         return qd_fail(c, "qd_truecolor_render: the true-colour frame needs a whole-globe handle; latitude bands are not supported");
     QdTrueColor* d = c->tcol;
     if (!d || !d->configured) return qd_fail(c, "qd_truecolor_render: qd_truecolor_configure has not been called");
@@ -365,13 +334,13 @@ extern "C" int qd_truecolor_render(qd_handle c, int want_f64, const double* flow
         QD_HIP(c, hipStreamSynchronize(c->stream));
         QD_HIP(c, hipMalloc(&d->rgb, cells * 3 * sizeof(double)));
     }
-    K.img = d->img; K.rgb = want_f64 ? d->rgb : nullptr; K.partial = d->partial;
+    K.img = d->img; K.rgb = want_f64 ? d->rgb : nullptr; K.partial = d->partial.p;
     {
         QdScope sc(c, "truecolor");
-        const dim3 grid(d->nblk), block(QD_BLOCK);
+        const dim3 grid(d->partial.nblk), block(QD_BLOCK);
         if (want_f64) hipLaunchKernelGGL(k_truecolor<true>, grid, block, 0, c->stream, K);
         else hipLaunchKernelGGL(k_truecolor<false>, grid, block, 0, c->stream, K);
-        hipLaunchKernelGGL(k_truecolor_final, dim3(1), block, 0, c->stream, d->partial, d->nblk, d->out2);
+        hipLaunchKernelGGL(k_truecolor_final, dim3(1), block, 0, c->stream, d->partial.p, d->partial.nblk, d->out2);
     }
     QD_HIP(c, hipMemcpyAsync(d->last2, d->out2, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     QD_HIP(c, hipStreamSynchronize(c->stream));
