@@ -325,6 +325,46 @@ int qd_eco_daily_schedule(qd_handle h, int n, const int32_t* fire);   /* the nex
 int qd_eco_daily_log(qd_handle h, double* out, int max, int* n);      /* drains the log: *n records of 4 doubles */
 int qd_eco_daily_state(qd_handle h, int64_t* n_firings);              /* firings since the configure */
 
+/* ---- daily step of the sampled individuals (IndividualPool.step_daily, pygcm/ecology/individuals.py:193-361; driver call
+ * scripts/run_simulation.py:1818-1835), whole-globe handles ----------------------------------------------------------------------
+ * Needs qd_indiv_configure (the pool, per_cell consecutive individuals per sampled cell) and qd_eco_daily_configure (the resident
+ * stack).  One firing, f64 in the reference's operation order, no atomics:
+ *   1 per sampled cell   E, stress days and counts per species in individual order (np.add.at, :219-235), denom, the weights, the
+ *                        stress penalty and the renormalisation (:224-243) into per-cell tables; the seed bank (:316-335)
+ *   2 one workgroup      medE = np.median(denom[denom > 0]) or 1.0 (:252), exact; beta_hint = mean_c max_s W (:359)
+ *   3 per level          the cell loop (:259-306): cells of one level of the host's plan write disjoint grid cells and run in one
+ *                        launch, levels in ascending order -- the sequential loop, bit for bit
+ *   4 whole stack        clip to [0, lai_max], ECO_LAI (:308-310), per-species land sums -> species_weights (population.py:343-359)
+ *                        and the daily lane's normalised germination weights
+ *   6 per individual     E_day = 0, stress relief / decay / +1 capped at 365 (:340-356)
+ * Once configured, every firing of the bit9 lane inside qd_step_n runs this step directly behind the vegetation step, on the
+ * same soil index.  A firing appends {firings so far, beta_hint, n_cells, levels} to a log of its own (QD_SPAN_LOG_CAP records). */
+#define QD_INDIV_DAILY_LOG_W 4
+typedef struct qd_indiv_daily_params {
+    int32_t n_species, n_layers;      /* must be the stack's */
+    int32_t per_cell;                 /* QD_ECO_INDIV_PER_CELL: individuals c * per_cell .. belong to sampled cell c */
+    int32_t seed_couple;              /* QD_ECO_INDIV_SEED_COUPLE == 1 (default 1) */
+    double stress_penalty;            /* QD_ECO_INDIV_STRESS_PENALTY 0.2; <= 0: no penalty and the cell's mean stress is 0 */
+    double lai_grow, lai_decay;       /* QD_ECO_LAI_GROWTH_RATE 0.002, QD_ECO_LAI_DECAY_RATE 0.001 */
+    double recruit_frac;              /* QD_ECO_LAI_RECRUIT_FRAC 0.2 */
+    double stress_decay;              /* QD_ECO_INDIV_STRESS_DECAY 0.5 */
+    double repro_frac, seed_energy;   /* pop.repro_fraction, pop.seed_energy as read (individuals.py:319-320) */
+    double retain, bank_max;          /* QD_ECO_SEED_BANK_RETAIN 0.2, QD_ECO_SEED_BANK_MAX 1000 */
+    double lai_max;                   /* pop.params.lai_max */
+} qd_indiv_daily_params;
+/* species_id [n_indiv]: 0 .. n_species-1.  level [n_cells]: the 1-based level of every sampled cell, level(c) = 1 + max(level of
+ * the earlier cells that write a grid cell c writes); checked here (two cells of a level share no grid cell, a later cell that
+ * shares one has the higher level).  Refused: latitude bands, no qd_indiv_configure / qd_eco_daily_configure, n_species or n_layers
+ * that differ from the stack's, n_cells * per_cell != n_indiv or a cell index that is not i / per_cell.  A later
+ * qd_indiv_configure or qd_eco_daily_configure drops this configuration. */
+int qd_indiv_daily_configure(qd_handle h, const qd_indiv_daily_params* p, size_t sizeof_params, const int32_t* species_id,
+                             const int32_t* level);
+/* one firing now (the class seam).  soil_index as in qd_eco_daily_step: NULL = from the resident W_LAND and GLACIER */
+int qd_indiv_daily_step(qd_handle h, const double* soil_index);
+int qd_indiv_daily_log(qd_handle h, double* out, int max, int* n);    /* drains the log: *n records of 4 doubles */
+int qd_indiv_daily_weights(qd_handle h, double* w, int n_species);    /* species_weights after the last firing */
+int qd_indiv_daily_state(qd_handle h, int64_t* n_firings);            /* firings since the configure; 0 when not configured */
+
 /* ---- diversity diagnostics (pygcm/ecology/diversity.py:8-135; scripts/run_simulation.py:2406-2414), whole-globe handles ------
  * From a [n_species][n_layers][n_lat][n_lon] LAI stack and the ecology's land mask (land == 1), f64 in the reference's operation
  * order: L_s = sum_k max(stack, 0) (plane after plane), the alpha map exp(-sum_s p log(p + 1e-15)) with p = L_s / (L_tot + 1e-15)

@@ -47,6 +47,7 @@ SYMBOLS = [
     "qd_phyto_daily_state", "qd_phyto_daily_insolation",
     "qd_eco_daily_configure", "qd_eco_daily_set_layers", "qd_eco_daily_get_layers", "qd_eco_daily_step", "qd_eco_daily_schedule",
     "qd_eco_daily_log", "qd_eco_daily_state",
+    "qd_indiv_daily_configure", "qd_indiv_daily_step", "qd_indiv_daily_log", "qd_indiv_daily_weights", "qd_indiv_daily_state",
     "qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download",
     "qd_truecolor_configure", "qd_truecolor_render", "qd_truecolor_download",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
@@ -79,6 +80,13 @@ class qd_eco_daily_params(ctypes.Structure):
                                                  "bank_decay")])
 
 
+class qd_indiv_daily_params(ctypes.Structure):
+    """include/qingdai_hip.h: qd_indiv_daily_params"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("n_species", "n_layers", "per_cell", "seed_couple")] +
+                [(n, ctypes.c_double) for n in ("stress_penalty", "lai_grow", "lai_decay", "recruit_frac", "stress_decay", "repro_frac",
+                                                 "seed_energy", "retain", "bank_max", "lai_max")])
+
+
 class qd_truecolor_params(ctypes.Structure):
     """include/qingdai_hip.h: qd_truecolor_params"""
     _fields_ = ([(n, ctypes.c_int32) for n in ("snow_by_swe", "veg", "veg_f_one", "oceancolor", "snow_by_ts", "rivers", "lakes", "nb_eco",
@@ -93,6 +101,7 @@ TRUECOLOR_MAX_BANDS = 16     # QD_TRUECOLOR_MAX_BANDS
 SPAN_LOG_CAP = 4096          # records a span lane's device log holds between two drains (csrc/qd_span.h: QD_SPAN_LOG_CAP is the same number)
 PHYTO_DAILY_LOG_W = 4        # doubles per [PhytoDiag] record
 ECO_DAILY_LOG_W = 4          # doubles per daily vegetation record {firings, LAI_min, LAI_mean, LAI_max}
+INDIV_DAILY_LOG_W = 4        # doubles per record of the individuals' daily step {firings, beta_hint, n_cells, levels}
 ROUTE_LOG_W = 8              # doubles per routing event record (routing.LOG_KEYS)
 
 # qd_step_n flags (include/qingdai_hip.h): bit k switches STEP_BITS[k], named as Device.step_n's keywords
@@ -195,6 +204,11 @@ def load():
     lib.qd_eco_daily_schedule.argtypes = [vp, i32, ip]
     lib.qd_eco_daily_log.argtypes = [vp, dp, i32, ip]
     lib.qd_eco_daily_state.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.qd_indiv_daily_configure.argtypes = [vp, ctypes.POINTER(qd_indiv_daily_params), sz, ip, ip]
+    lib.qd_indiv_daily_step.argtypes = [vp, vp]
+    lib.qd_indiv_daily_log.argtypes = [vp, dp, i32, ip]
+    lib.qd_indiv_daily_weights.argtypes = [vp, dp, i32]
+    lib.qd_indiv_daily_state.argtypes = [vp, ctypes.POINTER(i64)]
     lib.qd_eco_diversity.argtypes = [vp, vp, i32, i32, dp, dp]
     lib.qd_eco_diversity_on.argtypes = [vp, i32, i32, u8p, vp, i32, i32, dp, dp]
     lib.qd_eco_diversity_download.argtypes = [vp, i32, dp, sz]

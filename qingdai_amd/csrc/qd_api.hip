@@ -472,6 +472,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_phyto_release(c);
     qd_route_release(c);
     qd_phyto_daily_release(c);
+    qd_indiv_daily_release(c);
     qd_eco_daily_release(c);
     qd_eco_div_release(c);
     qd_truecolor_release(c);
@@ -689,6 +690,9 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     if (with_pdaily && !(span.lane[QD_LANE_PHYTO_DAILY] = qd_phyto_daily_span_begin(c, n, with_phys))) return -1;
     const int with_edaily = flags & 512;
     if (with_edaily && !(span.lane[QD_LANE_ECO_DAILY] = qd_eco_daily_span_begin(c, n, with_eco))) return -1;
+    // the individuals' daily step (qd_indiv_daily_configure) fires with the daily lane and logs into a lane of its own
+    const bool with_idaily = with_edaily && c->idaily;
+    if (with_idaily && !(span.lane[QD_LANE_INDIV_DAILY] = qd_indiv_daily_span_begin(c, span.lane[QD_LANE_ECO_DAILY]))) return -1;
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -700,7 +704,11 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // writes the LAI stack, ECO_LAI and E_day before this step's canopy test and E_day accumulation; dt > day fires more than once.
         // The hoisted precipitation block of this step (part 1) reads and writes none of these, so it stays hoisted on firing steps
         if (with_edaily)
-            for (int r = (int)span.lane[QD_LANE_ECO_DAILY]->at(s); r > 0; --r) if ((rc = qd_eco_daily_step_impl(c, nullptr))) return rc;
+            for (int r = (int)span.lane[QD_LANE_ECO_DAILY]->at(s); r > 0; --r) {
+                if ((rc = qd_eco_daily_step_impl(c, nullptr))) return rc;
+                // IndividualPool.step_daily directly behind it, on the same soil index (run_simulation.py:1818-1835)
+                if (with_idaily && (rc = qd_indiv_daily_step_impl(c, nullptr))) return rc;
+            }
         // EcologyAdapter.step_subdaily sits between the glacier mask and the base-albedo blend (run_simulation.py:2075-2104):
         // its clock / canopy / alpha part runs before the albedo kernel, its E_day += isr dt rides on this step's forcing launch
         if (with_eco && c->eco.p.albedo_couple) { if ((rc = qd_eco_canopy_impl(c, dt))) return rc; c->eco.eday_dt = c->eco.p.use_lai ? dt : 0.0; }

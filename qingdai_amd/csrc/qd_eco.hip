@@ -363,6 +363,7 @@ extern "C" int qd_indiv_configure(qd_handle c, int n_cells, const int32_t* sampl
     for (int i = 0; i < n_indiv; ++i)
         if (cell_index[i] < 0 || cell_index[i] >= n_cells) return qd_fail(c, "qd_indiv_configure: cell index outside the sample");
     QD_HIP(c, hipStreamSynchronize(c->stream));
+    qd_indiv_daily_release(c);                                  // its species ids belong to the pool configured before
     qd_eco_free(c);
     QdEco& E = c->eco;
     std::vector<double> abt((size_t)nb * n_indiv);              // [n_indiv][nb] -> [nb][n_indiv]

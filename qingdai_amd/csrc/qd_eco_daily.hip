@@ -275,6 +275,10 @@ bool qd_eco_daily_stack(const qd_ctx* c, const double** L, int* n_species, int* 
     return true;
 }
 
+double* qd_eco_daily_share_plane(qd_ctx* c) { return c->edaily ? c->edaily->share : nullptr; }
+double* qd_eco_daily_weights_dev(qd_ctx* c) { return c->edaily ? c->edaily->w : nullptr; }
+double qd_eco_daily_soil_cap(const qd_ctx* c) { return c->edaily ? c->edaily->p.soil_cap : 50.0; }
+
 extern "C" int qd_eco_daily_configure(qd_handle c, const qd_eco_daily_params* p, size_t sz, const int32_t* mode, const double* w) {
     if (!c || !p || !mode || !w) return -1;
     if (sz != sizeof(qd_eco_daily_params)) return qd_fail(c, "qd_eco_daily_configure: struct size mismatch (ABI)");
@@ -286,6 +290,7 @@ extern "C" int qd_eco_daily_configure(qd_handle c, const qd_eco_daily_params* p,
     if (K < 1 || K > QD_ECO_DAILY_MAX_K) return qd_fail(c, "qd_eco_daily_configure: n_layers out of range (1..8)");
     for (int s = 0; s < S; ++s) if (mode[s] != 0 && mode[s] != 1) return qd_fail(c, "qd_eco_daily_configure: species_mode is 0 (diffusion) or 1 (seed)");
     hipSetDevice(c->desc.device);
+    qd_indiv_daily_release(c);                                  // its tables and weights belong to the stack configured before
     QdEcoDaily* d = c->edaily;
     if (!d) d = c->edaily = new QdEcoDaily();
     QD_HIP(c, hipStreamSynchronize(c->stream));

@@ -206,6 +206,7 @@ struct qd_ctx {
     struct QdRoute* route = nullptr; // river routing network, buffer and event log (qd_route.hip), whole-globe handles
     struct QdPhytoDaily* pdaily = nullptr;   // daily phytoplankton step: tables, band stack, schedule, diagnostic log (qd_phyto_daily.hip)
     struct QdEcoDaily* edaily = nullptr;     // daily vegetation step: LAI stack, share plane, schedule, log (qd_eco_daily.hip)
+    struct QdIndivDaily* idaily = nullptr;   // daily step of the individuals: species ids, level plan, per-cell tables, log (qd_indiv_daily.hip)
     struct QdEcoDiv* ediv = nullptr;         // diversity diagnostics: L_s, the two maps, partials, summary (qd_eco_div.hip)
     struct QdTrueColor* tcol = nullptr;      // true-colour frame: parameters, band tables, image, partials (qd_truecolor.hip)
     int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
@@ -479,6 +480,12 @@ struct QdSpanLane* qd_eco_daily_span_begin(qd_ctx* c, int n, int with_eco);     
 int  qd_eco_daily_step_impl(qd_ctx* c, const double* soil_dev);
 void qd_eco_daily_release(qd_ctx* c);
 bool qd_eco_daily_stack(const qd_ctx* c, const double** L, int* n_species, int* n_layers);   // the resident LAI stack, when configured
+double* qd_eco_daily_share_plane(qd_ctx* c);          // [cells] free between two firings (nullptr: not configured)
+double* qd_eco_daily_weights_dev(qd_ctx* c);          // [S] the normalised germination weights on the device
+double qd_eco_daily_soil_cap(const qd_ctx* c);
+struct QdSpanLane* qd_indiv_daily_span_begin(qd_ctx* c, const struct QdSpanLane* daily);      // qd_indiv_daily.hip
+int  qd_indiv_daily_step_impl(qd_ctx* c, const double* soil_dev);
+void qd_indiv_daily_release(qd_ctx* c);
 void qd_eco_div_release(qd_ctx* c);                                              // qd_eco_div.hip
 void qd_truecolor_release(qd_ctx* c);                                            // qd_truecolor.hip
 const double* qd_route_flow(const qd_ctx* c);                                    // qd_route.hip: the resident flow map [cells], or nullptr

@@ -295,6 +295,36 @@ class Device:
         self._chk(self.lib.qd_eco_daily_state(self.h, ctypes.byref(n)), "qd_eco_daily_state")
         return int(n.value)
 
+    # ---- daily step of the individuals (qd_indiv_daily.hip)
+    def indiv_daily_configure(self, params, species_id, level):
+        s, l = _c(species_id, np.int32), _c(level, np.int32)
+        ip = ctypes.POINTER(ctypes.c_int32)
+        self._chk(self.lib.qd_indiv_daily_configure(self.h, ctypes.byref(params), ctypes.sizeof(params), s.ctypes.data_as(ip),
+                                                    l.ctypes.data_as(ip)), "qd_indiv_daily_configure")
+
+    def indiv_daily_step(self, soil_index=None):
+        """One firing now; soil_index None = from the resident W_LAND and GLACIER, as inside a span."""
+        self.flush()
+        a = None if soil_index is None else _c(np.broadcast_to(np.asarray(soil_index, dtype=np.float64), self.shape))
+        self._chk(self.lib.qd_indiv_daily_step(self.h, None if a is None else a.ctypes.data), "qd_indiv_daily_step")
+        for k in ("ECO_LAI", "ECO_SEEDBANK"):
+            self._host.pop(k, None)
+
+    def indiv_daily_log(self):
+        """Drain the individuals' daily records -> [n][4] (firings so far, beta_hint, n_cells, levels)."""
+        return self._drain(self.lib.qd_indiv_daily_log, _lib.INDIV_DAILY_LOG_W, "qd_indiv_daily_log")
+
+    def indiv_daily_weights(self, n_species):
+        out = np.empty(int(n_species), dtype=np.float64)
+        self._chk(self.lib.qd_indiv_daily_weights(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(n_species)),
+                  "qd_indiv_daily_weights")
+        return out
+
+    def indiv_daily_firings(self):
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.qd_indiv_daily_state(self.h, ctypes.byref(n)), "qd_indiv_daily_state")
+        return int(n.value)
+
     # ---- diversity diagnostics (qd_eco_div.hip)
     def eco_diversity(self, w_norm_row, layers=None, n_species=None, n_layers=None, land_mask=None):
         """pygcm/ecology/diversity.py on the device -> {alpha_mean, gamma_eff, beta_whittaker}; the maps stay resident

@@ -32,7 +32,13 @@ Daily vegetation dynamics (QD_ECO_DAILY=1, default 0, with QD_ECO_ENABLE=1 and n
 growth, senescence, layered allocation, per-species spread, seed bank, age -- runs inside the resident loop on the steps the
 reference's day accumulator names (qd_step_n bit9, at the top of the step; qingdai_amd/ecology.py PopulationDaily), spans are no
 longer cut at day boundaries, and each chunk's `[Ecology] daily:` lines are printed after it from the device log (QD_ECO_DIAG=1).
-QD_ECO_MUT_RATE > 0 is refused with it; IndividualPool.step_daily, genes export and ecology.nc stay out.
+QD_ECO_MUT_RATE > 0 is refused with it; genes export and ecology.nc stay out.
+Daily step of the individuals (QD_ECO_INDIV_DAILY=1, default 0; needs QD_ECO_DAILY=1, QD_ECO_ENABLE=1, a population, individuals
+and no daily_hook, else refused at start-up): IndividualPool.step_daily (individuals.py:193-361, run_simulation.py:1818-1835) runs
+on the device directly behind every firing of the daily vegetation step, on the same soil index (qingdai_amd/ecology.py
+IndividualDaily) -- species shares and LAI of the sampled cells, recruits, seed bank, species_weights (which the next day's
+germination, the banded albedo and the true-colour frame then use), the individuals' buffers -- and each chunk's `[EcoIndiv] daily
+applied` lines are printed after it from the device log (QD_ECO_DIAG=1).  At 0 the note that the step is not run stays.
 Diversity diagnostics (QD_ECO_DIVERSITY_ENABLE=1, default 0; QD_ECO_DIVERSITY_EVERY_DAYS, default 10; run_simulation.py:2406-2414,
 pygcm/ecology/diversity.py): on the reference's clock -- the step whose start time t_i satisfies t_i / day >= next fires at its end
 and sets next = t_i / day + every, so the first step always fires -- the alpha map, the local Bray-Curtis map and the Whittaker
@@ -223,8 +229,17 @@ class Simulation:
             if not quiet:
                 print(f"[Ecology] daily step on the device: K={self.eco.pop.K}, Ns={self.eco.pop.Ns}, "
                       f"spread {'on' if self.eco_daily.params.spread else 'off'}")
-                if self.indiv is not None:
-                    print("[Ecology] note: IndividualPool.step_daily is not run by the device daily step.")
+        # QD_ECO_INDIV_DAILY=1: IndividualPool.step_daily behind every firing of that lane
+        self.indiv_daily = None
+        if indiv_daily_enabled(env, eco_daily=self.eco_daily is not None, ecology=eco_on, population=eco_on and self.eco.pop is not None,
+                               individuals=self.indiv is not None, daily_hook=daily_hook is not None):
+            from .ecology import IndividualDaily
+            self.indiv_daily = IndividualDaily(self.indiv, self.eco.pop)
+            if not quiet:
+                print(f"[EcoIndiv] daily step on the device: {self.indiv.n_cells} cells x {self.indiv.per_cell} indiv, "
+                      f"{self.indiv_daily.n_levels} levels")
+        elif self.eco_daily is not None and self.indiv is not None and not quiet:
+            print("[Ecology] note: IndividualPool.step_daily is not run by the device daily step.")
         # diversity diagnostics (run_simulation.py:1425-1429, 1741): the switch, the cadence, the clock's threshold in days
         self.diversity_on, self.diversity_every = False, 10.0
         self.diversity_next_day = 0.0
@@ -489,6 +504,10 @@ class Simulation:
             for rec in self.dev.eco_daily_log():               # the span's firings, oldest first (adapter.py:434-436)
                 if self.eco_diag:
                     print(eco_daily_line(rec))
+            if getattr(self, "indiv_daily", None) is not None:     # the reference's line per firing (individuals.py:358-361)
+                for line in self.indiv_daily.lines():
+                    if self.eco_diag:
+                        print(line)
 
     def enable_routing(self, env=None):
         """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
@@ -566,6 +585,20 @@ def eco_daily_enabled(env):
     if mut > 0.0:
         raise ValueError(f"QD_ECO_DAILY=1 does not support QD_ECO_MUT_RATE > 0 (got {mut:g}): stochastic speciation is host code "
                          "outside the device daily step; unset one of the two")
+    return True
+
+
+def indiv_daily_enabled(env, *, eco_daily, ecology, population, individuals, daily_hook):
+    """QD_ECO_INDIV_DAILY (default 0): 1 runs IndividualPool.step_daily on the device behind every firing of the daily vegetation
+    lane.  It acts on that lane's resident stack, so it is refused without what the lane and the pool need."""
+    if int(env.get("QD_ECO_INDIV_DAILY", "0")) != 1:
+        return False
+    missing = [what for ok, what in ((ecology, "QD_ECO_ENABLE=1"), (population, "a population (QD_ECO_USE_LAI=1)"),
+                                     (individuals, "individuals (QD_ECO_INDIV_ENABLE=1)"), (not daily_hook, "no daily_hook"),
+                                     (eco_daily, "QD_ECO_DAILY=1")) if not ok]
+    if missing:
+        raise ValueError("QD_ECO_INDIV_DAILY=1 needs " + ", ".join(missing) + ": the individuals' daily step runs behind the device "
+                         "daily vegetation step on its resident stack; set what is missing or unset QD_ECO_INDIV_DAILY")
     return True
 
 

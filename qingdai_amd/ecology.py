@@ -15,9 +15,11 @@ population dynamics (PopulationManager.step_daily with its spread, seed bank and
 too: `PopulationDaily` configures it from the reference's environment variables, `PopulationCanopy.step_daily` is its class
 seam, and `Device.step_n(..., eco_daily=...)` fires it inside a span (QD_ECO_DAILY=1 in the driver).  The diversity diagnostics
 (pygcm/ecology/diversity.py) run on the device as well: `PopulationCanopy.diversity()` (qd_eco_diversity) with the clock, the line
-and the file writer the driver uses under QD_ECO_DIVERSITY_ENABLE=1.  Mutation, genes and
-IndividualPool.step_daily are host code outside this package: `Simulation` hands `E_day` to a caller-supplied daily hook and
-takes the new LAI layers back.
+and the file writer the driver uses under QD_ECO_DIVERSITY_ENABLE=1.  IndividualPool.step_daily
+(individuals.py:193-361) runs on the device behind every firing of that daily step: `IndividualDaily` reads its variables, plans
+the levels of the cell loop (`plan_levels`) and configures it, `IndividualPool.step_daily` is its class seam
+(QD_ECO_INDIV_DAILY=1 in the driver).  Mutation and genes are host code outside this package: `Simulation` hands `E_day` to a
+caller-supplied daily hook and takes the new LAI layers back.
 """
 from __future__ import annotations
 
@@ -28,7 +30,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import spectral as sp
-from ._lib import qd_eco_params, qd_eco_daily_params
+from ._lib import qd_eco_params, qd_eco_daily_params, qd_indiv_daily_params
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -92,14 +94,33 @@ class PopulationCanopy:
                 self.LAI_layers_SK[s, k] = float(self.species_weights[s]) * (lai0 / float(self.K))
         self._species_R_leaf = None
         self.daily = None                  # a PopulationDaily once the daily step runs on the device
+        self.indiv_daily = None            # an IndividualDaily once the individuals' daily step runs on the device
         self.push_layers(init=True)
+
+    def _stack_clock(self):
+        """What has changed the resident stack so far: firings of the vegetation step and of the individuals' step."""
+        return (self._dev.eco_daily_firings(), self._dev.indiv_daily_firings())
+
+    # -- species weights: recomputed on the device by every firing of the individuals' daily step (population.py:343-359)
+    @property
+    def species_weights(self):
+        if getattr(self, "indiv_daily", None) is not None:
+            fired = self._dev.indiv_daily_firings()
+            if fired and fired != self._weights_at:
+                self._weights, self._weights_at = self._dev.indiv_daily_weights(self._weights.size), fired
+        return self._weights
+
+    @species_weights.setter
+    def species_weights(self, w):
+        self._weights = w
+        self._weights_at = self._dev.indiv_daily_firings() if getattr(self, "indiv_daily", None) is not None else 0
 
     # -- LAI
     @property
     def LAI_layers_SK(self):
         """[S, K, lat, lon]; with a device daily step the resident stack is the truth and is downloaded."""
         if getattr(self, "daily", None) is not None:
-            fired = self._dev.eco_daily_firings()              # the device's own count: firings of a span or of a direct call alike
+            fired = self._stack_clock()                        # the device's own counts: firings of a span or of a direct call alike
             if fired != self._layers_at:
                 self._layers, self._layers_at = self._dev.eco_daily_get_layers(self.Ns, self.K), fired
         return self._layers
@@ -107,7 +128,7 @@ class PopulationCanopy:
     @LAI_layers_SK.setter
     def LAI_layers_SK(self, layers):
         self._layers = layers
-        self._layers_at = self._dev.eco_daily_firings() if getattr(self, "daily", None) is not None else 0
+        self._layers_at = self._stack_clock() if getattr(self, "daily", None) is not None else 0
 
     def push_layers(self, layers=None, init=False):
         """Hand the (changed) [S, K, lat, lon] stack to the device: what the daily step does once per planet-day."""
@@ -407,6 +428,8 @@ class PopulationDaily:
         pop.LAI_layers_SK = layers
         self.dev.eco_daily_set_layers(layers.reshape((-1,) + self.shape))
         self.dev.upload_now("ECO_GATE", pop.land.astype(float))                         # population.py:171
+        if getattr(pop, "indiv_daily", None) is not None:                               # the device dropped it with the old stack
+            pop.indiv_daily.configure()
 
     def _fired(self, n):
         self.n_firings += int(n)
@@ -431,6 +454,87 @@ class PopulationDaily:
         """Drain the device log -> list of summary() dicts, oldest first."""
         return [{"step": int(r[0]), "LAI_min": float(r[1]), "LAI_mean": float(r[2]), "LAI_max": float(r[3])}
                 for r in self.dev.eco_daily_log()]
+
+
+def spill_targets(j, i, H, W):
+    """The four grid cells the cell loop of IndividualPool.step_daily adds recruits to, in its order (individuals.py:296-299):
+    `zip(jn, in_)` of jn = [max(0, j-1), min(H-1, j+1), j, j] and in_ = [(i-1) % W, (i+1) % W, i, i] -- as written that pairs the
+    row neighbours with the column neighbours: the north-west and south-east cells, then the cell itself twice."""
+    jn = [max(0, j - 1), min(H - 1, j + 1), j, j]
+    in_ = [(i - 1) % W, (i + 1) % W, i, i]
+    return list(zip(jn, in_))
+
+
+def footprint(j, i, H, W):
+    """The set of grid cells a sampled cell reads or writes in the cell loop: itself and its spill targets."""
+    return {(j, i), *spill_targets(j, i, H, W)}
+
+
+def plan_levels(sample_j, sample_i, H, W):
+    """Levels of the cell loop (individuals.py:259-306): level(c) = 1 + max(level of the earlier cells whose footprint meets
+    c's), 1 without one -> int32 [C].  Cells of one level touch disjoint grid cells and may run together; running the levels in
+    ascending order keeps every conflicting pair (read-write and write-write alike: f64 addition does not commute in its
+    rounding) in the order of the sequential loop."""
+    top = {}                                     # grid cell -> the highest level of a cell so far whose footprint holds it
+    levels = np.zeros(len(sample_j), dtype=np.int32)
+    for c, (j, i) in enumerate(zip(np.asarray(sample_j).tolist(), np.asarray(sample_i).tolist())):
+        f = footprint(j, i, H, W)
+        lv = 1 + max(top.get(g, 0) for g in f)
+        for g in f:
+            top[g] = lv
+        levels[c] = lv
+    return levels
+
+
+def indiv_daily_line(n_cells, per_cell, beta_hint):
+    """The reference's diagnostic line (individuals.py:360-361)."""
+    return (f"[EcoIndiv] daily applied to {int(n_cells)} cells \u00d7 {int(per_cell)} indiv; "
+            f"mean max species share per cell ~ {beta_hint:.2f} (lower\u2192more even).")
+
+
+class IndividualDaily:
+    """The device daily step of an IndividualPool (individuals.py:193-361) on the stack of a PopulationDaily: parameters from the
+    reference's variables with its defaults, the species id of every individual, the level plan of the cell loop.  A value that
+    does not parse is an error here (the reference raises inside step_daily and its driver skips the step every day), except
+    in the seed-coupling block, whose `except Exception: pass` switches the coupling off."""
+
+    def __init__(self, pool, pop):
+        if pop is None or getattr(pop, "daily", None) is None:
+            raise ValueError("IndividualDaily needs a population whose daily step runs on the device (PopulationDaily)")
+        self.pool, self.pop, self.dev = pool, pop, pop._dev
+        strict = lambda name, default: float(os.getenv(name, default))
+        couple, repro, seed_energy, retain, bank_max = 0, 0.2, 1.0, 0.2, 1000.0
+        try:                                                                           # individuals.py:315-337
+            couple = 1 if int(os.getenv("QD_ECO_INDIV_SEED_COUPLE", "1")) == 1 else 0
+            repro = float(pop.daily.repro_fraction)
+            seed_energy = _envf_any("QD_ECO_SEED_ENERGY", 1.0)                          # pop.seed_energy (population.py:154-157)
+            retain = float(os.getenv("QD_ECO_SEED_BANK_RETAIN", "0.2"))
+            bank_max = float(os.getenv("QD_ECO_SEED_BANK_MAX", "1000.0"))
+        except Exception:      # noqa: BLE001
+            couple = 0
+        self.params = qd_indiv_daily_params(
+            n_species=pop.Ns, n_layers=pop.K, per_cell=int(pool.per_cell), seed_couple=couple,
+            stress_penalty=strict("QD_ECO_INDIV_STRESS_PENALTY", "0.2"), lai_grow=strict("QD_ECO_LAI_GROWTH_RATE", "0.002"),
+            lai_decay=strict("QD_ECO_LAI_DECAY_RATE", "0.001"), recruit_frac=strict("QD_ECO_LAI_RECRUIT_FRAC", "0.2"),
+            stress_decay=strict("QD_ECO_INDIV_STRESS_DECAY", "0.5"), repro_frac=repro, seed_energy=seed_energy, retain=retain,
+            bank_max=bank_max, lai_max=float(pop.daily.params.lai_max))
+        self.levels = plan_levels(pool.sample_j, pool.sample_i, pool.h, pool.w)
+        self.n_levels = int(self.levels.max()) if self.levels.size else 0
+        self.configure()
+
+    def configure(self):
+        self.dev.indiv_daily_configure(self.params, self.pool.indiv_species_id, self.levels)
+        self.pool.daily = self
+        self.pop.indiv_daily = self
+        self.pop.species_weights = self.pop._weights                                    # the firing count starts again at zero
+
+    def log(self):
+        """Drain the device log -> list of dicts, oldest first."""
+        return [{"step": int(r[0]), "beta_hint": float(r[1]), "n_cells": int(r[2]), "levels": int(r[3])} for r in self.dev.indiv_daily_log()]
+
+    def lines(self, records=None):
+        """The reference's line per firing."""
+        return [indiv_daily_line(r["n_cells"], self.pool.per_cell, r["beta_hint"]) for r in (self.log() if records is None else records)]
 
 
 @dataclass
@@ -596,6 +700,7 @@ class IndividualPool:
         self.soil_cap = float(soil_cap) if soil_cap is not None else _envf("QD_ECO_SOIL_WATER_CAP", 50.0)
         # QD_ECO_F32=1: keep the [N, NB] coefficient table as f32 on the device (BASELINE configs[4] "f32 mixed precision")
         self.f32_storage = (_envi("QD_ECO_F32", 0) == 1) if f32_storage is None else bool(f32_storage)
+        self.daily = None                  # an IndividualDaily once step_daily runs on the device
         self.configure()
 
     def configure(self, **star_kw):
@@ -608,6 +713,28 @@ class IndividualPool:
                                         ci.ctypes.data_as(_ip), Ab.ctypes.data, tol.ctypes.data, self.nb, specA.ctypes.data_as(_dp),
                                         specB.ctypes.data_as(_dp), tray.ctypes.data_as(_dp), self.substeps_per_day,
                                         self.day_seconds, self.soil_cap, 1 if self.f32_storage else 0), "qd_indiv_configure")
+        if self.daily is not None:                                                      # the device dropped it with the old pool
+            self.daily.configure()
+
+    def step_daily(self, eco_adapter, soil_W_land, Ts_map=None, day_length_hours=24.0):
+        """individuals.py:193-361 on the device, with the reference's arguments (Ts_map and day_length_hours are unused there
+        too): soil_W_land None = zeros, a scalar, or a [lat, lon] soil index (another shape falls back to its nanmean)."""
+        pop = getattr(eco_adapter, "pop", None)
+        if pop is None:
+            self.reset()
+            return
+        if self.daily is None:
+            IndividualDaily(self, pop)
+        shape = (self.h, self.w)
+        if soil_W_land is None:
+            soil = np.zeros(shape)
+        elif np.isscalar(soil_W_land):
+            soil = np.full(shape, float(soil_W_land))
+        else:
+            soil = np.asarray(soil_W_land, dtype=float)
+            if soil.shape != shape:
+                soil = np.full(shape, float(np.nanmean(soil)))
+        self._dev.indiv_daily_step(soil)
 
     def try_substep(self, isr_A=None, isr_B=None, eco_adapter=None, soil_W_land=None, dt_seconds=300.0, day_length_seconds=None):
         """individuals.py:142-191 on the resident ISR_A / ISR_B / W_LAND (arrays given here are uploaded first; `soil_W_land`
