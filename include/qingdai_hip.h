@@ -476,6 +476,33 @@ int qd_hydronet_build(qd_handle h, int n_lat, int n_lon, const uint8_t* land_mas
                       int32_t* lake_outlet_index, int lake_outlet_cap, int* n_land, int* n_lakes);
 int qd_hydronet_sweeps(qd_handle h, int* sweeps);   /* pit-fill sweeps the last qd_hydronet_build on this handle ran */
 
+/* ---- periodic budget diagnostics (QD_BUDGET_DIAG), whole-globe handles --------------------------------------------------
+ * The reference driver prints [EnergyDiag], [OceanDiag], [HumidityDiag], [WaterDiag] and [HydroRoutingDiag] on steps i % 200 == 0
+ * (run_simulation.py:2148-2188, 2263-2287, 2349-2398) and its ocean prints [OceanE] on its own step count (pygcm/ocean.py:446-516).
+ * Here they are a span lane without a flag bit: a schedule given before a qd_step_n span turns it on for that span.  On a
+ * scheduled step qd_step_n reduces on the device at the reference's positions in the step and leaves ONE record of
+ * QD_BUDGET_LOG_W doubles; a step that is not scheduled launches nothing extra.  The record holds fixed-order SUMS and extrema
+ * (w = max(cos lat, 0)); dividing by the weight sums and formatting is the host's (qingdai_amd/budget_diag.py):
+ *    0.. 4  [EnergyDiag]   sum w TOA_net, sum w SFC_net, sum w ATM_net (energy.py:515-525), sum and count of the non-NaN T_s
+ *    5..12  [OceanE]       sum w eff_Q, sum w dT ocean, sum w ocean, the same three over the polar ocean, its cell count,
+ *                          1 when an earlier firing had left an SST snapshot (else the dT sums are 0)
+ *   13..16  [OceanDiag]    sum w KE, max speed, eta min, eta max (ocean.py:539-545)
+ *   17..20  [HumidityDiag] sum w of E, P_cond, LH, LH_release
+ *   21..27  [WaterDiag]    sum w of E, precip, runoff, rho_a h_mbl q, rho_i h_ice, W_land, S_snow (hydrology.py:304-321)
+ *   28..30  [HydroRoutingDiag] np.nanmax of the flow map, the last event's ocean inflow (kg/s) and mass closure error (kg)
+ *   32..36  1 when the position ran (energy, ocean energy, ocean, humidity, water)     37  the step's schedule value
+ * Lines that need the ocean step, the hydrology commit or routing run only in spans whose flags bring them. */
+enum { QD_BD_LINE_ENERGY = 1, QD_BD_LINE_OCEAN = 2, QD_BD_LINE_OCEAN_ENERGY = 4, QD_BD_LINE_HUMIDITY = 8, QD_BD_LINE_WATER = 16 };
+#define QD_BUDGET_LOG_W 40
+/* lines: mask of QD_BD_LINE_*; polar_row[n_lat]: 1 where the reference's |lat| >= QD_OCEAN_POLAR_LAT test holds (ocean.py:488-489).
+ * Allocates the log, the row partials and one SST snapshot; forgets an earlier configuration. */
+int qd_budget_diag_configure(qd_handle h, int lines, const uint8_t* polar_row);
+/* the next qd_step_n span: per step 0 = nothing, bit0 = the driver's cadence (run_simulation.py:2150 `i % 200 == 0`), bit1 = the
+ * ocean's (ocean.py:452 `self._step % every == 0`) */
+int qd_budget_diag_schedule(qd_handle h, int n, const int32_t* fire);
+int qd_budget_diag_log(qd_handle h, double* out, int max, int* n);   /* drains the log: *n records of QD_BUDGET_LOG_W doubles */
+int qd_budget_diag_reset(qd_handle h);                                /* log, schedule and the SST snapshot (ocean.py:476-479) forgotten */
+
 /* ---- reductions for diagnostics (energy.py:494-538, ocean.py:535-561) -------------- */
 /* compute_energy_diagnostics (energy.py:494-538) from the resident state, with the flux formulas of the driver's
  * coupling block (run_simulation.py:2199-2239): out[10] = cos-weighted global means of

@@ -50,6 +50,7 @@ SYMBOLS = [
     "qd_indiv_daily_configure", "qd_indiv_daily_step", "qd_indiv_daily_log", "qd_indiv_daily_weights", "qd_indiv_daily_state",
     "qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download",
     "qd_truecolor_configure", "qd_truecolor_render", "qd_truecolor_download",
+    "qd_budget_diag_configure", "qd_budget_diag_schedule", "qd_budget_diag_log", "qd_budget_diag_reset",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
     "qd_hydronet_build", "qd_hydronet_sweeps",
@@ -102,6 +103,7 @@ SPAN_LOG_CAP = 4096          # records a span lane's device log holds between tw
 PHYTO_DAILY_LOG_W = 4        # doubles per [PhytoDiag] record
 ECO_DAILY_LOG_W = 4          # doubles per daily vegetation record {firings, LAI_min, LAI_mean, LAI_max}
 INDIV_DAILY_LOG_W = 4        # doubles per record of the individuals' daily step {firings, beta_hint, n_cells, levels}
+BUDGET_LOG_W = 40           # doubles per budget diagnostics record (QD_BUDGET_LOG_W; budget_diag.REC names the slots)
 ROUTE_LOG_W = 8              # doubles per routing event record (routing.LOG_KEYS)
 
 # qd_step_n flags (include/qingdai_hip.h): bit k switches STEP_BITS[k], named as Device.step_n's keywords
@@ -215,6 +217,10 @@ def load():
     lib.qd_truecolor_configure.argtypes = [vp, ctypes.POINTER(qd_truecolor_params), sz, dp, dp, dp, u8p]
     lib.qd_truecolor_render.argtypes = [vp, i32, dp, dp]
     lib.qd_truecolor_download.argtypes = [vp, i32, vp, sz]
+    lib.qd_budget_diag_configure.argtypes = [vp, i32, u8p]
+    lib.qd_budget_diag_schedule.argtypes = [vp, i32, ip]
+    lib.qd_budget_diag_log.argtypes = [vp, dp, i32, ip]
+    lib.qd_budget_diag_reset.argtypes = [vp]
     lib.qd_comm_unique_id.argtypes = [vp, sz]
     lib.qd_comm_init.argtypes = [vp, vp, sz]
     lib.qd_comm_barrier.argtypes = [vp]

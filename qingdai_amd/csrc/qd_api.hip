@@ -476,6 +476,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_eco_daily_release(c);
     qd_eco_div_release(c);
     qd_truecolor_release(c);
+    qd_budget_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -683,6 +684,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     // back to what a stand-alone qd_* call expects
     struct SpanGuard { qd_ctx* c; QdSpanLane* lane[QD_N_LANES] = {}; bool begun = false; ~SpanGuard() {
         for (QdSpanLane* l : lane) if (l) l->clear_schedule();
+        c->budget_fire = 0.0;
         if (begun) { c->diag_write = 1; c->want_pcond_ahead = 0; c->pcond_ahead = 0; c->defer_final = 0; c->final_pending.on = 0; qd_saf_drop(c); }
     } } span{c};
     if (with_route && !(span.lane[QD_LANE_ROUTE] = qd_route_span_begin(c, n))) return -1;
@@ -693,10 +695,19 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     // the individuals' daily step (qd_indiv_daily_configure) fires with the daily lane and logs into a lane of its own
     const bool with_idaily = with_edaily && c->idaily;
     if (with_idaily && !(span.lane[QD_LANE_INDIV_DAILY] = qd_indiv_daily_span_begin(c, span.lane[QD_LANE_ECO_DAILY]))) return -1;
+    // the budget diagnostics (qd_budget_diag.hip) have no flag bit: a schedule given for this span turns them on
+    const bool with_budget = qd_budget_scheduled(c);
+    if (with_budget && !(span.lane[QD_LANE_BUDGET] = qd_budget_span_begin(c, n))) return -1;
+    const int bd_lines = with_budget ? qd_budget_lines(c) : 0;
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
         int rc;
+        // budget diagnostics: bit0 of the step's value = the driver's cadence (every line but [OceanE]), bit1 = the ocean's own
+        const double bd_fire = with_budget ? span.lane[QD_LANE_BUDGET]->at(s) : 0.0;
+        const bool bd_main = ((int)bd_fire & 1) != 0;
+        const bool bd_water = bd_main && with_hydro && (bd_lines & QD_BD_LINE_WATER);
+        if (bd_fire != 0.0 && (rc = qd_budget_begin_step(c))) return rc;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
         if (with_pdaily && span.lane[QD_LANE_PHYTO_DAILY]->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
@@ -716,7 +727,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         const bool merged = with_phys && c->merge_pointwise;
         const QdForcingCall fc{st, st + 3, st[6]};
         // lazy diagnostics: inside a span only the last step stores what nothing inside a span reads -- unless a reader comes with the flags
-        c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag) ? 1 : 0;
+        c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag || bd_main) ? 1 : 0;
         if (with_phys) {
             const int part = c->precip_done ? 2 : 0;         // the precipitation block may have run inside the previous ocean step
             c->precip_done = 0;
@@ -730,9 +741,17 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (!merged && (rc = qd_forcing_impl(c, st, st + 3, st[6], 1))) return rc;
         // the ocean step follows at once and nothing in between reads the post-final fields: k_final rides on its first launch
         c->defer_final = (with_ocean && c->geo.full && c->merge_final && c->wgmax && !(want_diag && s == 0)) ? 1 : 0;
+        // [EnergyDiag] (run_simulation.py:2150-2185) stands between the albedo and time_step: a launch the driver physics left for
+        // time_step's column kernel goes out now, on its own
+        if (bd_main && (bd_lines & QD_BD_LINE_ENERGY)) {
+            if (c->saf_pending && (rc = qd_saf_flush(c))) return rc;
+            if ((rc = qd_budget_energy(c, bd_fire))) return rc;
+        }
         rc = qd_atmos_step_impl(c, dt, pass_alb ? 1 : 0);
         c->defer_final = 0;
         if (rc) return rc;
+        // [HumidityDiag] (run_simulation.py:2276-2283) reads what time_step left; the ocean step touches none of it
+        if (bd_main && (bd_lines & QD_BD_LINE_HUMIDITY) && (rc = qd_budget_humidity(c, bd_fire))) return rc;
         if (c->saf_pending && (rc = qd_saf_flush(c))) return rc;          // (never: the column block takes or flushes it)
         // bit4: energy-budget means of the FIRST step, taken where the reference driver takes them -- after time_step, on the
         // fluxes of the coupling block (run_simulation.py:2199-2246) -- and kept for qd_energy_diagnostics_last
@@ -740,15 +759,22 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // The precipitation block of step s + 1 (run_simulation.py:1740-1790) reads u, v and P_cond as time_step left them and
         // nothing the ocean step, the tracers, the individuals or the bucket touch, and writes only what the rest of step s + 1's
         // driver physics reads: it is queued inside the ocean step, between the stress kernel and the host's wait for the CFL maxima.
-        // (not on a routing event step: the event reads this step's PRECIP, which the hoisted block would overwrite)
-        if (with_ocean && with_phys && c->geo.full && c->hoist_precip && s + 1 < n && !(with_route && span.lane[QD_LANE_ROUTE]->at(s) != 0.0))
+        // (not on a routing event step: the event reads this step's PRECIP, which the hoisted block would overwrite; [WaterDiag] too)
+        if (with_ocean && with_phys && c->geo.full && c->hoist_precip && s + 1 < n && !(with_route && span.lane[QD_LANE_ROUTE]->at(s) != 0.0) && !bd_water)
             c->before_cfl_wait = [c, dt]() { const int r = qd_driver_physics_impl(c, dt, nullptr, 1); if (!r) c->precip_done = 1; return r; };
-        if (with_ocean) { rc = qd_ocean_step_impl(c, dt, 1, 1, 1); c->before_cfl_wait = nullptr; if (rc) return rc; }
+        if (with_ocean) {
+            c->budget_fire = (((int)bd_fire & 2) && (bd_lines & QD_BD_LINE_OCEAN_ENERGY)) ? bd_fire : 0.0;
+            rc = qd_ocean_step_impl(c, dt, 1, 1, 1);
+            c->before_cfl_wait = nullptr; c->budget_fire = 0.0;
+            if (rc) return rc;
+            if (bd_main && (bd_lines & QD_BD_LINE_OCEAN) && (rc = qd_budget_ocean(c, bd_fire))) return rc;     // run_simulation.py:2264-2267
+        }
         if (with_phyto && (rc = qd_phyto_step_impl(c, dt))) return rc;      // run_simulation.py:2254-2258
         // IndividualPool.try_substep reads this step's isr_A / isr_B and W_land before the bucket update (run_simulation.py:2021-2046)
         if (with_eco && c->eco.n_indiv > 0 && (rc = qd_indiv_substep_impl(c, dt, nullptr))) return rc;
         if (with_hydro && (rc = qd_hydrology_commit_impl(c, dt))) return rc;
         if (with_route && (rc = qd_route_step_impl(c, dt, s))) return rc;           // run_simulation.py:2342-2348
+        if (bd_water && (rc = qd_budget_water(c, bd_fire, with_route ? 1 : 0))) return rc;      // run_simulation.py:2350-2394
     }
     c->diag_write = 1;
     return qd_launch_check(c, "qd_step_n");

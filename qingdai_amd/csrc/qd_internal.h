@@ -209,6 +209,8 @@ struct qd_ctx {
     struct QdIndivDaily* idaily = nullptr;   // daily step of the individuals: species ids, level plan, per-cell tables, log (qd_indiv_daily.hip)
     struct QdEcoDiv* ediv = nullptr;         // diversity diagnostics: L_s, the two maps, partials, summary (qd_eco_div.hip)
     struct QdTrueColor* tcol = nullptr;      // true-colour frame: parameters, band tables, image, partials (qd_truecolor.hip)
+    struct QdBudget* budget = nullptr;       // periodic budget diagnostics: schedule, SST snapshot, row partials, log (qd_budget_diag.hip)
+    double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
     int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
     double* zonal_tw = nullptr;      // [2][nlon] cos / sin(2 pi m / nlon) of the zonal spectral filter
     double* sel_cand = nullptr;      // [2][cells] candidates of the two middle ranks after two radix passes (whole-globe handles)
@@ -488,6 +490,18 @@ int  qd_indiv_daily_step_impl(qd_ctx* c, const double* soil_dev);
 void qd_indiv_daily_release(qd_ctx* c);
 void qd_eco_div_release(qd_ctx* c);                                              // qd_eco_div.hip
 void qd_truecolor_release(qd_ctx* c);                                            // qd_truecolor.hip
+// qd_budget_diag.hip: the lane is on for a span when a schedule has been given; `fire` is the step's schedule value
+void qd_budget_release(qd_ctx* c);
+bool qd_budget_scheduled(const qd_ctx* c);
+int  qd_budget_lines(const qd_ctx* c);
+struct QdSpanLane* qd_budget_span_begin(qd_ctx* c, int n);
+int  qd_budget_begin_step(qd_ctx* c);
+int  qd_budget_energy(qd_ctx* c, double fire);
+int  qd_budget_ocean_energy(qd_ctx* c, double dt, int use_ice_mask);             // called by qd_ocean_step_impl while budget_fire != 0
+int  qd_budget_ocean(qd_ctx* c, double fire);
+int  qd_budget_humidity(qd_ctx* c, double fire);
+int  qd_budget_water(qd_ctx* c, double fire, int with_route);
+const double* qd_route_last_record(const qd_ctx* c);                             // qd_route.hip: the last event's record on the device, or nullptr
 const double* qd_route_flow(const qd_ctx* c);                                    // qd_route.hip: the resident flow map [cells], or nullptr
 bool qd_phyto_daily_bands(const qd_ctx* c, const double** bands, int* n_bands, int64_t* n_steps);   // qd_phyto_daily.hip: the resident band stack, when configured
 bool qd_phyto_daily_couples(const qd_ctx* c);                               // the albedo launches blend WATER_ALPHA into the ocean

@@ -97,7 +97,7 @@ k_energy_diag_finish(const double* __restrict__ partial, int nrows, double* __re
 }
 
 // the driver's coupling block works on its own EnergyParams copy (the one autotune nudges)
-static QdColP qd_make_colp_driver(const qd_ctx* c, double dt) {
+QdColP qd_make_colp_driver(const qd_ctx* c, double dt) {
     QdColP P = qd_make_colp(c, dt);
     if (c->p.qnet_lw_eps0 == c->p.qnet_lw_eps0) { P.lw_eps0 = c->p.qnet_lw_eps0; P.eps_clear = std::min(std::max(c->p.qnet_lw_eps0, 0.0), 1.0); }
     if (c->p.qnet_lw_kc == c->p.qnet_lw_kc) P.lw_kc = c->p.qnet_lw_kc;
@@ -1243,6 +1243,8 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
         }
     }
     if (qd_allreduce_flush(c)) return -1;
+    // [OceanE] (ocean.py:446-516) looks at the SST between the last sub-step's clamps and the polar fill
+    if (c->budget_fire != 0.0 && qd_budget_ocean_energy(c, dt, use_ice_mask)) return -1;
     {
         QdScope sc(c, "ocean_finish");
         if (!band && p.ocean_polar_fix && c->merge_pointwise) {

@@ -38,6 +38,7 @@ struct QdRoute {
     double* partial = nullptr;
     int red_blocks = 0;
     int64_t steps = 0;                    // accumulations since configure / reset
+    const double* last_rec = nullptr;     // the last event's record in the log (a drain leaves it in place)
     QdSpanLane lane;                      // qd_route_schedule: event_dt per step of the next span (0: none); the event log
 };
 
@@ -301,7 +302,7 @@ extern "C" int qd_route_reset(qd_handle c) {
     QD_HIP(c, hipMemsetAsync(r->flow, 0, r->cells * sizeof(double), c->stream));
     if (r->n_lakes) QD_HIP(c, hipMemsetAsync(r->lake_vol, 0, r->n_lakes * sizeof(double), c->stream));
     QD_HIP(c, hipStreamSynchronize(c->stream));
-    r->steps = 0; r->lane.reset();
+    r->steps = 0; r->lane.reset(); r->last_rec = nullptr;
     return 0;
 }
 
@@ -335,9 +336,11 @@ static int qr_event(qd_ctx* c, double event_dt, int with_pe) {
     hipLaunchKernelGGL(k_route_reduce, dim3(r->red_blocks), dim3(QD_ROUTE_BLOCK), 0, c->stream, r->nlon, r->cells,
                        (const int32_t*)r->code, (const uint8_t*)r->cflags, (const double*)r->area_row, (const double*)r->M, r->buf,
                        r->flow, (const double*)c->f[QD_F_PRECIP], (const double*)c->f[QD_F_EFLUX], pe, event_dt, dt_den, r->partial);
+    double* rec = r->lane.next();
     hipLaunchKernelGGL(k_route_final, dim3(1), dim3(QD_ROUTE_BLOCK), 0, c->stream, r->red_blocks, (const double*)r->partial, r->n_lakes,
                        (const int32_t*)r->lake_start, (const int32_t*)r->lake_cells, (const double*)r->lake_frac, (const double*)r->M,
-                       r->lake_vol, pe, event_dt, dt_den, (double)r->steps, r->lane.next());
+                       r->lake_vol, pe, event_dt, dt_den, (double)r->steps, rec);
+    r->last_rec = rec;
     return 0;
 }
 
@@ -379,6 +382,7 @@ int qd_route_step_impl(qd_ctx* c, double dt, int s) {
 }
 
 const double* qd_route_flow(const qd_ctx* c) { return c->route ? c->route->flow : nullptr; }
+const double* qd_route_last_record(const qd_ctx* c) { return c->route ? c->route->last_rec : nullptr; }
 
 extern "C" int qd_route_download(qd_handle c, int which, double* host, size_t n) {
     if (!c || !host) return -1;

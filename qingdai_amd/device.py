@@ -130,7 +130,7 @@ class Device:
         self._chk(self.lib.qd_hydrology_commit(self.h, float(dt)), "qd_hydrology_commit")
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
-               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None):
+               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  `routing`: a RiverRouting on this handle -- bit7, after the
         hydrology commit (which it needs); the host's t_accum schedule names the event steps, and the span's
@@ -138,12 +138,14 @@ class Device:
         this handle -- bit8; its firing clock turns the span's times (t0 + dt * arange(n), or t0 itself when it is the n times) into the schedule, and the span's
         [PhytoDiag] records stay in the device log (phyto_daily_log) until the caller drains them.  `eco_daily`: an
         ecology.PopulationDaily on this handle -- bit9 (needs `ecology`); its day accumulator names the firing steps, and the span's
-        LAI summaries stay in the device log (eco_daily_log) until the caller drains them."""
+        LAI summaries stay in the device log (eco_daily_log) until the caller drains them.  `budget`: a budget_diag.BudgetDiag on
+        this handle -- no flag bit: its schedule (run-local step index, the ocean's step count) turns the lane on for the span, and
+        the records stay in the device log (budget_diag_log) until the caller drains them."""
         self.flush()
         st = np.ascontiguousarray(stars, dtype=np.float64)
         assert st.ndim == 2 and st.shape[1] == 7
         n = int(st.shape[0])
-        lanes = [p for p in (phyto_daily, routing, eco_daily) if p is not None]          # the span's participants (csrc/qd_span.h)
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget) if p is not None]          # the span's participants (csrc/qd_span.h)
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -225,6 +227,25 @@ class Device:
 
     def route_last_event(self):
         return self._route_last
+
+    # ---- periodic budget diagnostics (qd_budget_diag.hip)
+    def budget_diag_configure(self, lines, polar_row):
+        pr = _c(polar_row, np.uint8)
+        if pr.size != self.shape[0]:
+            raise ValueError("budget_diag_configure: polar_row holds one flag per latitude row")
+        self._chk(self.lib.qd_budget_diag_configure(self.h, int(lines), pr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+                  "qd_budget_diag_configure")
+
+    def budget_diag_schedule(self, fire):
+        f = _c(fire, np.int32)
+        self._chk(self.lib.qd_budget_diag_schedule(self.h, int(f.size), f.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "qd_budget_diag_schedule")
+
+    def budget_diag_log(self):
+        """Drain the records -> [n][BUDGET_LOG_W] (budget_diag.REC names the slots), oldest first."""
+        return self._drain(self.lib.qd_budget_diag_log, _lib.BUDGET_LOG_W, "qd_budget_diag_log")
+
+    def budget_diag_reset(self):
+        self._chk(self.lib.qd_budget_diag_reset(self.h), "qd_budget_diag_reset")
 
     # ---- daily phytoplankton step (qd_phyto_daily.hip)
     def phyto_daily_configure(self, params, band_tab, species_tab, shape):

@@ -52,6 +52,12 @@ by its start time t_i / day -- the frame is composed on the device from the resi
 qd_truecolor_*), a chunk ends with the firing step, and each firing writes <QD_OUTPUT_DIR, default output>/true_color_day_*.png
 (n_lat x n_lon pixels, no axes) and prints the reference's [TrueColor] sea-ice line.  This replaces the earlier claim that the
 device driver produces no plots: with the switch on, the true-colour frame is produced; the other panels are not.
+Periodic budget lines (QD_BUDGET_DIAG=1, default 0; run_simulation.py:2148-2188, 2263-2287, 2349-2398, pygcm/ocean.py:446-516): the
+reference's [EnergyDiag], [OceanDiag], [HumidityDiag], [WaterDiag] and [HydroRoutingDiag] on steps with run-local index i % 200 == 0
+and its ocean's [OceanE] on the ocean's own step count % QD_OCEAN_DIAG_EVERY, selected by the reference's QD_ENERGY_DIAG,
+QD_OCEAN_DIAG, QD_OCEAN_ENERGY_DIAG, QD_HUMIDITY_DIAG, QD_WATER_DIAG (all default 1) and QD_OCEAN_POLAR_LAT.  A fourth span lane
+(qingdai_amd/budget_diag.py, qd_budget_diag_*): chunks are NOT cut at firing steps; the device reduces at the reference's positions
+inside the step and each chunk's lines are printed after it, in the reference's order and formats.
 Not carried over (out of the hot path): genes, plankton.json, the other matplotlib panels (plot_state, ocean,
 ecology, plankton, ISR; a note is printed instead; the diversity annotation of the plot panel, run_simulation.py:1025-1052, goes
 with them).
@@ -271,6 +277,7 @@ class Simulation:
             self.phyto_daily = PhytoDaily(self.phyto, H_mld_m=H_phyto, diag=diag, dev=self.dev, day_seconds=2 * np.pi / PLANET_OMEGA)
             if diag:
                 print("[Phyto] Manager initialized.")
+        self.budget = None                                     # enable_budget_diag (QD_BUDGET_DIAG=1)
         # banded initial surface temperature (run_simulation.py:310-328)
         if int(env.get("QD_INIT_BANDED", "0")) == 1:
             T_eq, T_pole = float(env.get("QD_INIT_T_EQ", "295.0")), float(env.get("QD_INIT_T_POLE", "265.0"))
@@ -486,10 +493,15 @@ class Simulation:
         routing = getattr(self, "routing", None)
         daily = self.phyto_daily
         eco_daily = self.eco_daily if self.daily_hook is None else None
+        budget = getattr(self, "budget", None)
+        lanes = {}
+        if budget is not None:
+            budget.routed = routing is not None
+            lanes["budget"] = budget
         try:
             self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
                             with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto_transport,
-                            routing=routing, phyto_daily=daily, t0=times, eco_daily=eco_daily)
+                            routing=routing, phyto_daily=daily, t0=times, eco_daily=eco_daily, **lanes)
         except Exception:
             self._t_origin = origin                            # nothing ran: the clock stays where it was, like the lanes' clocks
             raise
@@ -499,6 +511,8 @@ class Simulation:
             daily.print_diag(self.dev.phyto_daily_log())      # the span's [PhytoDiag] lines, oldest first
         if routing is not None:
             routing.take_events(self.dev.route_events())      # the span's events, oldest first
+        if budget is not None:
+            budget.take(self.dev.budget_diag_log(), float(self.dt))       # the span's budget lines, oldest first
         if eco_daily is not None:
             from .ecology import eco_daily_line
             for rec in self.dev.eco_daily_log():               # the span's firings, oldest first (adapter.py:434-436)
@@ -508,6 +522,15 @@ class Simulation:
                 for line in self.indiv_daily.lines():
                     if self.eco_diag:
                         print(line)
+
+    def enable_budget_diag(self, env=None):
+        """QD_BUDGET_DIAG=1: the reference's periodic budget lines ([EnergyDiag], [OceanE], [OceanDiag], [HumidityDiag],
+        [WaterDiag], [HydroRoutingDiag]) from a device lane (qingdai_amd/budget_diag.py) -> the BudgetDiag or None.  The run-local
+        step index the reference's `i % 200` counts starts where this is called."""
+        from .budget_diag import from_env
+        self.budget = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
+                               routed=getattr(self, "routing", None) is not None)
+        return self.budget
 
     def enable_routing(self, env=None):
         """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
@@ -673,6 +696,7 @@ def main(argv=None):
         elif env.get("QD_ORBIT_EPOCH_DAYS"):
             sim.t = float(env["QD_ORBIT_EPOCH_DAYS"]) * day
     sim.enable_routing(env)
+    sim.enable_budget_diag(env)
     sim.bootstrap_ecology()
     t0 = sim.t
     n_total = len(np.arange(t0, t0 + duration, sim.dt))
