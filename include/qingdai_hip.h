@@ -476,6 +476,41 @@ int qd_hydronet_build(qd_handle h, int n_lat, int n_lon, const uint8_t* land_mas
                       int32_t* lake_outlet_index, int lake_outlet_cap, int* n_land, int* n_lakes);
 int qd_hydronet_sweeps(qd_handle h, int* sweeps);   /* pit-fill sweeps the last qd_hydronet_build on this handle ran */
 
+/* ---- procedural topography (P004, pygcm/topography.py:58-83, 90-276), whole-globe handles ---------------------------------
+ * The elevation recipe of generate_elevation_map and the sea level of create_land_sea_mask_from_elevation on the handle's
+ * stream, all f64.  The random draws stay on the host (NumPy's default_rng stream); the host also makes the Gaussian weights.
+ *
+ * qd_topogen_smooth: gaussian_filter(field, sigma, mode=("nearest", "wrap")) (:164, :194, :245) as two separable passes, axis 0
+ * clamped, then axis 1 periodic.  w_lat [r_lat + 1] and w_lon [r_lon + 1] are the first half of the normalised kernel, centre
+ * last (w[r] is the centre weight; r = int(4 sigma + 0.5), r = 0 is the identity); a radius may exceed its axis.  The sum runs
+ * centre first, then the pairs (F[i-k] + F[i+k]) * w[r-k] from k = r down to 1: bit-identical to scipy's correlate1d.
+ * lds_bytes: the LDS a workgroup may use for a staged row / column strip (0: 64 KiB); a line that does not fit is read from
+ * global memory instead (same sums).
+ *
+ * qd_topogen_build: the whole recipe.  par[QD_TOPOGEN_NPAR] = {sigma_rad, shape_p, 1 - W_VLF, W_VLF, W1, W3, SCALE_M,
+ * target_land_frac}; oct_amp [n_oct] = 2 ** (-H k) as the reference accumulates it; noise [(1 + n_oct)][n_lat][n_lon]: the VLF
+ * field, then the octaves (:162, :193); cont [n_cont][3] = {sin lat0, cos lat0, A} and cont_coslon [n_cont][n_lon] =
+ * cos(lon - lon0) (:42-48); sin_lat, cos_lat, area_w [n_lat] (area_w = max(cos lat, 0), :262-264); radii [2 (n_oct + 2)] =
+ * (r_lat, r_lon) of the VLF filter, the octaves' and the final 0.5-sigma one, and weights: their half kernels one after the
+ * other in that order (lat, then lon, r + 1 entries each).  Every (x - mean) / (std + 1e-8) (:157-170, :195-202, :240) is two
+ * passes (mean, then centred squares) with the block reduction of qd_blockred.h.  The sea level (_weighted_quantile, :58-83) is
+ * a weighted MSB-first radix select over the f64 bit patterns with fixed-point row weights: one of the field's own values.
+ * Outputs: elevation [n_lat][n_lon], land_mask (u8, elevation >= sea level), *sea_level_m.
+ * Refused (nonzero): a band handle, a shape that is not the handle's, n_oct > QD_TOPOGEN_MAX_OCTAVES, n_cont >
+ * QD_TOPOGEN_MAX_CONTINENTS, a radius > QD_TOPOGEN_MAX_RADIUS, non-finite noise, tables, weights or parameters, and an
+ * elevation that comes out non-finite. */
+#define QD_TOPOGEN_NPAR 8
+#define QD_TOPOGEN_MAX_OCTAVES 16
+#define QD_TOPOGEN_MAX_CONTINENTS 64
+#define QD_TOPOGEN_MAX_RADIUS 65536
+int qd_topogen_smooth(qd_handle h, int n_lat, int n_lon, const double* field, const double* w_lat, int r_lat, const double* w_lon,
+                      int r_lon, int lds_bytes, double* out);
+int qd_topogen_build(qd_handle h, int n_lat, int n_lon, const double* par, int n_oct, const double* oct_amp, const double* noise,
+                     int n_cont, const double* cont, const double* cont_coslon, const double* sin_lat, const double* cos_lat,
+                     const double* area_w, const int32_t* radii, const double* weights, double* elevation, uint8_t* land_mask,
+                     double* sea_level_m);
+int qd_topogen_last_ms(qd_handle h, double* ms);   /* event time of the kernels of the last qd_topogen_build on this handle */
+
 /* ---- periodic budget diagnostics (QD_BUDGET_DIAG), whole-globe handles --------------------------------------------------
  * The reference driver prints [EnergyDiag], [OceanDiag], [HumidityDiag], [WaterDiag] and [HydroRoutingDiag] on steps i % 200 == 0
  * (run_simulation.py:2148-2188, 2263-2287, 2349-2398) and its ocean prints [OceanE] on its own step count (pygcm/ocean.py:446-516).

@@ -54,6 +54,7 @@ SYMBOLS = [
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
     "qd_hydronet_build", "qd_hydronet_sweeps",
+    "qd_topogen_smooth", "qd_topogen_build", "qd_topogen_last_ms",
     "qd_copy_ceiling", "qd_timing_enable", "qd_timing_select", "qd_timing_get", "qd_timing_reset",
 ]
 
@@ -261,6 +262,9 @@ def load():
     lib.qd_hydronet_build.argtypes = [vp, i32, i32, u8p, dp, dbl, i32, dp, dp, dp, dbl, dp, ip, ip, u8p, ip, ip, i32,
                                       ip, ip]
     lib.qd_hydronet_sweeps.argtypes = [vp, ip]
+    lib.qd_topogen_smooth.argtypes = [vp, i32, i32, dp, dp, i32, dp, i32, i32, dp]
+    lib.qd_topogen_build.argtypes = [vp, i32, i32, dp, i32, dp, dp, i32, dp, dp, dp, dp, dp, ip, dp, dp, u8p, dp]
+    lib.qd_topogen_last_ms.argtypes = [vp, dp]
     lib.qd_timing_enable.argtypes = [vp, i32]
     lib.qd_timing_select.argtypes = [vp, ctypes.c_char_p]
     lib.qd_timing_get.argtypes = [vp, ctypes.c_char_p, dp, ctypes.POINTER(i64)]

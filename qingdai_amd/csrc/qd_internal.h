@@ -212,6 +212,7 @@ struct qd_ctx {
     struct QdBudget* budget = nullptr;       // periodic budget diagnostics: schedule, SST snapshot, row partials, log (qd_budget_diag.hip)
     double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
     int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
+    double topogen_ms = -1.0;        // device time (events) of the kernels of the last qd_topogen_build on this handle (qd_topogen.hip)
     double* zonal_tw = nullptr;      // [2][nlon] cos / sin(2 pi m / nlon) of the zonal spectral filter
     double* sel_cand = nullptr;      // [2][cells] candidates of the two middle ranks after two radix passes (whole-globe handles)
     unsigned int* sel_ccount = nullptr; // [2] candidate counts

@@ -52,6 +52,11 @@ by its start time t_i / day -- the frame is composed on the device from the resi
 qd_truecolor_*), a chunk ends with the firing step, and each firing writes <QD_OUTPUT_DIR, default output>/true_color_day_*.png
 (n_lat x n_lon pixels, no axes) and prints the reference's [TrueColor] sea-ice line.  This replaces the earlier claim that the
 device driver produces no plots: with the switch on, the true-colour frame is produced; the other panels are not.
+Procedural planet on the device (QD_TOPO_DEVICE=1, default 0): without a QD_TOPO_NC file the land mask comes from
+qingdai_amd/topogen.py (qd_topogen_build) with the reference driver's settings -- seed 42, land fraction 0.29, no overrides, no
+elevation map -- instead of the host recipe of qingdai_amd/topography.py; base properties and the [Topo] line are the same.  The
+device's elevation agrees with the host's to about 1e-11 m, so the two masks can differ only in a cell whose elevation lies that
+close to sea level; the default stays 0 for that reason.
 Periodic budget lines (QD_BUDGET_DIAG=1, default 0; run_simulation.py:2148-2188, 2263-2287, 2349-2398, pygcm/ocean.py:446-516): the
 reference's [EnergyDiag], [OceanDiag], [HumidityDiag], [WaterDiag] and [HydroRoutingDiag] on steps with run-local index i % 200 == 0
 and its ocean's [OceanE] on the ocean's own step count % QD_OCEAN_DIAG_EVERY, selected by the reference's QD_ENERGY_DIAG,
@@ -177,7 +182,12 @@ class Simulation:
             except Exception as e:
                 print(f"[Topo] Failed to load '{topo_nc}': {e}\nFalling back to procedural generation.")
         if not loaded:
-            self.land_mask = topo.create_land_sea_mask(self.grid)
+            if topo_device(env):
+                # QD_TOPO_DEVICE=1: the same recipe on the device (seed 42, 0.29, no overrides; no elevation map either)
+                from . import topogen
+                self.land_mask = topogen.generate(self.grid, seed=42, target_land_frac=0.29, device=device)["land_mask"]
+            else:
+                self.land_mask = topo.create_land_sea_mask(self.grid)
             self.base_albedo, self.friction = topo.generate_base_properties(self.land_mask)
             if not quiet:
                 w = np.cos(np.deg2rad(self.grid.lat_mesh))
@@ -623,6 +633,11 @@ def indiv_daily_enabled(env, *, eco_daily, ecology, population, individuals, dai
         raise ValueError("QD_ECO_INDIV_DAILY=1 needs " + ", ".join(missing) + ": the individuals' daily step runs behind the device "
                          "daily vegetation step on its resident stack; set what is missing or unset QD_ECO_INDIV_DAILY")
     return True
+
+
+def topo_device(env):
+    """QD_TOPO_DEVICE (default 0): 1 builds the procedural planet on the device (qingdai_amd/topogen.py)."""
+    return int(env.get("QD_TOPO_DEVICE", "0")) == 1
 
 
 def hydro_autogen(env):
