@@ -428,6 +428,62 @@ int qd_truecolor_render(qd_handle h, int want_f64, const double* flow, double* o
  * which 1: the f64 rgb [n_lat][n_lon][3] in grid order of a render with want_f64 (n = doubles) */
 int qd_truecolor_download(qd_handle h, int which, void* host, size_t n);
 
+/* ---- 15-panel state frame (scripts/run_simulation.py:330-537, plot_state), whole-globe handles ----------------------------
+ * A frame is a mosaic of 5 rows x 3 columns of tiles in the reference's panel order, each tile n_lat x n_lon pixels (one per cell,
+ * northernmost row on top), with a white gutter of QD_STATEFRAME_GUTTER pixels between the tiles and around the mosaic:
+ * width 3 n_lon + 4 gutters, height 5 n_lat + 6 gutters.  A tile is the reference's contourf sampled at the cell centres: a cell
+ * takes the colour of the band i with levels[i] <= z < levels[i + 1]; the last band is closed above; a non-finite z or a z outside
+ * every band is white; with extend_max a z above the top level takes the colour with the index n_levels - 1.  The fields are f64 in
+ * the reference's operation order (:345-498); panels 7 and 8 fill the speed the reference colours its streamlines with. */
+#define QD_STATEFRAME_PANELS 15
+#define QD_STATEFRAME_MAX_LEVELS 32
+#define QD_STATEFRAME_GUTTER 4
+#define QD_STATEFRAME_SCAN_N 28
+typedef struct qd_stateframe_params {
+    int32_t ps_abs;                   /* QD_PLOT_PS_MODE == "abs" (:373-379) */
+    int32_t ocean;                    /* an ocean exists: panel 4 is SST, panel 8 the current speed; else T_s and h - H (:348, :418-427) */
+    int32_t rivers;                   /* routing exists and QD_PLOT_RIVERS == 1 (:513) */
+    int32_t lakes;                    /* routing exists and its lake mask has a set cell (:525-526) */
+    double p0, rho_a;                 /* the humidity parameters of the model (:368-369) */
+    double H;                         /* the model's mean depth (:425) */
+    double river_min, river_alpha, lake_alpha;   /* QD_RIVER_MIN_KGPS, QD_RIVER_ALPHA, QD_LAKE_ALPHA (:517-527) */
+} qd_stateframe_params;
+typedef struct qd_stateframe_panel {
+    int32_t n_levels;                 /* 2..QD_STATEFRAME_MAX_LEVELS; ignored when constant */
+    int32_t extend_max;               /* contourf(extend="max"), panel 5 (:396) */
+    int32_t constant;                 /* no usable range: the tile stays white apart from its overlays */
+    int32_t coast;                    /* 0 none (panel 10), 1 black, 2 white (panel 12) (:356 ... :500) */
+    double levels[QD_STATEFRAME_MAX_LEVELS];
+    double rgb[QD_STATEFRAME_MAX_LEVELS][3];    /* colour of band i; [n_levels - 1] the extended band */
+} qd_stateframe_panel;
+typedef struct qd_stateframe_table {
+    qd_stateframe_panel panel[QD_STATEFRAME_PANELS];
+    int64_t mark_cell[2];             /* flat cells of the star A (cyan x) and star B (yellow +) marks of panel 10, -1 = none (:444-449) */
+} qd_stateframe_table;
+/* Allocates the u8 mosaic, the vorticity plane and the partials.  lake_mask: host [n_lat][n_lon] uint8 or NULL.  Refused on
+ * latitude bands. */
+int qd_stateframe_configure(qd_handle h, const qd_stateframe_params* p, size_t sizeof_params, const uint8_t* lake_mask);
+/* One launch over the grid plus a one-workgroup finish (replaces the host reductions of :349-350, :433, :444-445 and contourf's
+ * zmin / zmax): writes the vorticity plane (the arithmetic of qd_op_vorticity) and out[QD_STATEFRAME_SCAN_N]:
+ *   [0..2] min, [3..5] max of nan_to_num(T_s - 273.15), T_a - 273.15, nan_to_num(SST - 273.15) -- T_a over its non-NaN cells, with
+ *   [25] = 1 when T_a holds a NaN (np.min then gives NaN and np.nanmin skips the field);
+ *   [6..14] min, [15..23] max over the FINITE values of the panels 3, 7, 8, 9, 10, 12, 13, 14, 15 (+inf / -inf when there is none);
+ *   [24] nanmax |vort| (-inf when every cell is NaN); [26], [27] isr_A, isr_B at their np.argmax cells, which go to mark_cells[2]
+ *   (a NaN beats every number, ties go to the lowest flat index).
+ * min, max and this argmax do not depend on the order of combination: the results are exact and repeatable. */
+int qd_stateframe_scan(qd_handle h, double* out, int64_t* mark_cells);
+/* One launch, one thread per (panel, cell), behind a memset of the mosaic to white (replaces the fifteen contourf calls, the coast
+ * contours and the river / lake / star overlays of :355-530).  Needs a scan on this state (the vorticity plane): a render
+ * after the handle's step counters have moved since the scan is refused.  The table is one constant-memory object per device; the
+ * library serialises the renders of all handles on it.  flow: NULL = the
+ * routing state's flow map; else a host [n_lat][n_lon] map (kg/s).  want_stacks != 0 also keeps the int8 band indices and the f64
+ * fields.  Refuses a panel with more than QD_STATEFRAME_MAX_LEVELS levels.  Reads the state and changes none of it. */
+int qd_stateframe_render(qd_handle h, const qd_stateframe_table* table, size_t sizeof_table, const double* flow, int want_stacks);
+/* which 0: the u8 mosaic [5 n_lat + 24][3 n_lon + 16][3], min(255, floor(x * 255 + 0.5)) (n = bytes); which 1: the int8 band
+ * indices [15][n_lat][n_lon] in grid order, -1 = white (n = bytes); which 2: the f64 fields [15][n_lat][n_lon] (n = doubles);
+ * 1 and 2 only after a render with want_stacks (replaces plt.savefig, :535-536) */
+int qd_stateframe_download(qd_handle h, int which, void* host, size_t n);
+
 /* ---- river routing (P014, pygcm/routing.py), whole-globe handles ----------------------------------
  * The host plans the network once (qingdai_amd/routing.py: build_plan): per cell a target code (>= 0 a live edge to that
  * cell; -1 ocean, -2 void, -3 residual, -4 never processed, -5 - k lake storage k) and the reference's sequential loop cut into

@@ -50,6 +50,7 @@ SYMBOLS = [
     "qd_indiv_daily_configure", "qd_indiv_daily_step", "qd_indiv_daily_log", "qd_indiv_daily_weights", "qd_indiv_daily_state",
     "qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download",
     "qd_truecolor_configure", "qd_truecolor_render", "qd_truecolor_download",
+    "qd_stateframe_configure", "qd_stateframe_scan", "qd_stateframe_render", "qd_stateframe_download",
     "qd_budget_diag_configure", "qd_budget_diag_schedule", "qd_budget_diag_log", "qd_budget_diag_reset",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
@@ -99,6 +100,29 @@ class qd_truecolor_params(ctypes.Structure):
 
 
 TRUECOLOR_MAX_BANDS = 16     # QD_TRUECOLOR_MAX_BANDS
+
+STATEFRAME_PANELS = 15       # QD_STATEFRAME_PANELS
+STATEFRAME_MAX_LEVELS = 32   # QD_STATEFRAME_MAX_LEVELS
+STATEFRAME_GUTTER = 4        # QD_STATEFRAME_GUTTER
+STATEFRAME_SCAN_N = 28       # QD_STATEFRAME_SCAN_N
+
+
+class qd_stateframe_params(ctypes.Structure):
+    """include/qingdai_hip.h: qd_stateframe_params"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("ps_abs", "ocean", "rivers", "lakes")] +
+                [(n, ctypes.c_double) for n in ("p0", "rho_a", "H", "river_min", "river_alpha", "lake_alpha")])
+
+
+class qd_stateframe_panel(ctypes.Structure):
+    """include/qingdai_hip.h: qd_stateframe_panel"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("n_levels", "extend_max", "constant", "coast")] +
+                [("levels", ctypes.c_double * STATEFRAME_MAX_LEVELS), ("rgb", (ctypes.c_double * 3) * STATEFRAME_MAX_LEVELS)])
+
+
+class qd_stateframe_table(ctypes.Structure):
+    """include/qingdai_hip.h: qd_stateframe_table"""
+    _fields_ = [("panel", qd_stateframe_panel * STATEFRAME_PANELS), ("mark_cell", ctypes.c_int64 * 2)]
+
 
 SPAN_LOG_CAP = 4096          # records a span lane's device log holds between two drains (csrc/qd_span.h: QD_SPAN_LOG_CAP is the same number)
 PHYTO_DAILY_LOG_W = 4        # doubles per [PhytoDiag] record
@@ -218,6 +242,10 @@ def load():
     lib.qd_truecolor_configure.argtypes = [vp, ctypes.POINTER(qd_truecolor_params), sz, dp, dp, dp, u8p]
     lib.qd_truecolor_render.argtypes = [vp, i32, dp, dp]
     lib.qd_truecolor_download.argtypes = [vp, i32, vp, sz]
+    lib.qd_stateframe_configure.argtypes = [vp, ctypes.POINTER(qd_stateframe_params), sz, u8p]
+    lib.qd_stateframe_scan.argtypes = [vp, dp, ctypes.POINTER(i64)]
+    lib.qd_stateframe_render.argtypes = [vp, ctypes.POINTER(qd_stateframe_table), sz, dp, i32]
+    lib.qd_stateframe_download.argtypes = [vp, i32, vp, sz]
     lib.qd_budget_diag_configure.argtypes = [vp, i32, u8p]
     lib.qd_budget_diag_schedule.argtypes = [vp, i32, ip]
     lib.qd_budget_diag_log.argtypes = [vp, dp, i32, ip]

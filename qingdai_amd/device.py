@@ -429,6 +429,55 @@ class Device:
         self._chk(self.lib.qd_truecolor_download(self.h, 1, out.ctypes.data, out.size), "qd_truecolor_download")
         return out
 
+    # ---- 15-panel state frame (qd_stateframe.hip)
+    def stateframe_configure(self, params, lake_mask=None):
+        """params: a _lib.qd_stateframe_params; lake_mask [lat, lon] or None."""
+        m = None if lake_mask is None else _c(lake_mask, np.uint8)
+        if m is not None and m.shape != self.shape:
+            raise ValueError(f"stateframe_configure: lake_mask must be {self.shape}, got {m.shape}")
+        self._chk(self.lib.qd_stateframe_configure(self.h, ctypes.byref(params), ctypes.sizeof(params),
+                                                   None if m is None else m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+                  "qd_stateframe_configure")
+
+    def stateframe_scan(self):
+        """The extremes and the two argmax cells the level rules need, from the state as it stands -> (the STATEFRAME_SCAN_N doubles
+        include/qingdai_hip.h names, [cell of star A, cell of star B]).  Also fills the vorticity plane the render reads."""
+        self.flush()
+        out = np.empty(_lib.STATEFRAME_SCAN_N, dtype=np.float64)
+        marks = (ctypes.c_int64 * 2)()
+        self._chk(self.lib.qd_stateframe_scan(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), marks), "qd_stateframe_scan")
+        return out, [int(marks[0]), int(marks[1])]
+
+    def stateframe_render(self, table, flow=None, want_stacks=False):
+        """table: a _lib.qd_stateframe_table.  flow None: the routing state's flow map; else a host [lat, lon] map.  The mosaic stays
+        resident (stateframe_image / stateframe_bands / stateframe_fields)."""
+        self.flush()
+        f = None if flow is None else _c(flow)
+        if f is not None and f.shape != self.shape:
+            raise ValueError(f"stateframe_render: flow must be {self.shape}, got {f.shape}")
+        self._chk(self.lib.qd_stateframe_render(self.h, ctypes.byref(table), ctypes.sizeof(table),
+                                                None if f is None else f.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                1 if want_stacks else 0), "qd_stateframe_render")
+
+    def stateframe_image(self):
+        """The u8 mosaic [5 lat + 6 gutters, 3 lon + 4 gutters, 3] of the last render."""
+        g = _lib.STATEFRAME_GUTTER
+        out = np.empty((5 * self.shape[0] + 6 * g, 3 * self.shape[1] + 4 * g, 3), dtype=np.uint8)
+        self._chk(self.lib.qd_stateframe_download(self.h, 0, out.ctypes.data, out.size), "qd_stateframe_download")
+        return out
+
+    def stateframe_bands(self):
+        """The int8 band indices [15, lat, lon] in grid order of the last render (want_stacks=True); -1 = white."""
+        out = np.empty((_lib.STATEFRAME_PANELS,) + self.shape, dtype=np.int8)
+        self._chk(self.lib.qd_stateframe_download(self.h, 1, out.ctypes.data, out.size), "qd_stateframe_download")
+        return out
+
+    def stateframe_fields(self):
+        """The f64 fields [15, lat, lon] handed to the band search by the last render (want_stacks=True)."""
+        out = np.empty((_lib.STATEFRAME_PANELS,) + self.shape, dtype=np.float64)
+        self._chk(self.lib.qd_stateframe_download(self.h, 2, out.ctypes.data, out.size), "qd_stateframe_download")
+        return out
+
     # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident
     def phyto_configure(self, n_species, K_h, adv_alpha):
         self._chk(self.lib.qd_phyto_configure(self.h, int(n_species), float(K_h), float(adv_alpha)), "qd_phyto_configure")

@@ -50,8 +50,7 @@ True-colour frames (QD_TRUECOLOR=1, default 0; QD_PLOT_EVERY_DAYS, default 10; p
 2426-2429): on the reference's plot clock -- the step with run-local index i % plot_interval_steps == 0 fires at its end, labelled
 by its start time t_i / day -- the frame is composed on the device from the resident state (qingdai_amd/truecolor.py,
 qd_truecolor_*), a chunk ends with the firing step, and each firing writes <QD_OUTPUT_DIR, default output>/true_color_day_*.png
-(n_lat x n_lon pixels, no axes) and prints the reference's [TrueColor] sea-ice line.  This replaces the earlier claim that the
-device driver produces no plots: with the switch on, the true-colour frame is produced; the other panels are not.
+(n_lat x n_lon pixels, no axes) and prints the reference's [TrueColor] sea-ice line.
 Procedural planet on the device (QD_TOPO_DEVICE=1, default 0): without a QD_TOPO_NC file the land mask comes from
 qingdai_amd/topogen.py (qd_topogen_build) with the reference driver's settings -- seed 42, land fraction 0.29, no overrides, no
 elevation map -- instead of the host recipe of qingdai_amd/topography.py; base properties and the [Topo] line are the same.  The
@@ -63,9 +62,15 @@ and its ocean's [OceanE] on the ocean's own step count % QD_OCEAN_DIAG_EVERY, se
 QD_OCEAN_DIAG, QD_OCEAN_ENERGY_DIAG, QD_HUMIDITY_DIAG, QD_WATER_DIAG (all default 1) and QD_OCEAN_POLAR_LAT.  A fourth span lane
 (qingdai_amd/budget_diag.py, qd_budget_diag_*): chunks are NOT cut at firing steps; the device reduces at the reference's positions
 inside the step and each chunk's lines are printed after it, in the reference's order and formats.
-Not carried over (out of the hot path): genes, plankton.json, the other matplotlib panels (plot_state, ocean,
-ecology, plankton, ISR; a note is printed instead; the diversity annotation of the plot panel, run_simulation.py:1025-1052, goes
-with them).
+State frames (QD_STATE_PLOT=1, default 0; the same plot clock; plot_state, run_simulation.py:330-537, 2426-2428): the reference's
+15-panel status figure as a mosaic of 5 x 3 tiles of n_lat x n_lon pixels -- every tile its contourf sampled at the cell centres,
+with the coast, river, lake and star-position overlays, no titles, axes or colourbars -- composed on the device from the resident
+state (qingdai_amd/stateframe.py, qd_stateframe_*).  A chunk ends with the firing step, which writes <QD_OUTPUT_DIR>/state_day_*.png
+and a state_day_*.json with the titles, units, colormaps and levels, before the true-colour frame as in the reference.  At the end
+of a chunk PRECIP, ALBEDO, EFLUX, PCOND and OLR hold the firing step's own values.  QD_PLOT_PS_MODE=abs as in
+the reference.  The streamlines of the panels 7 and 8 are not drawn (their speed field is filled instead).
+Not carried over (out of the hot path): genes, plankton.json, the other matplotlib figures (ocean, ecology,
+plankton, ISR; the diversity annotation of the plot panel, run_simulation.py:1025-1052, goes with them).
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -496,6 +501,43 @@ class Simulation:
             self._truecolor_failed = True
             return None
 
+    # -- 15-panel state frames (run_simulation.py:330-537, 2426-2428)
+    def enable_stateframe(self, env=None):
+        """QD_STATE_PLOT=1: the state-frame renderer on this run's device, configured at once (a latitude-band handle is refused
+        here), and the reference's plot interval -> the StateFrame or None."""
+        env = os.environ if env is None else env
+        self.stateframe = None
+        if int(env.get("QD_STATE_PLOT", "0")) == 1:
+            from .stateframe import StateFrame, plot_interval_steps
+            sf = StateFrame(self, env=env)                     # QD_PLOT_PS_MODE and the river variables from the same mapping
+            sf.configure()
+            self.stateframe = sf
+            self.stateframe_every = plot_interval_steps(env, self.dt)
+            self._stateframe_failed = False
+        return self.stateframe
+
+    def stateframe_due(self, i0, n_max):
+        """As truecolor_due, for the state frame: the same plot clock."""
+        if getattr(self, "stateframe", None) is None or n_max <= 0:
+            return None, None
+        from .stateframe import firing_steps
+        fired = firing_steps(i0, n_max, self.stateframe_every)
+        if not fired:
+            return None, None
+        times, _ = self._span_times(fired[0] + 1, advance=False)
+        return fired[0] + 1, float(times[fired[0]]) / self.day_seconds
+
+    def run_stateframe(self, t_days, output_dir=None):
+        """One firing on the state as it stands (the end of the firing step): state_day_*.png and its .json.  A failure is reported
+        once and never stops the run, like the reference's plotting."""
+        try:
+            return self.stateframe.write_frame(t_days, output_dir)
+        except Exception as e:      # noqa: BLE001
+            if not self._stateframe_failed:
+                print(f"[StatePlot] frame skipped: {e}")
+            self._stateframe_failed = True
+            return None
+
     def _run_chunk(self, n, energy_diag=False):
         origin = self._t_origin
         times, t_next = self._span_times(n)
@@ -645,6 +687,18 @@ def hydro_autogen(env):
     return int(env.get("QD_HYDRO_AUTOGEN", "0")) == 1
 
 
+def plots_line(stateframe, truecolor, sim):
+    """The [Plots] start-up line.  Without the state frame it is one of the two wordings it always had."""
+    if stateframe is None:
+        if truecolor is None:
+            return "[Plots] matplotlib panels are not produced by the device driver (out of the hot path)."
+        return (f"[Plots] only the true-colour frame is produced by the device driver, every {sim.truecolor_every} steps; "
+                "the matplotlib panels are not.")
+    what = "the 15-panel state frame (state_day_*.png + .json, no axes)" + (" and the true-colour frame" if truecolor is not None else "")
+    return (f"[Plots] {what} produced by the device driver, every {sim.stateframe_every} steps; the ocean, plankton, ISR and ecology "
+            "figures are not.")
+
+
 def chunk_until(t, dt, next_autosave_t, remaining, max_chunk=200, fire_in=None):
     """Steps to hand to the device loop in one go: at most `max_chunk`, at most `remaining`, and -- when a periodic autosave is
     pending -- exactly up to the step whose END reaches the threshold (the reference tests `t >= next_autosave_t` at the top of the
@@ -717,11 +771,8 @@ def main(argv=None):
     n_total = len(np.arange(t0, t0 + duration, sim.dt))
     print(f"Grid resolution: {sim.grid.n_lat} lat x {sim.grid.n_lon} lon | dt = {sim.dt} s | "
           f"{duration / day:.1f} planetary days | {n_total} steps")
-    if sim.enable_truecolor(env) is None:
-        print("[Plots] matplotlib panels are not produced by the device driver (out of the hot path).")
-    else:
-        print(f"[Plots] only the true-colour frame is produced by the device driver, every {sim.truecolor_every} steps; "
-              "the matplotlib panels are not.")
+    plots = plots_line(sim.enable_stateframe(env), sim.enable_truecolor(env), sim)
+    print(plots)
 
     autosave_on = int(env.get("QD_AUTOSAVE_ENABLE", "1")) == 1
     restart_out = env.get("QD_RESTART_OUT") or os.path.join("data", "restart_autosave.nc")
@@ -760,12 +811,15 @@ def main(argv=None):
     while done < n_total:
         fire_in, fire_day = sim.diversity_due(min(200, n_total - done))
         frame_in, frame_day = sim.truecolor_due(done, min(200, n_total - done))
+        state_in, state_day = sim.stateframe_due(done, min(200, n_total - done))
         n = chunk_until(sim.t, sim.dt, next_autosave_t if autosave_on else None, n_total - done,
-                        fire_in=min((k for k in (fire_in, frame_in) if k is not None), default=None))
+                        fire_in=min((k for k in (fire_in, frame_in, state_in) if k is not None), default=None))
         sim.run_steps(n)
         done += n
         if fire_in is not None and n == fire_in:               # the chunk ended with the firing step
             sim.run_diversity(fire_day)
+        if state_in is not None and n == state_in:             # plot_state, then plot_true_color (run_simulation.py:2428-2429)
+            sim.run_stateframe(state_day)
         if frame_in is not None and n == frame_in:             # (both cadences may fall on one step: diversity first, as in the reference)
             sim.run_truecolor(frame_day)
         if int(env.get("QD_DYN_DIAG_PRINT", "1")) == 1:
