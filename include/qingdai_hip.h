@@ -603,6 +603,7 @@ int qd_energy_diagnostics(qd_handle h, double out[10]);
  * before the ocean step, i.e. exactly where run_simulation.py:2242-2246 evaluates them for the autotuner */
 int qd_energy_diagnostics_last(qd_handle h, double out[10]);
 enum qd_reduce_op { QD_R_SUM = 0, QD_R_COSWEIGHTED_MEAN = 1, QD_R_MAX = 2, QD_R_MIN = 3, QD_R_MAXABS = 4 };
+/* NaN / inf: SUM and COSWEIGHTED_MEAN add them like any value (IEEE: NaN, or inf - inf = NaN, reaches the result); MAX, MIN and MAXABS compare (v > acc), so a NaN cell is skipped and +-inf counts as a value, from the identity -DBL_MAX (MIN: +DBL_MAX), which is what comes back when nothing beats it (every cell NaN; MAX of all -inf) */
 int qd_reduce(qd_handle h, int field, int op, double* out);
 
 /* ---- multi-GPU: latitude bands, RCCL halo exchange ------------------ */
@@ -670,6 +671,8 @@ int qd_tune_reload(qd_handle h);
 int qd_timing_enable(qd_handle h, int on);           /* 0 off, 1 every kernel group */
 int qd_timing_select(qd_handle h, const char* name); /* time only the groups "name[:stride],..." (implies on); with a stride
                                                        * only every stride-th launch of the group is bracketed */
+/* the operator seam's groups name the form that ran: k_shapiro_stream / k_shapiro_pass, k_gauss_rows1 / 2 / 4, k_gauss_fused, k_gauss_axis,
+ * k_zonal_filter / k_scrub_field (one bracket per call of the form, however many launches it takes) */
 int qd_timing_get(qd_handle h, const char* name, double* mean_ms, int64_t* launches);
 int qd_timing_reset(qd_handle h);
 

@@ -232,6 +232,7 @@ int qd_shapiro_fields(qd_ctx* c, double** fields, int n, int npass, int m_out) {
     if (npass < 1) npass = 1;
     QdFieldList a; a.n = n;
     if (npass <= 3 && c->geo.nlon >= 64 && c->shapiro_stream) {
+        QdScope sc(c, "k_shapiro_stream");
         for (int k = 0; k < n; ++k) { a.in[k] = fields[k]; a.out[k] = qd_scratch(c, k); a.aux[k] = nullptr; a.k4row[k] = nullptr; a.k4s[k] = 0; }
         const int R = qd_shapiro_rows(c), W = 64 - 2 * npass, ntc = (c->geo.nlon + W - 1) / W;
         QD_ROWS(c, m_out, G, {
@@ -244,6 +245,7 @@ int qd_shapiro_fields(qd_ctx* c, double** fields, int n, int npass, int m_out) {
         for (int k = 0; k < n; ++k) { double* t = fields[k]; fields[k] = c->scratch[k]; c->scratch[k] = t; qd_mark(c, {fields[k]}, m_out); }
         return 0;
     }
+    QdScope sc(c, "k_shapiro_pass");
     for (int p = 0; p < npass; ++p) {
         for (int k = 0; k < n; ++k) { a.in[k] = fields[k]; a.out[k] = qd_scratch(c, k); a.aux[k] = nullptr; a.k4row[k] = nullptr; a.k4s[k] = 0; }
         const int m = m_out + (npass - 1 - p);
@@ -601,6 +603,7 @@ int qd_gaussian(qd_ctx* c, const double* in, double* out, double* tmp, double si
     const int r = W.r;
     // axis 0 reaches r rows; axis 1 is row-local.  Both passes run on the output margin.
     if (c->use_fused && out != in && c->geo.nlon > 2 * r && (r == 1 || r == 2 || r == 4)) {
+        QdScope sc(c, r == 1 ? "k_gauss_rows1" : (r == 2 ? "k_gauss_rows2" : "k_gauss_rows4"));
         if (r == 1) qd_launch_gauss_rows<1>(c, in, out, W, mode_wrap, clip01, scale_p, scale_k, m_out);
         else if (r == 2) qd_launch_gauss_rows<2>(c, in, out, W, mode_wrap, clip01, scale_p, scale_k, m_out);
         else qd_launch_gauss_rows<4>(c, in, out, W, mode_wrap, clip01, scale_p, scale_k, m_out);
@@ -608,10 +611,12 @@ int qd_gaussian(qd_ctx* c, const double* in, double* out, double* tmp, double si
         return 0;
     }
     if (c->use_fused && out != in && c->geo.nlon > 2 * r) {
+        QdScope sc(c, "k_gauss_fused");
         QD_ROWS(c, m_out, G, hipLaunchKernelGGL(k_gauss_fused, qd_grid2d(G), dim3(QD_BLOCK), 0, c->stream, G, in, out, W, mode_wrap, clip01, scale_p, scale_k));
         qd_mark(c, {out}, m_out);
         return 0;
     }
+    QdScope sc(c, "k_gauss_axis");
     QD_ROWS(c, m_out, G, hipLaunchKernelGGL(k_gauss_axis, qd_grid2d(G), dim3(QD_BLOCK), 0, c->stream, G, in, tmp, W, 0, mode_wrap));
     QD_ROWS(c, m_out, G, hipLaunchKernelGGL(k_gauss_axis, qd_grid2d(G), dim3(QD_BLOCK), 0, c->stream, G, tmp, out, W, 1, mode_wrap));
     qd_mark(c, {tmp, out}, m_out);
@@ -700,6 +705,7 @@ int qd_zonal_filter_fields(qd_ctx* c, double** fields, int nf, double cutoff, do
     const int n = c->geo.nlon;
     if (!(damp > 0.0) || !(cutoff > 0.0) || n / 2 + 1 <= 1) {
         // the reference still scrubs: nan_to_num(F)
+        QdScope sc(c, "k_scrub_field");
         for (int f = 0; f < nf; ++f)
             QD_ROWS(c, m, G, hipLaunchKernelGGL(k_scrub_field, qd_grid2d(G), dim3(QD_BLOCK), 0, c->stream, G, fields[f]));
         return 0;
@@ -721,6 +727,7 @@ int qd_zonal_filter_fields(qd_ctx* c, double** fields, int nf, double cutoff, do
     if (!once[dv]) { hipFuncSetAttribute((const void*)k_zonal_filter, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); once[dv] = c->desc.device == dv; }
     QdFieldList fl{}; fl.n = nf;
     for (int f = 0; f < nf; ++f) { fl.in[f] = fields[f]; fl.out[f] = fields[f]; }
+    QdScope sc(c, "k_zonal_filter");
     QD_ROWS(c, m, G, hipLaunchKernelGGL(k_zonal_filter, dim3(1, G.nrows, nf), dim3(QD_BLOCK), lds, c->stream, G, fl, c->zonal_tw,
                                         kcut, kN, 1.0 - s));
     qd_mark(c, {fields[0], nf > 1 ? fields[1] : fields[0], nf > 2 ? fields[2] : fields[0]}, m);
