@@ -484,6 +484,67 @@ int qd_stateframe_render(qd_handle h, const qd_stateframe_table* table, size_t s
  * 1 and 2 only after a render with want_stacks (replaces plt.savefig, :535-536) */
 int qd_stateframe_download(qd_handle h, int which, void* host, size_t n);
 
+/* ---- tile renderer of the ecology, plankton and ISR figures (scripts/run_simulation.py:828-1060), whole-globe handles --------
+ * A figure is one row of up to QD_TILES_MAX tiles with the state frame's geometry (one pixel per cell, northernmost row on top,
+ * QD_STATEFRAME_GUTTER white pixels between and around): width n n_lon + (n + 1) gutters, height n_lat + 2 gutters.  A tile is
+ * contourf sampled at the cell centres with the state frame's band, coast and u8 rules.  Every source plane equals the array the
+ * reference hands to contourf bit for bit (no exp, log or pow is involved; stacks are reduced plane after plane, as NumPy does).
+ * Every call reads the state and changes none of it. */
+#define QD_TILES_MAX 8
+#define QD_TILES_MAX_RANKS 4
+typedef enum qd_tile_source {
+    QD_TILE_LAI = 0,                  /* nan_to_num(QD_F_ECO_LAI) (:978) */
+    QD_TILE_ALPHA = 1,                /* nan_to_num(QD_F_ECO_ALPHA) (:989) */
+    QD_TILE_ALPHA_BANDED = 2,         /* nan_to_num(QD_F_ECO_ALPHA_BANDED) (:1000) */
+    QD_TILE_CANOPY_HEIGHT = 3,        /* nan_to_num(canopy_height_map()) (:1009; pygcm/ecology/population.py:296-320, layered branch) */
+    QD_TILE_SPECIES_DENSITY = 4,      /* nan_to_num(species_density_maps()[index]) (:1019; population.py:322-341, layered branch) */
+    QD_TILE_PLANKTON = 5,             /* C_phyto_s[index], NaN where land_mask == 1 (:852-854), the resident tracer stack */
+    QD_TILE_ISR_A = 6,                /* QD_F_ISR_A (:906) */
+    QD_TILE_ISR_B = 7,                /* QD_F_ISR_B (:914) */
+    QD_TILE_HOST_PLANE = 8            /* nan_to_num of the plane of qd_tiles_set_plane: the panel's banded-alpha fallback (:2458-2466) */
+} qd_tile_source;
+typedef struct qd_tile_ref { int32_t source, index; } qd_tile_ref;   /* index: the species of the sources 4 and 5, else 0 */
+typedef struct qd_tile_desc {
+    int32_t source, index;
+    int32_t n_levels;                 /* 2..QD_STATEFRAME_MAX_LEVELS; ignored when constant or unavailable */
+    int32_t extend_max;               /* contourf(extend="max") */
+    int32_t constant;                 /* no usable range (contourf would raise): the tile stays white under its coast */
+    int32_t unavailable;              /* the reference's "... not available" placeholder: white under its coast, the source is not read */
+    int32_t coast;                    /* 0 none, 1 black, 2 white */
+    int32_t mark_kind;                /* 0 none, 1 a cyan x (:928), 2 a yellow + (:929), at mark_cell */
+    int64_t mark_cell;                /* flat cell, -1 = none */
+    double levels[QD_STATEFRAME_MAX_LEVELS];
+    double rgb[QD_STATEFRAME_MAX_LEVELS][3];
+} qd_tile_desc;
+/* height_scale: QD_ECO_HEIGHT_SCALE_M (population.py:302).  layers: NULL = the stack sources read the resident stack of
+ * qd_eco_daily_configure; else a host [n_species][n_layers][n_lat][n_lon] stack, uploaded to a scratch buffer here (the convention
+ * of qd_eco_diversity).  Allocates the select state.  Refused on latitude bands. */
+int qd_tiles_configure(qd_handle h, double height_scale, const double* layers, int n_species, int n_layers);
+/* plane: host [n_lat][n_lon], kept for QD_TILE_HOST_PLANE until the next qd_tiles_configure.  The reference computes its panel's
+ * banded-alpha fallback into a local (:2464); this is the way to draw such a map without writing it into the resident state. */
+int qd_tiles_set_plane(qd_handle h, const double* plane);
+/* out3: is there an LAI map (eco.pop.LAI), a scalar alpha map (last_alpha_ecology_map, :1851) and a banded one
+ * (last_alpha_banded, :1844) on the device? */
+int qd_tiles_available(qd_handle h, int32_t* out3);
+/* One launch over the grid plus a one-workgroup finish, for n <= QD_TILES_MAX planes (replaces contourf's zmin / zmax, np.max of
+ * :903 and np.argmax of :924-925): out[k][4] = {min, max over the FINITE values (+inf / -inf when there is none), 1 when the plane
+ * holds a NaN, the value at the np.argmax cell}, argmax_cell[k] that cell (a NaN beats every number, ties go to the lowest flat
+ * index).  Total-order selections: exact, whatever the launch shape. */
+int qd_tiles_scan(qd_handle h, const qd_tile_ref* refs, int n, double* out, int64_t* argmax_cell);
+/* Exact order statistics of one plane (replaces the sort inside np.nanpercentile, :862): *count = the number of non-NaN cells;
+ * values[k] = the ranks[k]-th smallest of them (0-based; +inf is a value, as in np.sort; either zero may stand for a zero), NaN for
+ * a rank that is not below *count -- every rank of an empty plane.  A radix select on the order-preserving 64-bit key, 8 bits a
+ * pass, all n_ranks <= QD_TILES_MAX_RANKS ranks narrowed in the same 8 passes. */
+int qd_tiles_order_stats(qd_handle h, int source, int index, const int64_t* ranks, int n_ranks, double* values, int64_t* count);
+/* One launch, one thread per (tile, cell), behind a memset of the mosaic to white (replaces the contourf and coast-contour calls of
+ * :871-873, :906-929, :978-1021).  want_stacks != 0 also keeps the int8 band indices and the f64 planes.  Refuses n > QD_TILES_MAX,
+ * more than QD_STATEFRAME_MAX_LEVELS levels, a species out of range and a stack source without a stack. */
+int qd_tiles_render(qd_handle h, const qd_tile_desc* tiles, size_t sizeof_tile, int n, int want_stacks);
+/* which 0: the u8 mosaic [n_lat + 8][n n_lon + 4 (n + 1)][3] (n = bytes); which 1: the int8 band indices [n][n_lat][n_lon], -1 =
+ * white (n = bytes); which 2: the f64 planes [n][n_lat][n_lon], NaN for an unavailable tile (n = doubles); 1 and 2 only after a
+ * render with want_stacks (replaces plt.savefig, :880, :950, :1059) */
+int qd_tiles_download(qd_handle h, int which, void* host, size_t n);
+
 /* ---- river routing (P014, pygcm/routing.py), whole-globe handles ----------------------------------
  * The host plans the network once (qingdai_amd/routing.py: build_plan): per cell a target code (>= 0 a live edge to that
  * cell; -1 ocean, -2 void, -3 residual, -4 never processed, -5 - k lake storage k) and the reference's sequential loop cut into

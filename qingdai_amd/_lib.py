@@ -51,6 +51,7 @@ SYMBOLS = [
     "qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download",
     "qd_truecolor_configure", "qd_truecolor_render", "qd_truecolor_download",
     "qd_stateframe_configure", "qd_stateframe_scan", "qd_stateframe_render", "qd_stateframe_download",
+    "qd_tiles_configure", "qd_tiles_set_plane", "qd_tiles_available", "qd_tiles_scan", "qd_tiles_order_stats", "qd_tiles_render", "qd_tiles_download",
     "qd_budget_diag_configure", "qd_budget_diag_schedule", "qd_budget_diag_log", "qd_budget_diag_reset",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
@@ -122,6 +123,25 @@ class qd_stateframe_panel(ctypes.Structure):
 class qd_stateframe_table(ctypes.Structure):
     """include/qingdai_hip.h: qd_stateframe_table"""
     _fields_ = [("panel", qd_stateframe_panel * STATEFRAME_PANELS), ("mark_cell", ctypes.c_int64 * 2)]
+
+
+TILES_MAX = 8                # QD_TILES_MAX
+TILES_MAX_RANKS = 4          # QD_TILES_MAX_RANKS
+# enum qd_tile_source
+TILE_SOURCES = ("LAI", "ALPHA", "ALPHA_BANDED", "CANOPY_HEIGHT", "SPECIES_DENSITY", "PLANKTON", "ISR_A", "ISR_B", "HOST_PLANE")
+TILE = {n: i for i, n in enumerate(TILE_SOURCES)}
+
+
+class qd_tile_ref(ctypes.Structure):
+    """include/qingdai_hip.h: qd_tile_ref"""
+    _fields_ = [("source", ctypes.c_int32), ("index", ctypes.c_int32)]
+
+
+class qd_tile_desc(ctypes.Structure):
+    """include/qingdai_hip.h: qd_tile_desc"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("source", "index", "n_levels", "extend_max", "constant", "unavailable", "coast", "mark_kind")] +
+                [("mark_cell", ctypes.c_int64), ("levels", ctypes.c_double * STATEFRAME_MAX_LEVELS),
+                 ("rgb", (ctypes.c_double * 3) * STATEFRAME_MAX_LEVELS)])
 
 
 SPAN_LOG_CAP = 4096          # records a span lane's device log holds between two drains (csrc/qd_span.h: QD_SPAN_LOG_CAP is the same number)
@@ -246,6 +266,13 @@ def load():
     lib.qd_stateframe_scan.argtypes = [vp, dp, ctypes.POINTER(i64)]
     lib.qd_stateframe_render.argtypes = [vp, ctypes.POINTER(qd_stateframe_table), sz, dp, i32]
     lib.qd_stateframe_download.argtypes = [vp, i32, vp, sz]
+    lib.qd_tiles_configure.argtypes = [vp, dbl, dp, i32, i32]
+    lib.qd_tiles_set_plane.argtypes = [vp, dp]
+    lib.qd_tiles_available.argtypes = [vp, ip]
+    lib.qd_tiles_scan.argtypes = [vp, ctypes.POINTER(qd_tile_ref), i32, dp, ctypes.POINTER(i64)]
+    lib.qd_tiles_order_stats.argtypes = [vp, i32, i32, ctypes.POINTER(i64), i32, dp, ctypes.POINTER(i64)]
+    lib.qd_tiles_render.argtypes = [vp, ctypes.POINTER(qd_tile_desc), sz, i32, i32]
+    lib.qd_tiles_download.argtypes = [vp, i32, vp, sz]
     lib.qd_budget_diag_configure.argtypes = [vp, i32, u8p]
     lib.qd_budget_diag_schedule.argtypes = [vp, i32, ip]
     lib.qd_budget_diag_log.argtypes = [vp, dp, i32, ip]

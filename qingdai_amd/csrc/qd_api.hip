@@ -477,6 +477,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_eco_div_release(c);
     qd_truecolor_release(c);
     qd_stateframe_release(c);
+    qd_tiles_release(c);
     qd_budget_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);

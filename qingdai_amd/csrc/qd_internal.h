@@ -209,6 +209,7 @@ struct qd_ctx {
     struct QdIndivDaily* idaily = nullptr;   // daily step of the individuals: species ids, level plan, per-cell tables, log (qd_indiv_daily.hip)
     struct QdEcoDiv* ediv = nullptr;         // diversity diagnostics: L_s, the two maps, partials, summary (qd_eco_div.hip)
     struct QdTrueColor* tcol = nullptr;      // true-colour frame: parameters, band tables, image, partials (qd_truecolor.hip)
+    struct QdTiles* tiles = nullptr;         // tile renderer of the ecology / plankton / ISR figures: mosaic, select state, host stack (qd_tiles.hip)
     struct QdStateFrame* sframe = nullptr;   // 15-panel state frame: parameters, mosaic, vorticity plane, partials (qd_stateframe.hip)
     struct QdBudget* budget = nullptr;       // periodic budget diagnostics: schedule, SST snapshot, row partials, log (qd_budget_diag.hip)
     double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
@@ -493,6 +494,7 @@ void qd_indiv_daily_release(qd_ctx* c);
 void qd_eco_div_release(qd_ctx* c);                                              // qd_eco_div.hip
 void qd_truecolor_release(qd_ctx* c);                                            // qd_truecolor.hip
 void qd_stateframe_release(qd_ctx* c);                                           // qd_stateframe.hip
+void qd_tiles_release(qd_ctx* c);                                                // qd_tiles.hip
 // qd_budget_diag.hip: the lane is on for a span when a schedule has been given; `fire` is the step's schedule value
 void qd_budget_release(qd_ctx* c);
 bool qd_budget_scheduled(const qd_ctx* c);

@@ -21,6 +21,7 @@
 // stores only; sqrt is the only rounded library operation and it is correctly rounded.
 #include "qd_internal.h"
 #include "qd_blockred.h"
+#include "qd_contour.h"
 #include "qd_device.h"
 #include <mutex>
 
@@ -65,8 +66,6 @@ struct QdSfArgs {
     uint8_t* img; int mw; int8_t* band; double* fields;
 };
 
-__device__ __forceinline__ bool sf_finite(double x) { return fabs(x) <= DBL_MAX; }
-
 // the field of panel p (0-based) at cell o (run_simulation.py:345-498); panel 8 (the vorticity) is read from its plane
 __device__ __forceinline__ double sf_field(const QdSfArgs& K, int p, int o) {
     const double g = 9.81;
@@ -92,25 +91,6 @@ __device__ __forceinline__ double sf_field(const QdSfArgs& K, int p, int o) {
     default: return qd_nn(K.pcond[o]) * 86400.0;
     }
 }
-
-// np.argmax as a selection: a NaN beats every number, a larger value beats a smaller one, the lower flat index breaks ties
-struct QdSfBest { double v, i; int nan; };
-__device__ __forceinline__ QdSfBest sf_better(const QdSfBest& a, const QdSfBest& b) {
-    const bool take_a = (a.nan != b.nan) ? (a.nan != 0) : ((!a.nan && a.v != b.v) ? (a.v > b.v) : (a.i <= b.i));
-    QdSfBest r;                                                 // field by field: a select of whole structs goes through scratch
-    r.v = take_a ? a.v : b.v; r.i = take_a ? a.i : b.i; r.nan = take_a ? a.nan : b.nan;
-    return r;
-}
-__device__ __forceinline__ QdSfBest sf_wave_best(QdSfBest x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        QdSfBest y;
-        y.v = __shfl_down(x.v, o, 64); y.i = __shfl_down(x.i, o, 64); y.nan = __shfl_down(x.nan, o, 64);
-        x = sf_better(x, y);
-    }
-    return x;
-}
-__device__ __forceinline__ QdSfBest sf_none() { QdSfBest b; b.v = -INFINITY; b.i = INFINITY; b.nan = 0; return b; }
 
 // slots of the scan result (QD_STATEFRAME_SCAN_N doubles; include/qingdai_hip.h names them): 0..2 the minima of T_s, T_a, SST, 3..5
 // their maxima, 6..14 the nine auto panels' minima, 15..23 their maxima, 24 |vort|, 25 the NaN flag of T_a.  The table lives in device
@@ -203,27 +183,10 @@ k_sf_final(const double* __restrict__ partial, int nblk, double* __restrict__ ou
     }
 }
 
-// the band of z in the panel's levels: -1 = white; the extended band has the index n_levels - 1
+// the band of z in the panel's levels: -1 = white; the extended band has the index n_levels - 1 (qd_contour.h)
 __device__ __forceinline__ int sf_band(const qd_stateframe_panel& P, double z) {
-    const int n = P.n_levels;
-    if (n < 2 || P.constant || !sf_finite(z)) return -1;
-    int lo = 0, hi = n;                                         // the number of levels <= z
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (P.levels[mid] <= z) lo = mid + 1; else hi = mid;
-    }
-    if (lo == 0) return -1;
-    if (lo < n) return lo - 1;
-    if (z == P.levels[n - 1]) return n - 2;                     // the last band is closed above
-    return P.extend_max ? n - 1 : -1;
+    return sf_band_of(P.levels, P.n_levels, P.constant != 0, P.extend_max != 0, z);
 }
-
-__device__ __forceinline__ uint8_t sf_u8(double x) {
-    const double q = floor(x * 255.0 + 0.5);
-    return (x == x) ? (uint8_t)(q > 255.0 ? 255.0 : (q < 0.0 ? 0.0 : q)) : (uint8_t)0;
-}
-
-__device__ __forceinline__ bool sf_is_ocean(const QdSfArgs& K, int row, int col) { return K.land[(size_t)row * K.nlon + col] == 0; }
 
 template <bool WANT>
 __global__ void __launch_bounds__(QD_BLOCK)
@@ -238,13 +201,9 @@ k_sf_render(QdSfArgs K) {
     double r = 1.0, g = 1.0, b = 1.0;
     if (bi >= 0) { r = P.rgb[bi][0]; g = P.rgb[bi][1]; b = P.rgb[bi][2]; }
     const bool land = K.land[o] == 1;
-    if (P.coast && land) {
-        const int rn = row + 1 < K.nlat ? row + 1 : row, rs = row > 0 ? row - 1 : row;
-        const int ce = qd_wrapc(col + 1, K.nlon), cw = qd_wrapc(col - 1, K.nlon);
-        if (sf_is_ocean(K, rn, col) || sf_is_ocean(K, rs, col) || sf_is_ocean(K, row, ce) || sf_is_ocean(K, row, cw)) {
-            const double c = P.coast == 2 ? 1.0 : 0.0;
-            r = c; g = c; b = c;
-        }
+    if (P.coast && land && sf_on_coast(K.land, K.nlat, K.nlon, row, col)) {
+        const double c = P.coast == 2 ? 1.0 : 0.0;
+        r = c; g = c; b = c;
     }
     if (p == 0 || p == 7) {
         if (K.flow && land && K.flow[o] >= K.p.river_min) {     // deepskyblue
@@ -261,13 +220,7 @@ k_sf_render(QdSfArgs K) {
         for (int s = 0; s < 2; ++s) {                           // star A: a cyan x; then star B: a yellow +
             const long long m = g_sf_table.mark_cell[s];
             if (m < 0 || m >= K.cells) continue;
-            const int mr = (int)(m / K.nlon), mc = (int)(m - (long long)mr * K.nlon);
-            const int dr = row - mr;
-            int dc = col - mc; if (dc < 0) dc += K.nlon;
-            const int adc = dc == 0 ? 0 : ((dc == 1 || dc == K.nlon - 1) ? 1 : 2);
-            const int adr = dr < 0 ? -dr : dr;
-            const bool centre = adr == 0 && adc == 0;
-            const bool hit = s == 0 ? (centre || (adr == 1 && adc == 1)) : (centre || (adr == 0 && adc == 1) || (adr == 1 && adc == 0));
+            const bool hit = sf_mark_hit(s == 1, m, K.nlon, row, col);
             if (hit) { r = s == 0 ? 0.0 : 1.0; g = 1.0; b = s == 0 ? 1.0 : 0.0; }
         }
     }

@@ -478,6 +478,85 @@ class Device:
         self._chk(self.lib.qd_stateframe_download(self.h, 2, out.ctypes.data, out.size), "qd_stateframe_download")
         return out
 
+    # ---- tiles of the ecology / plankton / ISR figures (qd_tiles.hip)
+    def tiles_configure(self, height_scale=10.0, layers=None):
+        """height_scale: QD_ECO_HEIGHT_SCALE_M.  layers None: the stack sources read the resident stack of eco_daily_configure; else a
+        host [S, K, lat, lon] stack, uploaded here."""
+        a = None if layers is None else _c(layers)
+        if a is not None and (a.ndim != 4 or a.shape[2:] != self.shape):
+            raise ValueError(f"tiles_configure: layers must be [S, K, {self.shape[0]}, {self.shape[1]}], got {a.shape}")
+        self._chk(self.lib.qd_tiles_configure(self.h, float(height_scale), None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                              0 if a is None else a.shape[0], 0 if a is None else a.shape[1]), "qd_tiles_configure")
+
+    def tiles_set_plane(self, plane):
+        """A host [lat, lon] map for the tile source "HOST_PLANE" (kept until the next tiles_configure)."""
+        a = _c(plane)
+        if a.shape != self.shape:
+            raise ValueError(f"tiles_set_plane: plane must be {self.shape}, got {a.shape}")
+        self._chk(self.lib.qd_tiles_set_plane(self.h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "qd_tiles_set_plane")
+
+    def tiles_available(self):
+        """-> (an LAI map, a scalar alpha map, a banded alpha map) are on the device."""
+        out = (ctypes.c_int32 * 3)()
+        self._chk(self.lib.qd_tiles_available(self.h, out), "qd_tiles_available")
+        return bool(out[0]), bool(out[1]), bool(out[2])
+
+    @staticmethod
+    def _tile_refs(refs):
+        arr = (_lib.qd_tile_ref * max(1, len(refs)))()
+        for k, (src, idx) in enumerate(refs):
+            arr[k].source, arr[k].index = (_lib.TILE[src] if isinstance(src, str) else int(src)), int(idx)
+        return arr
+
+    def tiles_scan(self, refs):
+        """refs: up to 8 (source, index), source a name of _lib.TILE_SOURCES or its id -> per plane {"min", "max" over the finite values,
+        "nan" (the plane holds one), "argmax" (np.argmax's flat cell), "argmax_value"}."""
+        self.flush()
+        n = len(refs)
+        out = np.empty((max(1, n), 4), dtype=np.float64)
+        cells = (ctypes.c_int64 * max(1, n))()
+        self._chk(self.lib.qd_tiles_scan(self.h, self._tile_refs(refs), n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cells), "qd_tiles_scan")
+        return [{"min": float(out[k, 0]), "max": float(out[k, 1]), "nan": bool(out[k, 2] > 0.0), "argmax": int(cells[k]),
+                 "argmax_value": float(out[k, 3])} for k in range(n)]
+
+    def tiles_order_stats(self, source, index, ranks):
+        """-> (count of non-NaN cells, [the ranks[k]-th smallest of them, 0-based]); NaN for a rank that is not below the count."""
+        self.flush()
+        r = (ctypes.c_int64 * max(1, len(ranks)))(*[int(x) for x in ranks])
+        vals = np.full(max(1, len(ranks)), np.nan, dtype=np.float64)
+        count = ctypes.c_int64(-1)
+        self._chk(self.lib.qd_tiles_order_stats(self.h, _lib.TILE[source] if isinstance(source, str) else int(source), int(index), r, len(ranks),
+                                                vals.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(count)), "qd_tiles_order_stats")
+        return int(count.value), vals[:len(ranks)]
+
+    def tiles_render(self, tiles, want_stacks=False):
+        """tiles: a sequence of _lib.qd_tile_desc (one row, at most 8).  The mosaic stays resident (tiles_image / tiles_bands /
+        tiles_planes)."""
+        self.flush()
+        n = len(tiles)
+        arr = (_lib.qd_tile_desc * max(1, n))(*tiles)
+        self._chk(self.lib.qd_tiles_render(self.h, arr, ctypes.sizeof(_lib.qd_tile_desc), n, 1 if want_stacks else 0), "qd_tiles_render")
+        self._tiles_n = n
+
+    def tiles_image(self):
+        """The u8 mosaic [lat + 2 gutters, n lon + (n + 1) gutters, 3] of the last render."""
+        g, n = _lib.STATEFRAME_GUTTER, getattr(self, "_tiles_n", 1)
+        out = np.empty((self.shape[0] + 2 * g, n * self.shape[1] + (n + 1) * g, 3), dtype=np.uint8)
+        self._chk(self.lib.qd_tiles_download(self.h, 0, out.ctypes.data, out.size), "qd_tiles_download")
+        return out
+
+    def tiles_bands(self):
+        """The int8 band indices [n, lat, lon] of the last render (want_stacks=True); -1 = white."""
+        out = np.empty((getattr(self, "_tiles_n", 1),) + self.shape, dtype=np.int8)
+        self._chk(self.lib.qd_tiles_download(self.h, 1, out.ctypes.data, out.size), "qd_tiles_download")
+        return out
+
+    def tiles_planes(self):
+        """The f64 planes [n, lat, lon] handed to the band search by the last render (want_stacks=True)."""
+        out = np.empty((getattr(self, "_tiles_n", 1),) + self.shape, dtype=np.float64)
+        self._chk(self.lib.qd_tiles_download(self.h, 2, out.ctypes.data, out.size), "qd_tiles_download")
+        return out
+
     # ---- phytoplankton tracers carried by the ocean currents (pygcm/ecology/phyto.py:496-547), resident
     def phyto_configure(self, n_species, K_h, adv_alpha):
         self._chk(self.lib.qd_phyto_configure(self.h, int(n_species), float(K_h), float(adv_alpha)), "qd_phyto_configure")

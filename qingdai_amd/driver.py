@@ -69,8 +69,21 @@ state (qingdai_amd/stateframe.py, qd_stateframe_*).  A chunk ends with the firin
 and a state_day_*.json with the titles, units, colormaps and levels, before the true-colour frame as in the reference.  At the end
 of a chunk PRECIP, ALBEDO, EFLUX, PCOND and OLR hold the firing step's own values.  QD_PLOT_PS_MODE=abs as in
 the reference.  The streamlines of the panels 7 and 8 are not drawn (their speed field is filled instead).
-Not carried over (out of the hot path): genes, plankton.json, the other matplotlib figures (ocean, ecology,
-plankton, ISR; the diversity annotation of the plot panel, run_simulation.py:1025-1052, goes with them).
+Ecology, plankton and ISR figures (QD_FIGURES=1, default 0; the same plot clock; plot_plankton_species, plot_isr_components and
+plot_ecology, run_simulation.py:828-1060, 2430-2490): with the switch on, the reference's QD_PLOT_PHYTO (default 1, needs
+plankton), QD_ECO_PLOT (default 1) and QD_PLOT_ISR (default 0) pick the figures.  Each is one row of n_lat x n_lon tiles with the
+state frame's geometry and rules, composed on the device from the resident state (qingdai_amd/figures.py, qd_tiles_*): the LAI,
+scalar alpha, banded alpha, canopy height and species-0 density maps (three "not available" tiles without a population); the
+tracers of species 0 and 1 with the colour range of QD_PHYTO_VMAX or the 99th percentile of the ocean cells (an exact radix select
+on the device); the two per-star planes with the subsolar marks and the reference's [Diagnostics] separation line.  A chunk ends
+with the firing step, which writes <QD_OUTPUT_DIR>/plankton/species{0,1}_day_*.png, ecology_day_*.png and
+isr_components_day_*.png, each with a .json of titles, units, colormaps, levels and marks, behind the state frame and the
+true-colour frame.  A banded alpha the run has not computed yet is computed for the panel alone, as the reference does
+(run_simulation.py:2458-2466); the resident map is left as it is.  A figure that fails prints one note ([PlanktonViz] / [EcologyViz]
+under their diag switches) and the run goes on.
+Not carried over (out of the hot path): genes, plankton.json, plot_ocean (defined in the reference, never
+called by its loop) and the diversity annotation of the ecology panel (run_simulation.py:1025-1052: it reads a name that is not
+in scope there and is never drawn).
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -538,6 +551,63 @@ class Simulation:
             self._stateframe_failed = True
             return None
 
+    # -- ecology, plankton and ISR figures (run_simulation.py:828-1060, 2430-2490)
+    def enable_figures(self, env=None):
+        """QD_FIGURES=1: the tile renderer on this run's device, configured at once (a latitude-band handle is refused here), and
+        the reference's plot interval -> the Figures or None.  QD_PLOT_PHYTO, QD_ECO_PLOT and QD_PLOT_ISR then pick the figures."""
+        env = os.environ if env is None else env
+        self.figures = None
+        from .figures import figures_enabled
+        if figures_enabled(env):
+            from .figures import Figures, plot_interval_steps
+            fg = Figures(self, env=env)
+            fg.configure()
+            self.figures = fg
+            self.figures_every = plot_interval_steps(env, self.dt)
+            self._figures_failed = set()
+        return self.figures
+
+    def figures_due(self, i0, n_max):
+        """As truecolor_due, for the three figures: the same plot clock."""
+        if getattr(self, "figures", None) is None or n_max <= 0:
+            return None, None
+        from .figures import firing_steps
+        fired = firing_steps(i0, n_max, self.figures_every)
+        if not fired:
+            return None, None
+        times, _ = self._span_times(fired[0] + 1, advance=False)
+        return fired[0] + 1, float(times[fired[0]]) / self.day_seconds
+
+    def figure_names(self, env=None):
+        """The figures this run writes, in their order (run_simulation.py:2431, 2469, 2489)."""
+        from .figures import read_env
+        e = read_env(self.figures.env if env is None else env)
+        return ([n for n, on in (("plankton", e["plot_phyto"] and self.phyto is not None), ("ecology", e["plot_eco"]), ("ISR", e["plot_isr"])) if on],
+                e)
+
+    def run_figures(self, t_days, output_dir=None):
+        """One firing on the state as it stands (the end of the firing step): the plankton maps, the ecology panel, the ISR figure,
+        each with its .json.  A failure prints one note per figure -- the reference's [PlanktonViz] / [EcologyViz] lines under their
+        diag switches -- and never stops the run."""
+        fg = self.figures
+        names, e = self.figure_names()
+        done = []
+
+        def attempt(name, fn, note):
+            try:
+                done.append(fn())
+            except Exception as ex:      # noqa: BLE001
+                if name not in self._figures_failed and note is not None:
+                    print(note.format(ex))
+                self._figures_failed.add(name)
+        if "plankton" in names:
+            attempt("plankton", lambda: fg.write_plankton(t_days, output_dir), "[PlanktonViz] skipped: {}" if e["phyto_diag"] else None)
+        if "ecology" in names:
+            attempt("ecology", lambda: fg.write_ecology(t_days, output_dir), "[EcologyViz] skipped: {}" if e["eco_diag"] else None)
+        if "ISR" in names:
+            attempt("ISR", lambda: fg.write_isr(t_days, output_dir, echo=print)[0], "[ISRViz] figure skipped: {}")
+        return done
+
     def _run_chunk(self, n, energy_diag=False):
         origin = self._t_origin
         times, t_next = self._span_times(n)
@@ -687,8 +757,15 @@ def hydro_autogen(env):
     return int(env.get("QD_HYDRO_AUTOGEN", "0")) == 1
 
 
-def plots_line(stateframe, truecolor, sim):
-    """The [Plots] start-up line.  Without the state frame it is one of the two wordings it always had."""
+def plots_line(stateframe, truecolor, sim, figures=None):
+    """The [Plots] start-up line.  Without the figures it is one of the three wordings it always had."""
+    if figures is not None:
+        names, _ = sim.figure_names()
+        what = [w for w, on in (("the 15-panel state frame (state_day_*.png + .json, no axes)", stateframe is not None),
+                                ("the true-colour frame", truecolor is not None)) if on]
+        what.append(("the " + ", ".join(names) + " figures (tiles + .json, no axes)") if names else "no further figure (every QD_FIGURES switch is off)")
+        return (f"[Plots] {'; '.join(what)}: produced by the device driver, every {sim.figures_every} steps; the reference's plot_ocean "
+                "is never called and is not.")
     if stateframe is None:
         if truecolor is None:
             return "[Plots] matplotlib panels are not produced by the device driver (out of the hot path)."
@@ -771,7 +848,7 @@ def main(argv=None):
     n_total = len(np.arange(t0, t0 + duration, sim.dt))
     print(f"Grid resolution: {sim.grid.n_lat} lat x {sim.grid.n_lon} lon | dt = {sim.dt} s | "
           f"{duration / day:.1f} planetary days | {n_total} steps")
-    plots = plots_line(sim.enable_stateframe(env), sim.enable_truecolor(env), sim)
+    plots = plots_line(sim.enable_stateframe(env), sim.enable_truecolor(env), sim, sim.enable_figures(env))
     print(plots)
 
     autosave_on = int(env.get("QD_AUTOSAVE_ENABLE", "1")) == 1
@@ -812,8 +889,9 @@ def main(argv=None):
         fire_in, fire_day = sim.diversity_due(min(200, n_total - done))
         frame_in, frame_day = sim.truecolor_due(done, min(200, n_total - done))
         state_in, state_day = sim.stateframe_due(done, min(200, n_total - done))
+        figs_in, figs_day = sim.figures_due(done, min(200, n_total - done))
         n = chunk_until(sim.t, sim.dt, next_autosave_t if autosave_on else None, n_total - done,
-                        fire_in=min((k for k in (fire_in, frame_in, state_in) if k is not None), default=None))
+                        fire_in=min((k for k in (fire_in, frame_in, state_in, figs_in) if k is not None), default=None))
         sim.run_steps(n)
         done += n
         if fire_in is not None and n == fire_in:               # the chunk ended with the firing step
@@ -822,6 +900,8 @@ def main(argv=None):
             sim.run_stateframe(state_day)
         if frame_in is not None and n == frame_in:             # (both cadences may fall on one step: diversity first, as in the reference)
             sim.run_truecolor(frame_day)
+        if figs_in is not None and n == figs_in:               # plankton, ecology, ISR behind the two frames (run_simulation.py:2430-2490)
+            sim.run_figures(figs_day)
         if int(env.get("QD_DYN_DIAG_PRINT", "1")) == 1:
             dg = sim.diagnostics()
             el = time.perf_counter() - wall0

@@ -7,9 +7,10 @@ tiles of n_lat x n_lon pixels (one pixel per cell, northernmost row on top, a wh
 colourbars): csrc/qd_stateframe.hip computes the fields, reduces the extremes the level rules need (qd_stateframe_scan), and draws
 every tile as the contourf sampled at the cell centres with the coast, river, lake and star-position overlays
 (qd_stateframe_render).  This module is the host side between the two launches: contourf's level rules restated without
-matplotlib (auto_levels), its band colours (band_colours; the twelve colormap tables are package data, data/stateframe_cmaps.json,
+matplotlib (auto_levels), its band colours (band_colours; the colormap tables are package data, data/stateframe_cmaps.json,
 written by scripts/gen_stateframe_cmaps.py -- text with repr floats, because the repository keeps binary files under tests/golden/
-only and this one is read by the product at run time; twelve tables, one per colormap name plot_state uses), the table the render reads (build_table / pack_table), and the JSON sidecar that
+only and this one is read by the product at run time; twelve tables, one per colormap name plot_state uses, and Greens for
+qingdai_amd/figures.py), the table the render reads (build_table / pack_table), and the JSON sidecar that
 carries what the colourbars would say.
 
 Two departures from the reference: the panels 7 and 8 fill the speed field the reference colours its streamlines with (the

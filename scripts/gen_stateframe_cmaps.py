@@ -1,5 +1,5 @@
 """Regenerate qingdai_amd/data/stateframe_cmaps.json: the 256 x 3 f64 lookup tables of the colormaps the reference's plot_state names
-(scripts/run_simulation.py:355-499), read from the local matplotlib.  The state frame (qingdai_amd/stateframe.py) looks its band
+(scripts/run_simulation.py:355-499) and, last, the one more its plot_ecology names (:1009), read from the local matplotlib.  The state frame (qingdai_amd/stateframe.py) looks its band
 colours up in these tables, so that no matplotlib is needed at run time.  The file is text: every number is written with repr,
 which reads back to the same double."""
 import json
@@ -9,7 +9,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "..", "qingdai_amd", "data", "stateframe_cmaps.json")
-NAMES = ("coolwarm", "viridis", "Blues", "Greys", "RdBu_r", "PuOr", "magma", "cividis", "plasma", "GnBu", "YlGn", "BuPu")
+NAMES = ("coolwarm", "viridis", "Blues", "Greys", "RdBu_r", "PuOr", "magma", "cividis", "plasma", "GnBu", "YlGn", "BuPu",
+         "Greens")      # plot_ecology's canopy-height tile (:1009, qingdai_amd/figures.py)
 
 
 def main():
