@@ -325,6 +325,21 @@ int qd_eco_daily_schedule(qd_handle h, int n, const int32_t* fire);   /* the nex
 int qd_eco_daily_log(qd_handle h, double* out, int max, int* n);      /* drains the log: *n records of 4 doubles */
 int qd_eco_daily_state(qd_handle h, int64_t* n_firings);              /* firings since the configure */
 
+/* ---- restore of the vegetation state from an ecology autosave (EcologyAdapter.load_autosave, pygcm/ecology/adapter.py:742-757),
+ * whole-globe handles ---------------------------------------------------------------------------------------------------------
+ * lai: the file's [n_lat][n_lon] LAI plane, float32 (lai_is_f32 != 0: what a NetCDF file hands the reference) or float64 (its NPZ
+ * branch).  w [n_species]: the species weights as the reference leaves them -- clipped at 0 and divided by their sum, or uniform
+ * when the sum is 0.  One launch over the cells: L = np.clip(LAI, 0, lai_max) (NaN passes, +inf -> lai_max, no land mask: ocean
+ * cells keep their values), q = L / n_layers, plane[s][k] = w_s * q for all n_species * n_layers planes -- with lai_is_f32 the
+ * clip, the IEEE divide and the multiply are float32 (subnormals kept) and only the store widens, as NumPy >= 2 runs it; else all
+ * f64.  The planes go into the resident stack of qd_eco_daily_configure when that exists (n_species / n_layers must be its);
+ * ECO_LAI receives their sum in np.sum(axis=(0,1))'s order, f64 -- total_LAI() after the load, which differs from the clipped
+ * plane pop.LAI in the last bit.  Leaves the canopy state as qd_eco_set_lai_layers(h, stack, n, 0) does; ECO_AGE, ECO_SEEDBANK,
+ * E_day and the clocks are untouched, as in the reference.  Refused: latitude bands, no qd_eco_configure, n_species outside
+ * 1..64, n_layers outside 1..8, a shape that is not the resident stack's. */
+int qd_eco_state_restore(qd_handle h, const void* lai, int lai_is_f32, const double* w, int n_species, int n_layers,
+                         double lai_max);
+
 /* ---- daily step of the sampled individuals (IndividualPool.step_daily, pygcm/ecology/individuals.py:193-361; driver call
  * scripts/run_simulation.py:1818-1835), whole-globe handles ----------------------------------------------------------------------
  * Needs qd_indiv_configure (the pool, per_cell consecutive individuals per sampled cell) and qd_eco_daily_configure (the resident

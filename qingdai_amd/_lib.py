@@ -47,6 +47,7 @@ SYMBOLS = [
     "qd_phyto_daily_state", "qd_phyto_daily_insolation",
     "qd_eco_daily_configure", "qd_eco_daily_set_layers", "qd_eco_daily_get_layers", "qd_eco_daily_step", "qd_eco_daily_schedule",
     "qd_eco_daily_log", "qd_eco_daily_state",
+    "qd_eco_state_restore",
     "qd_indiv_daily_configure", "qd_indiv_daily_step", "qd_indiv_daily_log", "qd_indiv_daily_weights", "qd_indiv_daily_state",
     "qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download",
     "qd_truecolor_configure", "qd_truecolor_render", "qd_truecolor_download",
@@ -247,6 +248,7 @@ def load():
     lib.qd_eco_daily_configure.argtypes = [vp, ctypes.POINTER(qd_eco_daily_params), sz, ip, dp]
     lib.qd_eco_daily_set_layers.argtypes = [vp, vp, i32]
     lib.qd_eco_daily_get_layers.argtypes = [vp, vp, i32]
+    lib.qd_eco_state_restore.argtypes = [vp, vp, i32, dp, i32, i32, ctypes.c_double]
     lib.qd_eco_daily_step.argtypes = [vp, vp]
     lib.qd_eco_daily_schedule.argtypes = [vp, i32, ip]
     lib.qd_eco_daily_log.argtypes = [vp, dp, i32, ip]

@@ -316,6 +316,21 @@ class Device:
         self._chk(self.lib.qd_eco_daily_state(self.h, ctypes.byref(n)), "qd_eco_daily_state")
         return int(n.value)
 
+    # ---- restore from an ecology autosave (qd_eco_state.hip)
+    def eco_state_restore(self, lai, weights, n_layers, lai_max):
+        """adapter.py:742-757 on the device: lai [lat, lon] float32 (the arithmetic is then float32, as the reference's NetCDF
+        branch runs it) or float64; weights [S] as the reference leaves them.  Writes the resident stack of the daily lane when it
+        exists, and ECO_LAI."""
+        self.flush()
+        f32 = np.asarray(lai).dtype == np.float32
+        a = _c(lai, np.float32 if f32 else np.float64)
+        if a.shape != self.shape:
+            raise ValueError(f"eco_state_restore: expected a [{self.shape[0]}, {self.shape[1]}] LAI plane, got {a.shape}")
+        w = _c(weights)
+        self._chk(self.lib.qd_eco_state_restore(self.h, a.ctypes.data, 1 if f32 else 0, w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                int(w.size), int(n_layers), float(lai_max)), "qd_eco_state_restore")
+        self._host.pop("ECO_LAI", None)
+
     # ---- daily step of the individuals (qd_indiv_daily.hip)
     def indiv_daily_configure(self, params, species_id, level):
         s, l = _c(species_id, np.int32), _c(level, np.int32)

@@ -32,7 +32,14 @@ Daily vegetation dynamics (QD_ECO_DAILY=1, default 0, with QD_ECO_ENABLE=1 and n
 growth, senescence, layered allocation, per-species spread, seed bank, age -- runs inside the resident loop on the steps the
 reference's day accumulator names (qd_step_n bit9, at the top of the step; qingdai_amd/ecology.py PopulationDaily), spans are no
 longer cut at day boundaries, and each chunk's `[Ecology] daily:` lines are printed after it from the device log (QD_ECO_DIAG=1).
-QD_ECO_MUT_RATE > 0 is refused with it; genes export and ecology.nc stay out.
+QD_ECO_MUT_RATE > 0 is refused with it; genes export stays out.
+Saving and resuming the vegetation state (QD_ECO_PERSIST, default 0; run_simulation.py:248-305, 1464-1488, 1566-1590,
+pygcm/ecology/adapter.py:284-426, 574-777): at 1 every autosave writes data/ecology.nc (QD_ECO_AUTOSAVE_PATH when that ends in .nc;
+the reference's variable set, a time-stamped copy, QD_ECO_AUTOSAVE_KEEP of them kept) behind data/atmosphere.nc and data/genes.json
+behind that, and start-up -- behind the atmosphere / ocean block, gated by QD_AUTOSAVE_LOAD alone, after the individuals were
+sampled -- reads genes.json (QD_ECO_GENES_JSON_PATH) and then the ecology file (QD_ECO_AUTOSAVE_PATH, QD_ECO_ON_MISMATCH) with the
+reference's [Ecology] lines.  The load rebuilds the LAI stack from the file's one plane on the device (qd_eco_state_restore) in the
+reference's arithmetic; at 2 the file also carries qd_* variables with which the ecology lanes resume bit for bit.
 Daily step of the individuals (QD_ECO_INDIV_DAILY=1, default 0; needs QD_ECO_DAILY=1, QD_ECO_ENABLE=1, a population, individuals
 and no daily_hook, else refused at start-up): IndividualPool.step_daily (individuals.py:193-361, run_simulation.py:1818-1835) runs
 on the device directly behind every firing of the daily vegetation step, on the same soil index (qingdai_amd/ecology.py
@@ -81,7 +88,7 @@ isr_components_day_*.png, each with a .json of titles, units, colormaps, levels 
 true-colour frame.  A banded alpha the run has not computed yet is computed for the panel alone, as the reference does
 (run_simulation.py:2458-2466); the resident map is left as it is.  A figure that fails prints one note ([PlanktonViz] / [EcologyViz]
 under their diag switches) and the run goes on.
-Not carried over (out of the hot path): genes, plankton.json, plot_ocean (defined in the reference, never
+Not carried over (out of the hot path): genes export (QD_ECO_GENES_EXPORT), plankton.json, plot_ocean (defined in the reference, never
 called by its loop) and the diversity annotation of the ecology panel (run_simulation.py:1025-1052: it reads a name that is not
 in scope there and is never drawn).
 
@@ -342,10 +349,11 @@ class Simulation:
         return bool(v)
 
     def save_autosave(self, data_dir="data"):
-        """run_simulation.py:248-270 + 126-159 + 185-220: data/atmosphere.nc (the restart layout with the epoch
-        in t_seconds), data/ocean.nc, data/topography.nc.  Ecology / genes files are outside this path."""
+        """run_simulation.py:248-304 + 126-159 + 185-220: data/atmosphere.nc (the restart layout with the epoch
+        in t_seconds), under QD_ECO_PERSIST >= 1 data/ecology.nc and data/genes.json, then data/ocean.nc, data/topography.nc."""
         day = self.t / (2 * np.pi / PLANET_OMEGA)
         save_restart(os.path.join(data_dir, "atmosphere.nc"), self.grid, self.dev, self.t, self.land_mask, with_ocean=self.ocean is not None)
+        self.save_ecology(data_dir, day)
         if self.ocean is not None:
             save_ocean(os.path.join(data_dir, "ocean.nc"), self.grid, self.dev, day_value=day)
         topo.export_topography_to_netcdf(os.path.join(data_dir, "topography.nc"), self.grid, self.land_mask, self.base_albedo,
@@ -354,6 +362,64 @@ class Simulation:
             self.phyto_daily.save_distribution_nc(os.path.join(data_dir, "plankton.nc"), day_value=day)
         elif self.phyto is not None:                            # (the tracer part of plankton.nc)
             self.phyto.save_distribution_nc(os.path.join(data_dir, "plankton.nc"), day_value=day)
+
+    def save_ecology(self, data_dir="data", day_value=None, env=None):
+        """run_simulation.py:274-304 under QD_ECO_PERSIST >= 1: ecology.nc -- at QD_ECO_AUTOSAVE_PATH when that ends in `.nc`, else
+        <data>/ecology.nc -- through EcologyAdapter.save_autosave, then <data>/genes.json.  A failure prints the reference's line and
+        never stops the run -> the path written, or None."""
+        env = os.environ if env is None else env
+        if eco_persist_level(env) < 1 or self.eco is None or self.eco.pop is None:
+            return None
+        try:
+            path_env = env.get("QD_ECO_AUTOSAVE_PATH")
+            path = path_env if (path_env and path_env.lower().endswith(".nc")) else os.path.join(data_dir, "ecology.nc")
+            try:
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            except Exception:      # noqa: BLE001
+                pass
+            ok = False
+            try:
+                ok = bool(self.eco.save_autosave(path, day_value=float(day_value), extended=eco_persist_level(env) == 2, indiv=self.indiv))
+                if not ok:
+                    print(f"[Autosave] Ecology extended save returned False for '{path}'")
+            except Exception as e:      # noqa: BLE001
+                print(f"[Autosave] Ecology extended save failed: {e}")
+            try:
+                self.eco.save_genes_json(os.path.join(data_dir, "genes.json"), day_value=float(day_value))
+            except Exception:      # noqa: BLE001
+                pass
+            return path if ok else None
+        except Exception as e:      # noqa: BLE001
+            print(f"[Autosave] Ecology save failed: {e}")
+            return None
+
+    def load_ecology(self, data_dir="data", env=None):
+        """run_simulation.py:1464-1488 / 1566-1590 under QD_ECO_PERSIST >= 1 and QD_AUTOSAVE_LOAD=1 (default): genes.json first (from
+        QD_ECO_GENES_JSON_PATH or <data>/genes.json), then the ecology file (QD_ECO_AUTOSAVE_PATH -- any extension -- or
+        <data>/ecology.nc) with QD_ECO_ON_MISMATCH, and the reference's lines under QD_ECO_DIAG -> True when the state was loaded."""
+        env = os.environ if env is None else env
+        if eco_persist_level(env) < 1 or self.eco is None or int(env.get("QD_AUTOSAVE_LOAD", "1")) != 1:
+            return False
+        diag = int(env.get("QD_ECO_DIAG", "1")) == 1
+        try:
+            genes_path = env.get("QD_ECO_GENES_JSON_PATH") or os.path.join(data_dir, "genes.json")
+            if os.path.exists(genes_path):
+                self.eco.load_genes_json(genes_path)
+        except Exception as e:      # noqa: BLE001
+            if diag:
+                print(f"[Ecology] genes autosave load skipped: {e}")
+        ok = False
+        try:
+            eco_path = env.get("QD_ECO_AUTOSAVE_PATH") or os.path.join(data_dir, "ecology.nc")
+            if os.path.exists(eco_path):
+                ok = bool(self.eco.load_autosave(eco_path, on_mismatch=env.get("QD_ECO_ON_MISMATCH", "fallback"), indiv=self.indiv,
+                                                        extended=eco_persist_level(env) == 2))
+                if diag:
+                    print(f"[Ecology] autosave load {'OK' if ok else 'failed'} from '{eco_path}'")
+        except Exception as e:      # noqa: BLE001
+            if diag:
+                print(f"[Ecology] autosave load skipped: {e}")
+        return ok
 
     # -- the loop
     def bootstrap_ecology(self):
@@ -733,6 +799,13 @@ def eco_daily_enabled(env):
     return True
 
 
+def eco_persist_level(env):
+    """QD_ECO_PERSIST (default 0): 1 writes and reads data/ecology.nc and data/genes.json with the reference's variable set, 2 adds the
+    qd_* extension variables with which the ecology lanes resume bit for bit (qingdai_amd/ecology.py persist_level)."""
+    from .ecology import persist_level
+    return persist_level(env)
+
+
 def indiv_daily_enabled(env, *, eco_daily, ecology, population, individuals, daily_hook):
     """QD_ECO_INDIV_DAILY (default 0): 1 runs IndividualPool.step_daily on the device behind every firing of the daily vegetation
     lane.  It acts on that lane's resident stack, so it is refused without what the lane and the pool need."""
@@ -830,6 +903,9 @@ def main(argv=None):
         except Exception as e:             # noqa: BLE001
             print(f"[Restart] Failed to load '{loaded}': {e}\nContinuing with fresh init.")
             loaded = None
+    # run_simulation.py:1464-1488 / 1566-1590: genes.json, then the ecology autosave, behind either checkpoint or none
+    # (QD_ECO_PERSIST >= 1; gated by QD_AUTOSAVE_LOAD alone, like the reference)
+    sim.load_ecology(data_dir, env)
     # run_simulation.py:1377-1399: data/plankton.nc restores the tracer distributions at startup (QD_LOAD_PLANKTON=1, default)
     if sim.phyto is not None and int(env.get("QD_LOAD_PLANKTON", "1")) == 1:
         pnc = os.path.join(data_dir, "plankton.nc")

@@ -18,19 +18,27 @@ seam, and `Device.step_n(..., eco_daily=...)` fires it inside a span (QD_ECO_DAI
 and the file writer the driver uses under QD_ECO_DIVERSITY_ENABLE=1.  IndividualPool.step_daily
 (individuals.py:193-361) runs on the device behind every firing of that daily step: `IndividualDaily` reads its variables, plans
 the levels of the cell loop (`plan_levels`) and configures it, `IndividualPool.step_daily` is its class seam
-(QD_ECO_INDIV_DAILY=1 in the driver).  Mutation and genes are host code outside this package: `Simulation` hands `E_day` to a
+(QD_ECO_INDIV_DAILY=1 in the driver).  The state survives a restart through the reference's files (adapter.py:284-426, 574-777;
+QD_ECO_PERSIST in the driver): `EcologyAdapter.save_autosave` / `load_autosave` write and read ecology.nc (or its NPZ form),
+`save_genes_json` / `load_genes_json` genes.json from a small host gene table (`Gene`), and the load rebuilds the LAI stack from the
+file's one plane on the device (qd_eco_state_restore).  Mutation is host code outside this package: `Simulation` hands `E_day` to a
 caller-supplied daily hook and takes the new LAI layers back.
 """
 from __future__ import annotations
 
 import ctypes
+import glob
+import json
 import os
-from dataclasses import dataclass
+import shutil
+import time
+from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import ncio
 from . import spectral as sp
-from ._lib import qd_eco_params, qd_eco_daily_params, qd_indiv_daily_params
+from ._lib import QdError, qd_eco_params, qd_eco_daily_params, qd_indiv_daily_params
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -415,21 +423,34 @@ class PopulationDaily:
             germ_frac=_envf_any("QD_ECO_SEED_GERMINATE_FRAC", 0.10), bank_decay=_envf_any("QD_ECO_SEED_BANK_DECAY", 0.02))
         self.configure()
 
-    def configure(self):
-        """(Re)configure the device: parameters, modes, weights, the current layers; age, seed bank, log and firing count to zero."""
+    def configure(self, stack=True):
+        """(Re)configure the device: parameters, modes, weights, the current layers; age, seed bank, log and firing count to zero.
+        stack=False leaves the resident stack as the device holds it (zeros after a change of the plane count): the caller fills it,
+        and the host copy counts as stale."""
         pop = self.pop
-        layers = np.ascontiguousarray(pop.LAI_layers_SK, dtype=np.float64)
+        layers = np.ascontiguousarray(pop.LAI_layers_SK, dtype=np.float64) if stack else None
         w = np.asarray(pop.species_weights, dtype=float)
         w = w / (np.sum(w) + 1e-12)                                                     # population.py:571-572
         mode = [1 if str(m).lower() == "seed" else 0 for m in self.species_modes]
         self.dev.eco_daily_configure(self.params, mode, w)
         self.n_firings = 0
         pop.daily = self
-        pop.LAI_layers_SK = layers
-        self.dev.eco_daily_set_layers(layers.reshape((-1,) + self.shape))
+        if stack:
+            pop.LAI_layers_SK = layers
+            self.dev.eco_daily_set_layers(layers.reshape((-1,) + self.shape))
+        else:
+            pop._layers_at = None
         self.dev.upload_now("ECO_GATE", pop.land.astype(float))                         # population.py:171
         if getattr(pop, "indiv_daily", None) is not None:                               # the device dropped it with the old stack
             pop.indiv_daily.configure()
+
+    def resize(self, n_species, stack=True):
+        """An autosave file with another species count (adapter.py:745-752): the lane is configured again for it, with modes from
+        species_modes_from_env.  The caller has already given pop.Ns and pop.species_weights."""
+        self.params.n_species = int(n_species)
+        self.species_modes = species_modes_from_env(int(n_species), self.pop.species_weights,
+                                                    bool(os.getenv("QD_ECO_SPECIES_WEIGHTS", "").strip()))
+        self.configure(stack=stack)
 
     def _fired(self, n):
         self.n_firings += int(n)
@@ -538,6 +559,156 @@ class IndividualDaily:
 
 
 @dataclass
+class Gene:
+    """One row of the host gene table: the fields the reference's Genes carries (genes.py:19-41); peaks are (center_nm, width_nm,
+    height) tuples.  Only the peaks and the drought tolerance act on the run; the rest travels through genes.json."""
+    identity: str = "grass"
+    alloc_root: float = 0.3
+    alloc_stem: float = 0.2
+    alloc_leaf: float = 0.5
+    leaf_area_per_energy: float = 2.0e-3
+    peaks: list = field(default_factory=list)
+    drought_tolerance: float = 0.3
+    gdd_germinate: float = 80.0
+    lifespan_days: int = 365
+    provenance: str | None = None
+
+    @staticmethod
+    def from_env(prefix="QD_ECO_GENE_"):
+        """Genes.from_env (genes.py:45-92): <prefix>IDENTITY, ALLOC_ROOT / _STEM / _LEAF (normalised; 0.3 / 0.2 / 0.5 when their
+        sum is not positive), LEAF_AREA_PER_EN, PEAKS, DROUGHT_TOL, GDD_GERMINATE, LIFESPAN_DAYS, each with its default on a
+        parse error."""
+        def f(name, default):
+            try:
+                return float(os.getenv(prefix + name, str(default)))
+            except Exception:      # noqa: BLE001
+                return default
+        g = Gene(identity=os.getenv(prefix + "IDENTITY", "grass").strip(), alloc_root=f("ALLOC_ROOT", 0.3),
+                 alloc_stem=f("ALLOC_STEM", 0.2), alloc_leaf=f("ALLOC_LEAF", 0.5), leaf_area_per_energy=f("LEAF_AREA_PER_EN", 2.0e-3),
+                 peaks=_peaks_from_env(prefix), drought_tolerance=f("DROUGHT_TOL", 0.3), gdd_germinate=f("GDD_GERMINATE", 80.0),
+                 lifespan_days=int(f("LIFESPAN_DAYS", 365)))
+        s = g.alloc_root + g.alloc_stem + g.alloc_leaf
+        if s <= 0:
+            g.alloc_root, g.alloc_stem, g.alloc_leaf = 0.3, 0.2, 0.5
+        else:
+            g.alloc_root /= s
+            g.alloc_stem /= s
+            g.alloc_leaf /= s
+        g.provenance = f"env:{prefix}"
+        return g
+
+    def reflectance(self, bands):
+        """reflectance_from_genes (genes.py:114-120) on `bands`."""
+        return np.clip(1.0 - sp.absorbance_from_peaks(bands, self.peaks), 0.0, 1.0)
+
+
+def genes_from_env(bands, n_species, species_modes=None):
+    """The adapter's genes_list (adapter.py:84-138): one gene per species from QD_ECO_SPECIES_{i}_*, the template gene QD_ECO_GENE_*
+    where that one's reflectance is not finite; identities from the spread modes ('seed' -> tree, 'diffusion' -> grass; without
+    modes species 1 is the tree) unless QD_ECO_SPECIES_{i}_IDENTITY names one."""
+    out = []
+    for i in range(int(n_species)):
+        try:
+            g = Gene.from_env(f"QD_ECO_SPECIES_{i}_")
+            if not np.all(np.isfinite(g.reflectance(bands))):
+                raise ValueError("non-finite R_leaf")
+        except Exception:      # noqa: BLE001
+            g = Gene.from_env("QD_ECO_GENE_")
+        out.append(g)
+    modes = list(species_modes) if species_modes is not None else []
+    for i, g in enumerate(out):
+        if os.getenv(f"QD_ECO_SPECIES_{i}_IDENTITY"):
+            continue
+        mode = modes[i] if (i < len(modes) and modes[i] in ("seed", "diffusion")) else ("seed" if i == 1 else "diffusion")
+        g.identity = "tree" if mode == "seed" else "grass"
+    return out
+
+
+def genes_document(genes, bands, w_b, species_weights, day_value=None):
+    """The schema-3 document of save_genes_json (adapter.py:300-346)."""
+    table = []
+    for i, g in enumerate(genes):
+        table.append({
+            "index": i, "identity": g.identity, "provenance": g.provenance, "alloc_root": float(g.alloc_root),
+            "alloc_stem": float(g.alloc_stem), "alloc_leaf": float(g.alloc_leaf), "leaf_area_per_energy": float(g.leaf_area_per_energy),
+            "drought_tolerance": float(g.drought_tolerance), "gdd_germinate": float(g.gdd_germinate),
+            "lifespan_days": int(g.lifespan_days), "peaks_model": "gaussian",
+            "peaks": [{"center_nm": float(c), "sigma_nm": float(w), "variance_nm2": float(float(w) * float(w)), "height": float(h)}
+                      for (c, w, h) in g.peaks]})
+    doc = {"schema_version": 3, "source": "PyGCM.EcologyAdapter.save_genes_json",
+           "day": float(day_value) if day_value is not None else None,
+           "bands": {"nbands": int(bands.nbands), "band_weights": [float(x) for x in np.asarray(w_b, dtype=float).tolist()]},
+           "genes": table}
+    weights = [float(x) for x in np.asarray(species_weights, dtype=float).tolist()] if species_weights is not None else []
+    if weights:
+        doc["species_weights"] = weights
+    return doc
+
+
+def genes_from_document(doc):
+    """The gene table of load_genes_json (adapter.py:370-401): sigma_nm where it is positive, else sqrt(max(0, variance_nm2));
+    allocations normalised; a peak that does not parse is dropped."""
+    out = []
+    for rec in doc.get("genes", []):
+        peaks = []
+        for pk in rec.get("peaks", []) or []:
+            try:
+                sigma = float(pk.get("sigma_nm", 0.0))
+                if sigma <= 0 and "variance_nm2" in pk:
+                    sigma = float(np.sqrt(max(0.0, float(pk.get("variance_nm2", 0.0)))))
+                peaks.append((float(pk.get("center_nm", 0.0)), sigma, float(pk.get("height", 0.0))))
+            except Exception:      # noqa: BLE001
+                continue
+        g = Gene(identity=str(rec.get("identity", "sp")), alloc_root=float(rec.get("alloc_root", 0.3)),
+                 alloc_stem=float(rec.get("alloc_stem", 0.2)), alloc_leaf=float(rec.get("alloc_leaf", 0.5)),
+                 leaf_area_per_energy=float(rec.get("leaf_area_per_energy", 2.0e-3)), peaks=peaks,
+                 drought_tolerance=float(rec.get("drought_tolerance", 0.3)), gdd_germinate=float(rec.get("gdd_germinate", 80.0)),
+                 lifespan_days=int(rec.get("lifespan_days", 365)), provenance="autosave:genes_json")
+        s = g.alloc_root + g.alloc_stem + g.alloc_leaf
+        if s > 0:
+            g.alloc_root /= s
+            g.alloc_stem /= s
+            g.alloc_leaf /= s
+        out.append(g)
+    return out
+
+
+def persist_level(env=None):
+    """QD_ECO_PERSIST (default 0): 1 writes and reads ecology.nc and genes.json with the reference's variable set; 2 adds the qd_*
+    extension variables, with which the ecology lanes resume bit for bit.  A value that does not parse counts as 0."""
+    env = os.environ if env is None else env
+    try:
+        return max(0, min(2, int(env.get("QD_ECO_PERSIST", "0"))))
+    except ValueError:
+        return 0
+
+
+def restore_weights(w):
+    """The species weights load_autosave leaves (adapter.py:748-750): clipped at 0 and divided by their sum -- in the dtype they
+    arrive in, float32 from a NetCDF file -- or uniform float64 when the sum is 0."""
+    w = np.clip(np.asarray(w), 0.0, None)
+    ssum = float(np.sum(w))
+    return (w / ssum) if ssum > 0 else np.full((int(w.size),), 1.0 / float(max(int(w.size), 1)), dtype=float)
+
+
+def restore_layers(lai, weights, n_layers, lai_max):
+    """The host form of qd_eco_state_restore (adapter.py:744-756), for a population whose stack lives on the host: NumPy keeps the
+    dtype of `lai` through the clip, the division and the product; the store into the float64 stack widens."""
+    K = max(1, int(n_layers))
+    L = np.clip(lai, 0.0, lai_max)
+    out = np.zeros((len(weights), K) + L.shape, dtype=float)
+    for s in range(len(weights)):
+        for k in range(K):
+            out[s, k] = float(weights[s]) * (L / float(K))
+    return out
+
+
+# the [lat, lon] planes among the qd_* variables, in the order they are put back (ECO_LAI behind the stack's plane sum: after a
+# firing of the individuals' step the map is summed layer by layer, which the plane-after-plane sum does not reproduce in the last bit)
+EXT_PLANES = (("qd_LAI", "ECO_LAI"), ("qd_age_days", "ECO_AGE"), ("qd_seed_bank", "ECO_SEEDBANK"), ("qd_E_day", "ECO_EDAY"))
+
+
+@dataclass
 class AdapterConfig:
     substep_every_nphys: int = 1
     lai_albedo_weight: float = 1.0
@@ -572,6 +743,8 @@ class EcologyAdapter:
         self.configure()
         self._count = 0
         self.pop = None
+        self._diag = _envi("QD_ECO_DIAG", 1) == 1
+        self._genes = None                 # the host gene table, built when genes.json is first written or read
         if not self.params.use_lai:        # M1 branch (adapter.py:79-80,162-166): no population, scalar leaf alpha on land
             self.species_drought_tolerance = None
             return
@@ -580,6 +753,313 @@ class EcologyAdapter:
         R, tol = species_tables(self.bands, self.pop.Ns)
         self.pop.set_species_reflectance_bands(R)
         self.species_drought_tolerance = tol
+
+    # -- genes.json (adapter.py:284-426)
+    @property
+    def genes_list(self):
+        """The gene table (adapter.py:84-138), read from the QD_ECO_SPECIES_{i}_* / QD_ECO_GENE_* variables on first use.  The
+        identities follow the spread modes of the daily lane; without one they are drawn as the reference's population draws them."""
+        if self._genes is None:
+            n = self.pop.Ns if self.pop is not None else 1
+            daily = getattr(self.pop, "daily", None) if self.pop is not None else None
+            if daily is not None:
+                modes = daily.species_modes
+            elif self.pop is not None:
+                modes = species_modes_from_env(n, self.pop.species_weights, bool(os.getenv("QD_ECO_SPECIES_WEIGHTS", "").strip()))
+            else:
+                modes = None
+            self._genes = genes_from_env(self.bands, n, modes)
+        return self._genes
+
+    @genes_list.setter
+    def genes_list(self, genes):
+        self._genes = list(genes)
+
+    def save_genes_json(self, path, day_value=None):
+        try:
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        except Exception:      # noqa: BLE001
+            pass
+        try:
+            try:
+                weights = np.asarray(getattr(self.pop, "species_weights", []), dtype=float)
+            except Exception:      # noqa: BLE001
+                weights = None
+            doc = genes_document(self.genes_list, self.bands, self.w_b, weights, day_value)
+            with open(path, "w", encoding="utf-8") as f:
+                json.dump(doc, f, ensure_ascii=False, indent=2)
+            if self._diag:
+                print(f"[Ecology] Genes autosave written: {path} (Ns={len(doc['genes'])})")
+            return True
+        except Exception as e:      # noqa: BLE001
+            if self._diag:
+                print(f"[Ecology] Genes autosave save failed: {e}")
+            return False
+
+    def load_genes_json(self, path, *, on_mismatch="keep"):
+        try:
+            with open(path, "r", encoding="utf-8") as f:
+                doc = json.load(f)
+        except Exception as e:      # noqa: BLE001
+            if self._diag:
+                print(f"[Ecology] Genes autosave load failed: {e}")
+            return False
+        try:
+            genes_in = genes_from_document(doc)
+            if len(genes_in) == 0:
+                if self._diag:
+                    print("[Ecology] Genes autosave contains no genes; keeping current.")
+                return False
+            self.genes_list = genes_in
+            try:
+                R = np.stack([g.reflectance(self.bands) for g in genes_in], axis=0)
+                if self.pop is not None:
+                    self.pop.set_species_reflectance_bands(R)
+            except Exception as e:      # noqa: BLE001
+                if self._diag:
+                    print(f"[Ecology] Genes reflectance rebuild failed: {e}")
+            if self._diag:
+                print(f"[Ecology] Genes autosave loaded: Ns={len(genes_in)} (band nb={self.bands.nbands})")
+            return True
+        except Exception as e:      # noqa: BLE001
+            if self._diag:
+                print(f"[Ecology] Genes autosave parse failed: {e}")
+            return False
+
+    # -- ecology.nc (adapter.py:574-777)
+    @property
+    def lai_max(self):
+        daily = getattr(self.pop, "daily", None)
+        return float(daily.params.lai_max) if daily is not None else _envf_any("QD_ECO_LAI_MAX", 5.0)
+
+    def _extension_variables(self, indiv=None):
+        """The qd_* variables of QD_ECO_PERSIST=2, all f8, read through the getters: -> (dims, variables)."""
+        pop, d = self.pop, self._dev
+        stack = np.asarray(pop.LAI_layers_SK, dtype=np.float64)
+        dims = {"layer": int(stack.shape[1]), "qd_clock": 3}
+        v = {"qd_LAI_layers_SK": ("f8", ("species", "layer", "lat", "lon"), stack)}
+        for name, fid in EXT_PLANES:
+            d._host.pop(fid, None)
+            v[name] = ("f8", ("lat", "lon"), d.get(fid).copy())
+        v["qd_species_weights"] = ("f8", ("species",), np.asarray(pop.species_weights, dtype=np.float64))
+        v["qd_accum_day"] = ("f8", (), float(pop.daily.accum_day) if pop.daily is not None else 0.0)
+        st = pop.state()
+        v["qd_eco_clock"] = ("f8", ("qd_clock",), np.array([st["hours"], st["next_recompute_hours"], float(st["step_count"])]))
+        if indiv is not None and indiv.n_indiv > 0:
+            E, S = indiv._pull()
+            dims["qd_indiv"] = int(indiv.n_indiv)
+            v["qd_indiv_E_day"] = ("f8", ("qd_indiv",), E)
+            v["qd_indiv_stress_days"] = ("f8", ("qd_indiv",), S)
+        return dims, v
+
+    def save_autosave(self, path_npz, day_value=None, *, extended=None, indiv=None):
+        """adapter.py:574-710: `.nc` -> the reference's NetCDF layout through ncio.write_nc, anything else -> its NPZ; written to
+        .<name>.tmp<ext> and moved onto the target, then copied to <name>_<UTC stamp><ext>, the copies pruned by mtime to
+        QD_ECO_AUTOSAVE_KEEP (default 4), genes.json written beside it.  LAI is ECO_LAI.  extended (None = QD_ECO_PERSIST == 2)
+        adds the qd_* variables to a `.nc` file; indiv names the IndividualPool whose buffers go with them."""
+        try:
+            out_dir = os.path.dirname(path_npz) or "."
+            name, ext = os.path.splitext(os.path.basename(path_npz))
+            os.makedirs(out_dir, exist_ok=True)
+            ts = time.strftime("%Y%m%dT%H%M%SZ", time.gmtime())
+            backup_path = os.path.join(out_dir, f"{name}_{ts}{ext}")
+            tmp_path = os.path.join(out_dir, f".{name}.tmp{ext}")
+            pop = self.pop
+            LAI = species_w = R = None
+            if pop is not None:
+                LAI = pop.total_LAI()
+                species_w = np.asarray(pop.species_weights, dtype=float)
+                if pop._species_R_leaf is not None:
+                    R = np.asarray(pop._species_R_leaf, dtype=float)
+            if ext.lower() == ".nc":
+                g = self.grid
+                dims = {"lat": g.n_lat, "lon": g.n_lon}
+                if species_w is not None:
+                    dims["species"] = int(species_w.size)
+                dims["band"] = int(self.bands.nbands)
+                v = {"lat": ("f4", ("lat",), np.asarray(g.lat, np.float32)), "lon": ("f4", ("lon",), np.asarray(g.lon, np.float32))}
+                if LAI is not None:
+                    v["LAI"] = ("f4", ("lat", "lon"), np.asarray(LAI, dtype=np.float32))
+                if species_w is not None:
+                    v["species_weights"] = ("f4", ("species",), species_w.astype(np.float32))
+                v["bands_lambda_centers"] = ("f4", ("band",), np.asarray(self.bands.lambda_centers, dtype=np.float32))
+                v["bands_delta_lambda"] = ("f4", ("band",), np.asarray(self.bands.delta_lambda, dtype=np.float32))
+                v["w_b"] = ("f4", ("band",), np.asarray(self.w_b, dtype=np.float32))
+                if R is not None and species_w is not None:
+                    v["R_species_nb"] = ("f4", ("species", "band"), R.astype(np.float32))
+                if day_value is not None:
+                    v["day_value"] = ("f4", (), float(day_value))
+                if (persist_level() == 2 if extended is None else bool(extended)) and pop is not None:
+                    xd, xv = self._extension_variables(indiv)
+                    dims.update(xd)
+                    v.update(xv)
+                ncio.write_nc(tmp_path, dims, v, {"title": "Qingdai Ecology State", "schema_version": 1,
+                                                  "source": "EcologyAdapter.save_autosave"})
+                os.replace(tmp_path, path_npz)
+            else:
+                data = {"schema_version": np.int32(1)}
+                if LAI is not None:
+                    data["LAI"] = np.asarray(LAI, dtype=float)
+                if species_w is not None:
+                    data["species_weights"] = species_w
+                data["bands_lambda_centers"] = np.asarray(self.bands.lambda_centers, dtype=float)
+                data["bands_delta_lambda"] = np.asarray(self.bands.delta_lambda, dtype=float)
+                data["w_b"] = np.asarray(self.w_b, dtype=float)
+                if R is not None:
+                    data["R_species_nb"] = R
+                if day_value is not None:
+                    data["day_value"] = float(day_value)
+                with open(tmp_path, "wb") as f:
+                    np.savez(f, **data)
+                    f.flush()
+                    os.fsync(f.fileno())
+                os.replace(tmp_path, path_npz)
+            try:
+                shutil.copy2(path_npz, backup_path)
+            except Exception:      # noqa: BLE001
+                backup_path = None
+            try:
+                keep = int(os.getenv("QD_ECO_AUTOSAVE_KEEP", "4"))
+                files = sorted(glob.glob(os.path.join(out_dir, f"{name}_*{ext}")), key=os.path.getmtime, reverse=True)
+                for old in files[keep:]:
+                    try:
+                        os.remove(old)
+                    except Exception:      # noqa: BLE001
+                        pass
+            except Exception:      # noqa: BLE001
+                pass
+            try:
+                self.save_genes_json(os.path.join(out_dir, "genes.json"), day_value=day_value)
+            except Exception:      # noqa: BLE001
+                pass
+            if self._diag:
+                print(f"[Ecology] Autosave written: {path_npz}" + (f"; backup={backup_path}" if backup_path else ""))
+            return True
+        except Exception as e:      # noqa: BLE001
+            if self._diag:
+                print(f"[Ecology] Autosave+ load failed: {e}")          # (the reference's wording, adapter.py:709)
+            return False
+
+    def _read_autosave(self, path):
+        """-> {name: array} of an autosave file: the `.nc` branch through ncio.read_nc (arrays arrive float32, as netCDF4 hands them
+        to the reference), anything else through np.load."""
+        if os.path.splitext(path)[1].lower() == ".nc":
+            v, _ = ncio.read_nc(path)
+            return v
+        with np.load(path) as data:
+            return {k: data[k] for k in data.files}
+
+    def _restore_extended(self, v, indiv):
+        """The qd_* variables when every shape fits -> True; touches nothing otherwise."""
+        pop, d = self.pop, self._dev
+        need = ("qd_LAI_layers_SK", "qd_species_weights", "qd_accum_day", "qd_eco_clock") + tuple(n for n, _ in EXT_PLANES)
+        if any(n not in v for n in need):
+            return False
+        stack, w = np.ascontiguousarray(v["qd_LAI_layers_SK"], dtype=np.float64), np.asarray(v["qd_species_weights"], dtype=np.float64)
+        if stack.ndim != 4 or stack.shape[1:] != (pop.K,) + pop.shape or w.shape != (stack.shape[0],) or np.size(v["qd_eco_clock"]) != 3:
+            return False
+        if any(np.shape(v[n]) != pop.shape for n, _ in EXT_PLANES):
+            return False
+        with_indiv = indiv is not None and indiv.n_indiv > 0
+        if with_indiv != ("qd_indiv_E_day" in v) or (with_indiv and (np.shape(v["qd_indiv_E_day"]) != (indiv.n_indiv,) or
+                                                                     np.shape(v.get("qd_indiv_stress_days")) != (indiv.n_indiv,))):
+            return False
+        self._resize(int(w.size), w)
+        if pop.daily is not None:
+            d.eco_daily_set_layers(stack.reshape((-1,) + pop.shape))
+            pop.LAI_layers_SK = stack
+            pop.daily.accum_day = float(v["qd_accum_day"])
+            d._chk(d.lib.qd_eco_set_lai_layers(d.h, stack.ctypes.data, int(stack.shape[0] * stack.shape[1]), 0), "qd_eco_set_lai_layers")
+            d._host.pop("ECO_LAI", None)
+        else:
+            pop.push_layers(stack)
+        for name, fid in EXT_PLANES:
+            d.upload_now(fid, np.asarray(v[name], dtype=np.float64))
+        clock = (ctypes.c_double * 3)(*[float(x) for x in np.ravel(v["qd_eco_clock"])])
+        d._chk(d.lib.qd_eco_set_state(d.h, clock), "qd_eco_set_state")
+        if with_indiv:
+            indiv.reset(np.asarray(v["qd_indiv_E_day"], dtype=np.float64), np.asarray(v["qd_indiv_stress_days"], dtype=np.float64))
+        return True
+
+    def _resize(self, n_species, weights):
+        """Give the population the file's species count and weights.  A daily lane is configured again for them -- the reference reads
+        pop.species_weights in every step_daily, the device holds its own copy -- with ECO_AGE and ECO_SEEDBANK put back behind the
+        configure; its resident stack is left for the caller to fill."""
+        pop, d = self.pop, self._dev
+        changed = int(n_species) != pop.Ns
+        if pop.daily is not None:
+            age, bank = pop.age_days, pop.seed_bank
+        pop.Ns = int(n_species)
+        pop.species_weights = weights
+        if pop.daily is not None:
+            if changed:
+                pop.daily.resize(pop.Ns, stack=False)
+            else:
+                pop.daily.configure(stack=False)
+            d.upload_now("ECO_AGE", age)
+            d.upload_now("ECO_SEEDBANK", bank)
+
+    def load_autosave(self, path_npz, *, on_mismatch="fallback", indiv=None, extended=None):
+        """adapter.py:712-777 with the restore on the device (qd_eco_state_restore): LAI and species_weights rebuild the stack by
+        the reference's rule, in the precision the file's arrays arrive in; bands and R_species_nb are taken when their band count
+        is the run's.  The qd_* variables of QD_ECO_PERSIST=2, when present and fitting, win over that rule (extended=False ignores
+        them).  A file whose species count differs from a run with the individuals' daily step raises (the pool was sampled for the
+        run's species), and so does a latitude-band handle."""
+        pop = self.pop
+        if pop is None:
+            return False
+        try:
+            v = self._read_autosave(path_npz)
+            LAI, w = v.get("LAI"), v.get("species_weights")
+            if LAI is None or np.ndim(LAI) != 2 or w is None or np.ndim(w) != 1:
+                if self._diag:
+                    print("[Ecology] Autosave+ malformed: require LAI (2D) and species_weights (1D).")
+                return False
+            LAI, w = np.asarray(LAI), np.asarray(w)
+            if LAI.shape != pop.shape:
+                raise ValueError(f"LAI is {LAI.shape}, the grid is {pop.shape}")
+        except Exception as e:      # noqa: BLE001
+            if self._diag:
+                print(f"[Ecology] Autosave+ load failed: {e}")
+            return False
+        if getattr(pop, "indiv_daily", None) is not None and int(w.size) != pop.Ns:
+            raise ValueError(f"the file holds {int(w.size)} species, the run {pop.Ns}, and the individuals of QD_ECO_INDIV_DAILY=1 were "
+                             "sampled for the run's; starting fresh")
+        try:
+            has_ext = (extended is None or bool(extended)) and any(k.startswith("qd_") for k in v)
+            exact = has_ext and self._restore_extended(v, indiv)
+            if not exact:
+                if has_ext and self._diag:
+                    print("[Ecology] Autosave+: the qd_* extension variables do not fit this run -- restored by the reference rule.")
+                if LAI.dtype != np.float32:                                 # float32 stays float32 (NumPy's rule); the rest is float64
+                    LAI = LAI.astype(np.float64)
+                weights = restore_weights(w)
+                self._resize(int(weights.size), weights)
+                self._dev.eco_state_restore(LAI, np.asarray(weights, dtype=np.float64), pop.K, self.lai_max)
+                if pop.daily is not None:
+                    pop._layers_at = None                                   # the resident stack is the truth: downloaded on the next read
+                else:
+                    pop.LAI_layers_SK = restore_layers(LAI, weights, pop.K, self.lai_max)
+            centers, R = v.get("bands_lambda_centers"), v.get("R_species_nb")
+            ok_adv = (centers is not None and len(centers) == self.bands.nbands and R is not None and np.ndim(R) == 2 and
+                      R.shape[1] == self.bands.nbands)
+            if ok_adv:
+                pop.set_species_reflectance_bands(np.asarray(R, dtype=float))
+            elif self._diag and on_mismatch != "ignore":
+                print("[Ecology] Autosave+: advanced fields (bands/R_species) mismatched – restored base LAI/weights only.")
+            if self._diag:
+                s = pop.summary()
+                print(f"[Ecology] Autosave+ loaded: LAI(min/mean/max)={s['LAI_min']:.2f}/{s['LAI_mean']:.2f}/{s['LAI_max']:.2f}; "
+                      f"S={pop.Ns}, K={pop.K}, advanced={'OK' if ok_adv else 'NO'}")
+                if exact:
+                    print("[Ecology] Autosave+: exact resume from the qd_* extension variables.")
+            return True
+        except QdError:
+            raise
+        except Exception as e:      # noqa: BLE001
+            if self._diag:
+                print(f"[Ecology] Autosave+ load failed: {e}")
+            return False
 
     def configure(self):
         self._dev._chk(self._dev.lib.qd_eco_configure(self._dev.h, ctypes.byref(self.params), ctypes.sizeof(self.params)),

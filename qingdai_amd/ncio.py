@@ -101,7 +101,7 @@ def read_nc_full(path):
         for d, n in ds.dimensions.items():
             dims[d] = int(n) if n is not None else 0
         for name, var in ds.variables.items():
-            a = np.array(var[:]) if var.shape else np.array(var.getValue())
+            a = np.array(var[:]) if var.shape else np.array(var.data).reshape(())      # (getValue() would widen a scalar to f8)
             a = a.astype(a.dtype.newbyteorder("="))
             out[name] = (a.dtype.str.lstrip("<>=|"), tuple(var.dimensions), a)
         for k, val in ds._attributes.items():
