@@ -294,7 +294,8 @@ int qd_phyto_daily_insolation(qd_handle h, const double* star_row, double* insA,
  * (qd_eco_daily_set_layers / _get_layers); ECO_AGE, ECO_SEEDBANK and ECO_GATE are ordinary fields.  A firing leaves the canopy
  * state as qd_eco_set_lai_layers(h, layers, n, 0) does (snapshot and recompute clock untouched) and appends one record of
  * QD_ECO_DAILY_LOG_W = 4 doubles to a device log: {firings so far, LAI_min, LAI_mean, LAI_max} over land (summary(),
- * population.py:947-957; zeros without land).  Mutation, genes and the individuals' daily step are not part of it. */
+ * population.py:947-957; zeros without land).  The individuals' daily step runs behind it once configured (below); a speciation
+ * event is qd_eco_daily_speciate; the gene table and the mutation's draws stay on the host. */
 #define QD_ECO_DAILY_LOG_W 4
 #define QD_ECO_DAILY_MAX_K 8
 typedef struct qd_eco_daily_params {
@@ -324,6 +325,19 @@ int qd_eco_daily_step(qd_handle h, const double* soil_index);
 int qd_eco_daily_schedule(qd_handle h, int n, const int32_t* fire);   /* the next qd_step_n span: firings at the top of each step */
 int qd_eco_daily_log(qd_handle h, double* out, int max, int* n);      /* drains the log: *n records of 4 doubles */
 int qd_eco_daily_state(qd_handle h, int64_t* n_firings);              /* firings since the configure */
+/* one speciation event on the resident stack (PopulationManager.add_species_from_parent, population.py:361-387): a new
+ * [(n_species + 1) * K] stack is allocated, one pass over the cells fills it from the old one -- transfer = f * x_p with
+ * f = clip(frac, 0, 0.5) and p = clip(parent, 0, n_species - 1), the parent plane x_p - transfer, the new (last) species transfer,
+ * every plane clipped to [0, lai_max] (NaN passes), all bit for bit -- and the stacks are swapped.  The same pass writes ECO_LAI
+ * (species summed within a layer, then the layers) and the per-species land sums, from which one workgroup derives
+ * species_weights (totals / their sum clipped to [0, 1]; 1 / (n_species + 1) when the sum is <= 0) -> weights_out
+ * [n_species + 1] and the lane's germination weights w / (sum(w) + 1e-12).  The weights differ from NumPy's by the blocked order
+ * of the land sums.  The mode table grows by the mode the reference gives an index its list does not hold (seed for index 1,
+ * else diffusion); n_species grows by one.  ECO_AGE, ECO_SEEDBANK, ECO_EDAY, ECO_GATE, the firing count, the log and a pending
+ * schedule are untouched; the canopy state is left as by qd_eco_set_lai_layers(h, stack, n, 0).  Refused: latitude bands, no
+ * qd_eco_daily_configure, n_species + 1 > 64, a configured qd_indiv_daily (its pool was sampled for the old species), frac <= 0
+ * (the reference adds no species then). */
+int qd_eco_daily_speciate(qd_handle h, int parent, double frac, double* weights_out);
 
 /* ---- restore of the vegetation state from an ecology autosave (EcologyAdapter.load_autosave, pygcm/ecology/adapter.py:742-757),
  * whole-globe handles ---------------------------------------------------------------------------------------------------------

@@ -46,7 +46,7 @@ SYMBOLS = [
     "qd_phyto_daily_configure", "qd_phyto_daily", "qd_phyto_daily_schedule", "qd_phyto_daily_log", "qd_phyto_daily_download_bands",
     "qd_phyto_daily_state", "qd_phyto_daily_insolation",
     "qd_eco_daily_configure", "qd_eco_daily_set_layers", "qd_eco_daily_get_layers", "qd_eco_daily_step", "qd_eco_daily_schedule",
-    "qd_eco_daily_log", "qd_eco_daily_state",
+    "qd_eco_daily_log", "qd_eco_daily_state", "qd_eco_daily_speciate",
     "qd_eco_state_restore",
     "qd_indiv_daily_configure", "qd_indiv_daily_step", "qd_indiv_daily_log", "qd_indiv_daily_weights", "qd_indiv_daily_state",
     "qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download",
@@ -253,6 +253,7 @@ def load():
     lib.qd_eco_daily_schedule.argtypes = [vp, i32, ip]
     lib.qd_eco_daily_log.argtypes = [vp, dp, i32, ip]
     lib.qd_eco_daily_state.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.qd_eco_daily_speciate.argtypes = [vp, i32, ctypes.c_double, dp]
     lib.qd_indiv_daily_configure.argtypes = [vp, ctypes.POINTER(qd_indiv_daily_params), sz, ip, ip]
     lib.qd_indiv_daily_step.argtypes = [vp, vp]
     lib.qd_indiv_daily_log.argtypes = [vp, dp, i32, ip]

@@ -278,6 +278,19 @@ bool qd_eco_daily_stack(const qd_ctx* c, const double** L, int* n_species, int* 
 double* qd_eco_daily_share_plane(qd_ctx* c) { return c->edaily ? c->edaily->share : nullptr; }
 double* qd_eco_daily_weights_dev(qd_ctx* c) { return c->edaily ? c->edaily->w : nullptr; }
 double qd_eco_daily_soil_cap(const qd_ctx* c) { return c->edaily ? c->edaily->p.soil_cap : 50.0; }
+double qd_eco_daily_lai_max(const qd_ctx* c) { return c->edaily ? c->edaily->p.lai_max : 5.0; }
+
+// qd_eco_speciate.hip: the stack grown by one species.  Takes L1 [(S + 1) * K][cells] and w1 [S + 1] and frees the old ones (the
+// caller has synchronised the stream).  The new index gets the mode population.py:511 gives an index the mode list does not hold
+// (the reference never extends species_modes).  Age, seed bank, E_day, gate, firing count, log and schedule stay.
+void qd_eco_daily_adopt(qd_ctx* c, double* L1, double* w1) {
+    QdEcoDaily* d = c->edaily;
+    hipFree(d->L); hipFree(d->w);
+    d->L = L1; d->w = w1;
+    d->mode.push_back(d->p.n_species == 1 ? 1 : 0);
+    d->p.n_species += 1;
+    d->planes = d->p.n_species * d->p.n_layers;
+}
 
 extern "C" int qd_eco_daily_configure(qd_handle c, const qd_eco_daily_params* p, size_t sz, const int32_t* mode, const double* w) {
     if (!c || !p || !mode || !w) return -1;

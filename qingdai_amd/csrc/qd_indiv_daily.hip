@@ -286,6 +286,10 @@ k_ind_weights(const double* __restrict__ partial, int nblk, int S, double* __res
     }
 }
 
+void qd_species_weights_launch(qd_ctx* c, const double* partial, int nblk, int S, double* wout, double* wnorm) {
+    hipLaunchKernelGGL(k_ind_weights, dim3(1), dim3(QD_BLOCK), 0, c->stream, partial, nblk, S, wout, wnorm);
+}
+
 // ------------------------------------------------------------------ 6: the individuals' buffers
 __global__ void __launch_bounds__(QD_BLOCK)
 k_ind_reset(QdIDArgs A, const double* __restrict__ soil_in) {
@@ -421,8 +425,7 @@ int qd_indiv_daily_step_impl(qd_ctx* c, const double* soil_dev) {
     if (S <= 8) hipLaunchKernelGGL(k_ind_stack<8>, grid, block, 0, c->stream, A);
     else if (S <= 24) hipLaunchKernelGGL(k_ind_stack<24>, grid, block, 0, c->stream, A);
     else hipLaunchKernelGGL(k_ind_stack<QD_MAX_SPECIES>, grid, block, 0, c->stream, A);
-    hipLaunchKernelGGL(k_ind_weights, dim3(1), block, 0, c->stream, (const double*)d->partial.p, (int)(grid.x * grid.y), S, d->wout,
-                       qd_eco_daily_weights_dev(c));
+    qd_species_weights_launch(c, d->partial.p, (int)(grid.x * grid.y), S, d->wout, qd_eco_daily_weights_dev(c));
     hipLaunchKernelGGL(k_ind_reset, flat(A.n_indiv), block, 0, c->stream, A, soil_dev);
     // the canopy state qd_eco_daily_step_impl leaves: new layers, snapshot and recompute clock untouched
     c->eco.have_lai = 1; c->eco.lai_version++;

@@ -488,9 +488,13 @@ bool qd_eco_daily_stack(const qd_ctx* c, const double** L, int* n_species, int* 
 double* qd_eco_daily_share_plane(qd_ctx* c);          // [cells] free between two firings (nullptr: not configured)
 double* qd_eco_daily_weights_dev(qd_ctx* c);          // [S] the normalised germination weights on the device
 double qd_eco_daily_soil_cap(const qd_ctx* c);
+double qd_eco_daily_lai_max(const qd_ctx* c);
+void qd_eco_daily_adopt(qd_ctx* c, double* L1, double* w1);   // qd_eco_speciate.hip hands over the stack grown by one species
 struct QdSpanLane* qd_indiv_daily_span_begin(qd_ctx* c, const struct QdSpanLane* daily);      // qd_indiv_daily.hip
 int  qd_indiv_daily_step_impl(qd_ctx* c, const double* soil_dev);
 void qd_indiv_daily_release(qd_ctx* c);
+// k_ind_weights on the handle's stream: per-species land partials [S][nblk] -> species_weights wout [S], w / (sum(w) + 1e-12) wnorm [S]
+void qd_species_weights_launch(qd_ctx* c, const double* partial, int nblk, int S, double* wout, double* wnorm);
 void qd_eco_div_release(qd_ctx* c);                                              // qd_eco_div.hip
 void qd_truecolor_release(qd_ctx* c);                                            // qd_truecolor.hip
 void qd_stateframe_release(qd_ctx* c);                                           // qd_stateframe.hip

@@ -316,6 +316,15 @@ class Device:
         self._chk(self.lib.qd_eco_daily_state(self.h, ctypes.byref(n)), "qd_eco_daily_state")
         return int(n.value)
 
+    def eco_daily_speciate(self, parent, frac, n_species):
+        """One speciation event on the resident stack of n_species species (qd_eco_speciate.hip) -> species_weights [n_species + 1]."""
+        self.flush()
+        out = np.empty(int(n_species) + 1, dtype=np.float64)
+        self._chk(self.lib.qd_eco_daily_speciate(self.h, int(parent), float(frac), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+                  "qd_eco_daily_speciate")
+        self._host.pop("ECO_LAI", None)
+        return out
+
     # ---- restore from an ecology autosave (qd_eco_state.hip)
     def eco_state_restore(self, lai, weights, n_layers, lai_max):
         """adapter.py:742-757 on the device: lai [lat, lon] float32 (the arithmetic is then float32, as the reference's NetCDF

@@ -32,7 +32,18 @@ Daily vegetation dynamics (QD_ECO_DAILY=1, default 0, with QD_ECO_ENABLE=1 and n
 growth, senescence, layered allocation, per-species spread, seed bank, age -- runs inside the resident loop on the steps the
 reference's day accumulator names (qd_step_n bit9, at the top of the step; qingdai_amd/ecology.py PopulationDaily), spans are no
 longer cut at day boundaries, and each chunk's `[Ecology] daily:` lines are printed after it from the device log (QD_ECO_DIAG=1).
-QD_ECO_MUT_RATE > 0 is refused with it; genes export stays out.
+QD_ECO_MUT_RATE > 0 is refused with it unless QD_ECO_SPECIATION=1 is set.
+Speciation (QD_ECO_SPECIATION=1, default 0; needs QD_ECO_DAILY=1 and no daily_hook; adapter.py:437-515, run_simulation.py:1847-1861):
+behind every daily firing the reference draws rand() against QD_ECO_MUT_RATE and, on a hit below QD_ECO_SPECIES_MAX, picks a parent
+by species weight, splits QD_ECO_MUT_EPS of its LAI into a new species, mutates its genes and rebuilds the reflectance table --
+inside the step, before the rest of it.  Here `speciation_due` walks the firings of the steps ahead, draws each firing's rand() once
+(kept by firing number, in firing order, no further than the first hit), and a chunk ends with the step BEFORE a hit's step; that
+step's firings then run through the lane's class seam (qd_eco_daily_step on the resident soil water), each followed by
+ecology.Speciation.event -- the split on the resident stack (qd_eco_daily_speciate), Gene.mutated, the table, the reference's
+`[Ecology] mutation:` lines -- and, under QD_ECO_BANDS_COUPLE=1, the banded alpha; the step itself runs with those firings struck
+out of the lane's schedule.  QD_ECO_GENES_EXPORT=1 writes <QD_OUTPUT_DIR>/genes_day_*.json for every firing after its chunk (weights
+and genes are constant within one), as often as the reference prints its line.  Refused at start-up: QD_ECO_INDIV_DAILY=1 (the pool
+was sampled for the run's species), QD_ECO_MUT_EPS <= 0 (the reference then truncates its gene table), QD_ECO_SPECIES_MAX > 64.
 Saving and resuming the vegetation state (QD_ECO_PERSIST, default 0; run_simulation.py:248-305, 1464-1488, 1566-1590,
 pygcm/ecology/adapter.py:284-426, 574-777): at 1 every autosave writes data/ecology.nc (QD_ECO_AUTOSAVE_PATH when that ends in .nc;
 the reference's variable set, a time-stamped copy, QD_ECO_AUTOSAVE_KEEP of them kept) behind data/atmosphere.nc and data/genes.json
@@ -88,7 +99,7 @@ isr_components_day_*.png, each with a .json of titles, units, colormaps, levels 
 true-colour frame.  A banded alpha the run has not computed yet is computed for the panel alone, as the reference does
 (run_simulation.py:2458-2466); the resident map is left as it is.  A figure that fails prints one note ([PlanktonViz] / [EcologyViz]
 under their diag switches) and the run goes on.
-Not carried over (out of the hot path): genes export (QD_ECO_GENES_EXPORT), plankton.json, plot_ocean (defined in the reference, never
+Not carried over (out of the hot path): plankton.json, plot_ocean (defined in the reference, never
 called by its loop) and the diversity annotation of the ecology panel (run_simulation.py:1025-1052: it reads a name that is not
 in scope there and is never drawn).
 
@@ -183,11 +194,14 @@ def load_ocean(path):
 # ------------------------------------------------------------------------------------- simulation
 class Simulation:
     """The reference driver's state + loop, device resident."""
+    speciation = None                      # a Speciation under QD_ECO_SPECIATION=1
+    genes_export = False                   # QD_ECO_GENES_EXPORT=1 with it
 
     def __init__(self, n_lat=None, n_lon=None, params: QdParams | None = None, use_ocean=None, quiet=False, device=0,
-                 ecology=None, individuals=None, daily_hook=None, phyto=None):
+                 ecology=None, individuals=None, daily_hook=None, phyto=None, speciation_rng=None):
         """ecology / individuals: None = QD_ECO_ENABLE / QD_ECO_INDIV_ENABLE (both default 1, run_simulation.py:1324,1404).
         daily_hook(sim, soil_idx, glacier_mask): the host-side daily ecology, called at planet-day boundaries.
+        speciation_rng: the generator of QD_ECO_SPECIATION=1 (None = the numpy.random module, as in the reference).
         phyto: None = QD_PHYTO_ENABLE and QD_PHYTO_ADVECTION (both default 1, run_simulation.py:1347,1351)."""
         env = os.environ
         n_lat = int(n_lat if n_lat is not None else env.get("QD_N_LAT", "121"))   # run_simulation.py:1195 is 121x240
@@ -270,6 +284,16 @@ class Simulation:
             if not quiet:
                 print(f"[Ecology] daily step on the device: K={self.eco.pop.K}, Ns={self.eco.pop.Ns}, "
                       f"spread {'on' if self.eco_daily.params.spread else 'off'}")
+        # QD_ECO_SPECIATION=1: the reference's mutation draw behind every firing of that lane, the split on its resident stack
+        self.speciation = None
+        self.genes_export = False
+        if speciation_enabled(env, eco_daily=self.eco_daily is not None, daily_hook=daily_hook is not None):
+            from .ecology import Speciation
+            self.speciation = Speciation(rng=speciation_rng, env=env)
+            self.genes_export = int(env.get("QD_ECO_GENES_EXPORT", "0")) == 1
+            if not quiet:
+                print(f"[Ecology] speciation on the device: mut_rate={self.speciation.mut_rate:g}, mut_eps={self.speciation.mut_eps:g}, "
+                      f"species_max={self.speciation.species_max}, genes export {'on' if self.genes_export else 'off'}")
         # QD_ECO_INDIV_DAILY=1: IndividualPool.step_daily behind every firing of that lane
         self.indiv_daily = None
         if indiv_daily_enabled(env, eco_daily=self.eco_daily is not None, ecology=eco_on, population=eco_on and self.eco.pop is not None,
@@ -674,7 +698,72 @@ class Simulation:
             attempt("ISR", lambda: fg.write_isr(t_days, output_dir, echo=print)[0], "[ISRViz] figure skipped: {}")
         return done
 
+    # -- speciation (adapter.py:437-466 inside run_simulation.py:1786-1864)
+    def speciation_due(self, n_max):
+        """Walks the daily firings of the next n_max steps in firing order, one rand() per firing (kept by firing number, so a
+        second look never draws again), and stops drawing at the first hit -> the steps BEFORE the hit's step (the chunk that may
+        run with the lane; 0 when the very next step holds the hit), or None when none of them holds one or the switch is off."""
+        spec = self.speciation
+        if spec is None or n_max <= 0 or not spec.mut_rate > 0.0:
+            return None
+        from .ecology import daily_counts
+        fire, _ = daily_counts(self.eco_daily.accum_day, float(self.dt), int(n_max), self.eco_daily.day_seconds)
+        k = 0
+        for i, c in enumerate(fire.tolist()):
+            for _ in range(c):
+                k += 1
+                if spec.hit_ahead(k):
+                    return i
+        return None
+
+    def _speciation_step(self, energy_diag=False):
+        """The step that holds a hit: its firings are taken one by one through the lane's class seam (qd_eco_daily_step on the
+        resident soil water, what an in-span firing runs), each followed by the reference's draw and, on a hit, the event -- all
+        BEFORE the rest of the step, as in the reference, whose day-boundary block then refreshes the banded alpha
+        (run_simulation.py:1837-1846; here under QD_ECO_BANDS_COUPLE=1, on a hit).  The step then runs with these firings struck
+        out of the lane's schedule; the day accumulator advances as always."""
+        from .ecology import daily_counts, eco_daily_line
+        lane, spec = self.eco_daily, self.speciation
+        fire, _ = daily_counts(lane.accum_day, float(self.dt), 1, lane.day_seconds)
+        a = np.float64(lane.accum_day) + np.float64(self.dt)
+        t_i = float(self._span_times(1, advance=False)[0][0])
+        for _ in range(int(fire[0])):
+            a = a - np.float64(lane.day_seconds)
+            self.dev.eco_daily_step(None)
+            lane._fired(1)
+            for rec in self.dev.eco_daily_log():
+                if self.eco_diag:
+                    print(eco_daily_line(rec))
+            if spec.event(self.eco) is not None and self.eco.params.bands_couple:
+                self.eco.banded_alpha()
+            self._export_genes(t_i, float(a))
+        lane.struck = int(fire[0])
+        self._run_lanes(1, energy_diag)
+
+    def _export_genes(self, t_i, accum_after):
+        """QD_ECO_GENES_EXPORT=1: genes_day_*.json of one firing, named by (t_i - accum_after) / day (run_simulation.py:1847-1861:
+        twice under QD_ECO_BANDS_COUPLE=1, behind the banded update and again behind it, like the reference)."""
+        if not self.genes_export:
+            return
+        out = os.environ.get("QD_OUTPUT_DIR", "output")
+        day_value = float((t_i - accum_after) / self.day_seconds)
+        for _ in range(2 if self.eco.params.bands_couple else 1):
+            self.eco.export_genes(out, day_value)
+
     def _run_chunk(self, n, energy_diag=False):
+        """n steps; under QD_ECO_SPECIATION=1 cut so that a chunk ends with the step BEFORE one that holds a hit."""
+        while self.speciation is not None and n > 0:
+            k = self.speciation_due(n)
+            if k is None:
+                break
+            if k > 0:
+                self._run_lanes(k, energy_diag)
+            self._speciation_step(energy_diag)
+            n -= k + 1
+        if n > 0:
+            self._run_lanes(n, energy_diag)
+
+    def _run_lanes(self, n, energy_diag=False):
         origin = self._t_origin
         times, t_next = self._span_times(n)
         stars = self.forcing.star_table(times)
@@ -682,6 +771,7 @@ class Simulation:
         daily = self.phyto_daily
         eco_daily = self.eco_daily if self.daily_hook is None else None
         budget = getattr(self, "budget", None)
+        accum0, struck0 = (eco_daily.accum_day, eco_daily.struck) if eco_daily is not None else (0.0, 0)
         lanes = {}
         if budget is not None:
             budget.routed = routing is not None
@@ -703,9 +793,22 @@ class Simulation:
             budget.take(self.dev.budget_diag_log(), float(self.dt))       # the span's budget lines, oldest first
         if eco_daily is not None:
             from .ecology import eco_daily_line
-            for rec in self.dev.eco_daily_log():               # the span's firings, oldest first (adapter.py:434-436)
+            recs = self.dev.eco_daily_log()
+            for rec in recs:                                   # the span's firings, oldest first (adapter.py:434-436)
                 if self.eco_diag:
                     print(eco_daily_line(rec))
+            if self.speciation is not None and len(recs):      # none of them was a hit; weights and genes are the chunk's
+                self.speciation.passed(len(recs))
+                if self.genes_export:
+                    from .ecology import daily_counts
+                    fire, _ = daily_counts(accum0, float(self.dt), n, eco_daily.day_seconds)
+                    a = np.float64(accum0)
+                    for i in range(n):
+                        a = a + np.float64(self.dt)
+                        for q in range(int(fire[i])):
+                            a = a - np.float64(eco_daily.day_seconds)
+                            if not (i == 0 and q < struck0):
+                                self._export_genes(float(times[i]), float(a))
             if getattr(self, "indiv_daily", None) is not None:     # the reference's line per firing (individuals.py:358-361)
                 for line in self.indiv_daily.lines():
                     if self.eco_diag:
@@ -785,17 +888,49 @@ def hydro_env(env):
 
 
 def eco_daily_enabled(env):
-    """QD_ECO_DAILY (default 0): 1 runs the daily population step on the device.  Refuses QD_ECO_MUT_RATE > 0: the reference's
-    speciation draws from the global NumPy generator after every daily step, which the device step does not restate."""
+    """QD_ECO_DAILY (default 0): 1 runs the daily population step on the device.  Refuses QD_ECO_MUT_RATE > 0 without
+    QD_ECO_SPECIATION=1: the reference's speciation draws from the global NumPy generator after every daily step, which the device
+    step alone does not restate."""
     if int(env.get("QD_ECO_DAILY", "0")) != 1:
         return False
     try:
         mut = float(env.get("QD_ECO_MUT_RATE", "0.0"))
     except ValueError:
         mut = 0.0
-    if mut > 0.0:
+    if mut > 0.0 and not _speciation_switch(env):
         raise ValueError(f"QD_ECO_DAILY=1 does not support QD_ECO_MUT_RATE > 0 (got {mut:g}): stochastic speciation is host code "
                          "outside the device daily step; unset one of the two")
+    return True
+
+
+def _speciation_switch(env):
+    try:
+        return int(env.get("QD_ECO_SPECIATION", "0")) == 1
+    except ValueError:
+        return False
+
+
+def speciation_enabled(env, *, eco_daily, daily_hook):
+    """QD_ECO_SPECIATION (default 0): 1 runs the reference's speciation (adapter.py:437-515) behind the device daily vegetation
+    step: QD_ECO_MUT_RATE, QD_ECO_MUT_EPS, QD_ECO_SPECIES_MAX, QD_ECO_MUT_LAMBDA_DRIFT and QD_ECO_GENES_EXPORT as the reference
+    reads them.  Refused at start-up without what it stands on, and where the reference's behaviour is not restated."""
+    if not _speciation_switch(env):
+        return False
+    missing = [what for ok, what in ((eco_daily, "QD_ECO_DAILY=1 with QD_ECO_ENABLE=1 and a population"), (not daily_hook, "no daily_hook")) if not ok]
+    if missing:
+        raise ValueError("QD_ECO_SPECIATION=1 needs " + ", ".join(missing) + ": the event runs on the resident stack of the device "
+                         "daily vegetation step; set what is missing or unset QD_ECO_SPECIATION")
+    if int(env.get("QD_ECO_INDIV_DAILY", "0")) == 1:
+        raise ValueError("QD_ECO_SPECIATION=1 does not run with QD_ECO_INDIV_DAILY=1: the individuals were sampled for the run's "
+                         "species; unset one of the two")
+    from .ecology import Speciation
+    probe = Speciation(env=env)
+    if not probe.mut_eps > 0.0:
+        raise ValueError(f"QD_ECO_SPECIATION=1 needs QD_ECO_MUT_EPS > 0 (got {probe.mut_eps:g}): with nothing to split the reference "
+                         "adds no species and truncates its gene table (adapter.py:456-460), which is not restated")
+    if probe.species_max > 64:
+        raise ValueError(f"QD_ECO_SPECIATION=1 needs QD_ECO_SPECIES_MAX <= 64 (got {probe.species_max}): the resident stack holds at "
+                         "most 64 species")
     return True
 
 

@@ -21,8 +21,10 @@ the levels of the cell loop (`plan_levels`) and configures it, `IndividualPool.s
 (QD_ECO_INDIV_DAILY=1 in the driver).  The state survives a restart through the reference's files (adapter.py:284-426, 574-777;
 QD_ECO_PERSIST in the driver): `EcologyAdapter.save_autosave` / `load_autosave` write and read ecology.nc (or its NPZ form),
 `save_genes_json` / `load_genes_json` genes.json from a small host gene table (`Gene`), and the load rebuilds the LAI stack from the
-file's one plane on the device (qd_eco_state_restore).  Mutation is host code outside this package: `Simulation` hands `E_day` to a
-caller-supplied daily hook and takes the new LAI layers back.
+file's one plane on the device (qd_eco_state_restore).  Speciation (adapter.py:437-515; QD_ECO_SPECIATION=1 in the driver): `Speciation`
+holds the reference's draws and limits, `Gene.mutated` restates _mutate_genes draw for draw, and the split of the parent's LAI into
+the new species runs on the resident stack (`PopulationCanopy.add_species_from_parent`, qd_eco_daily_speciate);
+`EcologyAdapter.export_genes` writes the reference's genes_day_*.json.
 """
 from __future__ import annotations
 
@@ -166,6 +168,22 @@ class PopulationCanopy:
                 soil = np.full(self.shape, float(np.nanmean(soil)))
         self._dev.eco_daily_step(soil)
         self.daily._fired(1)
+
+    # -- one speciation event (population.py:361-387) on the resident stack
+    def add_species_from_parent(self, parent_idx, frac=0.02):
+        """Split clip(frac, 0, 0.5) of the parent's LAI into a new last species on the device (qd_eco_daily_speciate) and follow
+        it on the host: Ns, species_weights (recomputed from the land sums), the lane's parameters and mode list -- the new index
+        gets what population.py:511 gives an index the list does not hold -- and the host copy of the stack counts as stale.
+        Returns the index of the new species."""
+        if self.daily is None:
+            raise RuntimeError("add_species_from_parent needs the device daily step (PopulationDaily): the event runs on its resident stack")
+        w = self._dev.eco_daily_speciate(int(parent_idx), float(frac), self.Ns)
+        self.Ns += 1
+        self.species_weights = w
+        self.daily.params.n_species = self.Ns
+        self.daily.species_modes.append(new_species_mode(self.Ns - 1))
+        self._layers_at = None
+        return self.Ns - 1
 
     @property
     def age_days(self):
@@ -354,6 +372,11 @@ def species_modes_from_env(n_species, species_weights, weights_from_env):
     return modes
 
 
+def new_species_mode(index):
+    """The spread mode of a species index the mode list does not hold (population.py:511)."""
+    return "seed" if int(index) == 1 else "diffusion"
+
+
 def daily_counts(accum, dt, n, day):
     """The reference's day accumulator over n steps (run_simulation.py:1784-1789, float64): accum += dt; while accum >= day:
     accum -= day, one firing -> (firings per step [n] int32, the accumulator afterwards)."""
@@ -377,6 +400,8 @@ class PopulationDaily:
     parse fallbacks (LAIParams.from_env, QD_ECO_SPREAD_*, QD_ECO_REPRO_FRACTION, QD_ECO_SEED_*, QD_ECO_SEEDLING_LAI,
     QD_ECO_LAYER_UPFRAC, QD_ECO_SOIL_WATER_CAP), the per-species spread modes, and the span participant of Device.step_n: a day
     accumulator on the host names the firing steps, rolled back when the span does not run."""
+
+    struck = 0                             # firings of the next span's first step the host has already run through the class seam
 
     def __init__(self, pop, day_seconds=None, species_modes=None):
         self.pop, self.dev = pop, pop._dev
@@ -445,11 +470,13 @@ class PopulationDaily:
             pop.indiv_daily.configure()
 
     def resize(self, n_species, stack=True):
-        """An autosave file with another species count (adapter.py:745-752): the lane is configured again for it, with modes from
-        species_modes_from_env.  The caller has already given pop.Ns and pop.species_weights."""
-        self.params.n_species = int(n_species)
-        self.species_modes = species_modes_from_env(int(n_species), self.pop.species_weights,
-                                                    bool(os.getenv("QD_ECO_SPECIES_WEIGHTS", "").strip()))
+        """An autosave file with another species count (adapter.py:745-752): the lane is configured again for it.  The reference
+        keeps the mode list it drew for the run's own species and never extends it: an index beyond it spreads by population.py:511
+        (new_species_mode), which is also what a species born from a speciation event has -- so a run resumes with the modes it was
+        saved with.  The caller has already given pop.Ns and pop.species_weights."""
+        n = int(n_species)
+        self.params.n_species = n
+        self.species_modes = list(self.species_modes[:n]) + [new_species_mode(i) for i in range(len(self.species_modes), n)]
         self.configure(stack=stack)
 
     def _fired(self, n):
@@ -461,15 +488,20 @@ class PopulationDaily:
 
     # ---- span participant (Device.step_n)
     def span_clock(self):
-        return self.accum_day
+        return (self.accum_day, self.struck)
 
     def span_schedule(self, t0, dt, n):
         fire = self.schedule(dt, n)
+        if self.struck:                    # run by the host before this span: the accumulator moved as always, the lane stays idle
+            if self.struck > fire[0]:
+                raise ValueError(f"PopulationDaily: {self.struck} firings struck out of a step that has {int(fire[0])}")
+            fire[0] -= self.struck
+            self.struck = 0
         self.dev.eco_daily_schedule(fire)
         return int(fire.sum())
 
     def span_restore(self, clock):
-        self.accum_day = clock
+        self.accum_day, self.struck = clock
 
     def log(self):
         """Drain the device log -> list of summary() dicts, oldest first."""
@@ -601,6 +633,40 @@ class Gene:
         """reflectance_from_genes (genes.py:114-120) on `bands`."""
         return np.clip(1.0 - sp.absorbance_from_peaks(bands, self.peaks), 0.0, 1.0)
 
+    def mutated(self, rng, bands, w_b, drift=None):
+        """EcologyAdapter._mutate_genes (adapter.py:471-515), draw for draw from `rng` (None = the numpy.random module, the global
+        legacy generator the reference uses): three uniform(-0.05, 0.05) for the allocations, clipped to [0.05, 0.90] and
+        renormalised; per peak normal(0, 8), normal(0, 5), normal(0, 0.05) for centre, width and height with their clips; normal
+        draws for drought tolerance, GDD, lifespan (int(np.clip(...))) and leaf area (multiplicative); then every centre is
+        nudged by drift (None = QD_ECO_MUT_LAMBDA_DRIFT, 0.1; not a number: no nudge, like the reference's `except: pass`) towards
+        the weighted band centre.  Identity <parent>_mut, no provenance."""
+        rng = np.random if rng is None else rng
+        root = float(np.clip(self.alloc_root + rng.uniform(-0.05, 0.05), 0.05, 0.90))
+        stem = float(np.clip(self.alloc_stem + rng.uniform(-0.05, 0.05), 0.05, 0.90))
+        leaf = float(np.clip(self.alloc_leaf + rng.uniform(-0.05, 0.05), 0.05, 0.90))
+        tot = root + stem + leaf
+        peaks = []
+        for (c, w, h) in self.peaks:
+            c = float(np.clip(c + rng.normal(0.0, 8.0), 380.0, 780.0))
+            w = float(np.clip(w + rng.normal(0.0, 5.0), 10.0, 120.0))
+            h = float(np.clip(h + rng.normal(0.0, 0.05), 0.05, 0.98))
+            peaks.append((c, w, h))
+        g = Gene(identity=self.identity + "_mut", alloc_root=root / tot, alloc_stem=stem / tot, alloc_leaf=leaf / tot,
+                 leaf_area_per_energy=self.leaf_area_per_energy, peaks=peaks, drought_tolerance=self.drought_tolerance,
+                 gdd_germinate=self.gdd_germinate, lifespan_days=self.lifespan_days)
+        g.drought_tolerance = float(np.clip(g.drought_tolerance + rng.normal(0.0, 0.03), 0.05, 0.95))
+        g.gdd_germinate = float(np.clip(g.gdd_germinate + rng.normal(0.0, 5.0), 10.0, 500.0))
+        g.lifespan_days = int(np.clip(g.lifespan_days + rng.normal(0.0, 30.0), 30, 365 * 5))
+        g.leaf_area_per_energy = float(np.clip(g.leaf_area_per_energy * (1.0 + rng.normal(0.0, 0.1)), 1e-5, 5e-2))
+        try:
+            lam, wb = np.asarray(bands.lambda_centers, dtype=float), np.asarray(w_b, dtype=float)
+            lam_w = float(np.sum(lam * wb) / (np.sum(wb) + 1e-12))
+            alpha = float(os.getenv("QD_ECO_MUT_LAMBDA_DRIFT", "0.1")) if drift is None else float(drift)
+            g.peaks = [(float(np.clip(c + alpha * (lam_w - c), 380.0, 780.0)), w, h) for (c, w, h) in g.peaks]
+        except Exception:      # noqa: BLE001
+            pass
+        return g
+
 
 def genes_from_env(bands, n_species, species_modes=None):
     """The adapter's genes_list (adapter.py:84-138): one gene per species from QD_ECO_SPECIES_{i}_*, the template gene QD_ECO_GENE_*
@@ -671,6 +737,111 @@ def genes_from_document(doc):
             g.alloc_leaf /= s
         out.append(g)
     return out
+
+
+def genes_export_document(genes, bands, w_b, species_weights, day_value):
+    """The schema-3 document of export_genes (adapter.py:188-281): every gene entry carries the three band arrays and, where the
+    weight list reaches it, its `weight`; no top-level species_weights."""
+    doc = genes_document(genes, bands, w_b, None, day_value)
+    doc["source"] = "PyGCM.EcologyAdapter.export_genes"
+    doc["day"] = float(day_value)
+    weights = None if species_weights is None else [float(x) for x in np.asarray(species_weights, dtype=float).tolist()]
+    arrays = {k: [float(x) for x in np.asarray(getattr(bands, a), dtype=float).tolist()]
+              for k, a in (("lambda_centers_nm", "lambda_centers"), ("delta_lambda_nm", "delta_lambda"), ("lambda_edges_nm", "lambda_edges"))}
+    for i, entry in enumerate(doc["genes"]):
+        entry.update(arrays)
+        if weights is not None and i < len(weights):
+            entry["weight"] = weights[i]
+    return doc
+
+
+def genes_export_path(out_dir, day_value):
+    return os.path.join(out_dir, f"genes_day_{day_value:05.1f}.json")
+
+
+class Speciation:
+    """The stochastic tail of EcologyAdapter.step_daily (adapter.py:437-466): after every daily firing one rand() against
+    QD_ECO_MUT_RATE; on a hit below QD_ECO_SPECIES_MAX a parent drawn by species weight, the split of QD_ECO_MUT_EPS of its LAI
+    into a new species on the device, the mutated gene, the new reflectance table.  rng None = the numpy.random module (the
+    global legacy generator the reference draws from); np.random.RandomState(seed) gives the reference's numbers under
+    np.random.seed(seed).  The rand() of a firing can be drawn ahead (`hit_ahead`) and is kept until its firing is taken, so
+    looking ahead twice never draws twice; nothing else is drawn ahead."""
+
+    def __init__(self, mut_rate=None, mut_eps=None, species_max=None, rng=None, env=None):
+        env = os.environ if env is None else env
+
+        def read(name, default, kind):
+            try:
+                return kind(env.get(name, str(default)))
+            except Exception:      # noqa: BLE001  (adapter.py:42-53)
+                return default
+        self.mut_rate = read("QD_ECO_MUT_RATE", 0.0, float) if mut_rate is None else float(mut_rate)
+        self.mut_eps = read("QD_ECO_MUT_EPS", 0.02, float) if mut_eps is None else float(mut_eps)
+        self.species_max = read("QD_ECO_SPECIES_MAX", 8, int) if species_max is None else int(species_max)
+        self.rng = rng
+        self.n_done = 0                    # firings taken so far
+        self._draws = {}                   # firing number (1-based) -> its rand(), drawn ahead and not yet taken
+        self.n_events = 0
+
+    def _rng(self):
+        return np.random if self.rng is None else self.rng
+
+    def hit_ahead(self, k):
+        """Is the k-th firing from now (k >= 1) a hit?  Draws its rand() once.  The caller asks in firing order and stops at the
+        first hit, so the generator never runs past the draws the reference has made by then."""
+        if not self.mut_rate > 0.0:
+            return False
+        f = self.n_done + int(k)
+        if f not in self._draws:
+            self._draws[f] = float(self._rng().rand())
+        return self._draws[f] < self.mut_rate
+
+    def passed(self, n):
+        """n firings ran inside a span; none of them was a hit (the driver ends a chunk before one)."""
+        for _ in range(int(n)):
+            self.n_done += 1
+            if self.mut_rate > 0.0 and self._draws.pop(self.n_done, 1.0) < self.mut_rate:
+                raise RuntimeError("Speciation: a firing that was drawn as a hit ran inside a span")
+
+    def event(self, adapter):
+        """What follows one daily firing -> the index of the new species, or None."""
+        self.n_done += 1
+        if not self.mut_rate > 0.0:
+            return None
+        u = self._draws.pop(self.n_done, None)
+        if u is None:
+            u = float(self._rng().rand())
+        if not u < self.mut_rate:
+            return None
+        pop, rng = adapter.pop, self._rng()
+        S_now = int(pop.Ns)
+        if not S_now < self.species_max:
+            if adapter._diag:
+                print(f"[Ecology] mutation skipped: species_max={self.species_max} reached.")
+            return None
+        genes = adapter.genes_list                                  # (read from the environment on first use: before Ns moves)
+        try:
+            w = np.asarray(pop.species_weights, dtype=float)
+            w = w / (np.sum(w) + 1e-12)
+            parent = int(rng.choice(np.arange(S_now), p=w))
+        except Exception:      # noqa: BLE001
+            parent = int(rng.randint(0, max(1, S_now)))
+        idx_new = pop.add_species_from_parent(parent, frac=self.mut_eps)
+        try:
+            g_parent = genes[parent] if parent < len(genes) else Gene.from_env()
+            g_new = g_parent.mutated(rng, adapter.bands, adapter.w_b)
+        except Exception:      # noqa: BLE001
+            g_new = Gene.from_env()
+        if idx_new >= len(genes):
+            genes.append(g_new)
+        else:
+            genes = (genes + [g_new])[:idx_new + 1]
+        adapter.genes_list = genes
+        pop.set_species_reflectance_bands(np.stack([g.reflectance(adapter.bands) for g in genes], axis=0))
+        self.n_events += 1
+        if adapter._diag:
+            print(f"[Ecology] mutation: parent={parent} \u2192 new species idx={idx_new}; Ns={len(genes)}")
+        return idx_new
 
 
 def persist_level(env=None):
@@ -795,6 +966,24 @@ class EcologyAdapter:
             if self._diag:
                 print(f"[Ecology] Genes autosave save failed: {e}")
             return False
+
+    def export_genes(self, out_dir, day_value):
+        """adapter.py:188-281: <out_dir>/genes_day_{day:05.1f}.json with the current gene table and weights; never raises."""
+        try:
+            os.makedirs(out_dir, exist_ok=True)
+            path = genes_export_path(out_dir, day_value)
+            try:
+                weights = np.asarray(getattr(self.pop, "species_weights", []), dtype=float)
+            except Exception:      # noqa: BLE001
+                weights = None
+            doc = genes_export_document(self.genes_list, self.bands, self.w_b, weights, day_value)
+            with open(path, "w", encoding="utf-8") as f:
+                json.dump(doc, f, ensure_ascii=False, indent=2)
+            if self._diag:
+                print(f"[Ecology] Genes exported: {path} (Ns={len(doc['genes'])}, schema=3)")
+        except Exception as e:      # noqa: BLE001
+            if self._diag:
+                print(f"[Ecology] Genes export failed: {e}")
 
     def load_genes_json(self, path, *, on_mismatch="keep"):
         try:
