@@ -36,18 +36,19 @@ import qd_oracle as qo                                   # noqa: E402
 from qd_oracle import atmos as oat, numerics as onx, physics as oph, column as ocol  # noqa: E402
 from qingdai_amd.topography import create_land_sea_mask, generate_base_properties  # noqa: E402
 
-# env var name for every oracle parameter the cases below override
-ENV_OF = {
-    "energy_w": "QD_ENERGY_W", "mom_scheme": "QD_MOM_SCHEME", "filter_type": "QD_FILTER_TYPE",
-    "cloud_couple": "QD_CLOUD_COUPLE", "lw_v2": "QD_LW_V2", "gh_lock": "QD_GH_LOCK",
-    "seaice_enabled": "QD_USE_SEAICE", "shapiro_every": "QD_SHAPIRO_EVERY", "shapiro_n": "QD_SHAPIRO_N",
-    "spec_every": "QD_SPEC_EVERY", "diff_q": "QD_DIFF_Q", "diff_cloud": "QD_DIFF_CLOUD",
-    "k4_nsub": "QD_K4_NSUB", "pcond_ref": "QD_PCOND_REF", "tau_cond": "QD_TAU_COND",
-    "ocean_outlier": "QD_OCEAN_OUTLIER", "ocean_shapiro_n": "QD_OCEAN_SHAPIRO_N",
-    "ocean_shapiro_every": "QD_OCEAN_SHAPIRO_EVERY", "K_h": "QD_KH_OCEAN", "ocean_cfl": "QD_OCEAN_CFL",
-    "k4_u": "QD_K4_U", "k4_q": "QD_K4_Q", "diff_every": "QD_DIFF_EVERY", "gh_factor_lw": "QD_GH_FACTOR",
-    "diff_factor": "QD_DIFF_FACTOR", "ocean_ice_qfac": "QD_OCEAN_ICE_QFAC",
-}
+from qingdai_amd.params import _DOUBLES as _PD, _INTS as _PI        # noqa: E402
+
+# env var name of every parameter: the product's own table (qingdai_amd.params), so a name the reference does not read shows up
+# as a reference run that does not respond (case_param_sweep asserts that it does)
+ENV_OF = {n: env for n, env, _ in _PD + _PI if env is not None}
+# the four variables the reference reads as words
+ENV_WORDS = {"mom_scheme": {0: "geos", 1: "primitive"}, "snow_melt_mode": {0: "degree_day", 1: "constant"}}
+
+
+def env_text(k, v):
+    if k in ENV_WORDS and not isinstance(v, str):
+        return ENV_WORDS[k][int(v)]
+    return str(v)              # filter_type / ocean_outlier are already words in the cases
 
 
 @contextlib.contextmanager
@@ -61,10 +62,7 @@ def ref_env(over):
     os.environ["QD_OCEAN_ENERGY_DIAG"] = "0"
     os.environ["QD_USE_JAX"] = "0"
     for k, v in over.items():
-        name = ENV_OF[k]
-        if k == "mom_scheme":
-            v = "primitive" if v == 1 else "geos"
-        os.environ[name] = str(v)
+        os.environ[ENV_OF[k]] = env_text(k, v)
     try:
         yield
     finally:
@@ -743,6 +741,105 @@ def case_driver_physics(nlat, nlon, seed, nsteps=3):
          ref_precip_last=precip, ref_albedo_last=albedo, **snaps)
 
 
+# parameters the reference takes as constructor / function arguments or as a plain attribute, not from the environment
+SWEEP_ARGS = ("g", "H", "tau_rad", "greenhouse_factor", "Cs_ocean", "Cs_land", "Cs_ice", "H_ocean", "g_ocean", "orog_k", "orog_enable",
+              "D_crit", "k_precip", "p_betadiv")
+
+
+def sweep_reference_run(C, scenario, over):
+    """One run of the REFERENCE on a sweep scenario's inputs (tests/param_sweep_cases.py) -> {field: array}.  Every override
+    reaches it the way the table says: its QD_* variable, or a constructor / function argument / attribute (SWEEP_ARGS)."""
+    from types import SimpleNamespace
+    from pygcm import physics as rph
+    from pygcm.dynamics import SpectralModel
+    from pygcm.forcing import ThermalForcing
+    from pygcm.grid import SphericalGrid
+    from pygcm.ocean import WindDrivenSlabOcean
+    from pygcm.orbital import OrbitalSystem
+    I = C._inputs(scenario)
+    full = C.scenario_over(scenario, over)
+    P = qo.defaults(**full)
+    env = {k: v for k, v in full.items() if k not in SWEEP_ARGS}
+    g = SphericalGrid(*C.SHAPE)
+    mask = I["mask"]
+    n = C.SCENARIOS[scenario]["nsteps"]
+    with ref_env(env):
+        if scenario in ("column", "column_init"):
+            forcing = ThermalForcing(g, OrbitalSystem())
+            m = SpectralModel(g, I["fric"], g=P.g, H=P.H, tau_rad=P.tau_rad, greenhouse_factor=P.greenhouse_factor,
+                              C_s_map=I["csmap"], land_mask=mask, Cs_ocean=P.Cs_ocean, Cs_land=P.Cs_land, Cs_ice=P.Cs_ice)
+            if I["state"] is not None:
+                for k in STATE:
+                    setattr(m, k, I["state"][k].copy())
+            for i in range(n):
+                insA, insB = forcing.calculate_insolation_components(i * C.DT)
+                m.isr_A, m.isr_B, m.isr = insA, insB, insA + insB
+                m.time_step(forcing.calculate_equilibrium_temp(i * C.DT, I["albedo"]), C.DT, albedo=I["albedo"])
+            return {k: np.array(getattr(m, k)) for k in C.COLUMN_FIELDS}
+        if scenario == "ocean":
+            oc = WindDrivenSlabOcean(g, mask, P.H_ocean, init_Ts=I["init_Ts"])
+            oc.g = P.g_ocean
+            oc.uo, oc.vo, oc.eta = I["uo"].copy(), I["vo"].copy(), I["eta"].copy()
+            for _ in range(n):
+                oc.step(C.DT, I["u_atm"], I["v_atm"], Q_net=I["Q_net"], ice_mask=I["ice"])
+            return {k: np.array(getattr(oc, k)) for k in C.OCEAN_FIELDS}
+        if scenario == "hydro":
+            from pygcm import hydrology as rhy
+            hp = rhy.get_hydrology_params_from_env()
+            land = (mask == 1)
+            P_rain, P_snow, _ = rhy.partition_precip_phase_smooth(I["P_flux"].copy(), I["T_hat"], T_thresh=hp.snow_thresh_K,
+                                                                  dT_half_K=hp.snow_t_band_K)
+            S_next, melt, C_snow, alpha_snow = rhy.snowpack_step(I["S"], P_snow * land, I["T_hat"], hp, C.DT)
+            W_next, R_flux = rhy.update_land_bucket(I["W"], (P_rain * land) + melt, I["E_land"], hp, C.DT)
+            return dict(P_rain=P_rain, P_snow=P_snow, S_next=S_next, melt=melt, C_snow=C_snow, alpha_snow=alpha_snow,
+                        W_next=W_next, R_flux=R_flux)
+        if scenario == "orog":
+            ns = SimpleNamespace(u=I["u"], v=I["v"], T_s=I["T_s"], cloud_cover=I["cloud_cover"], P_cond_flux_last=I["Pc"])
+            fac = rph.compute_orographic_factor(g, I["elev"], I["u"], I["v"], k_orog=P.orog_k) if int(P.orog_enable) == 1 else None
+            return {"precip": rph.diagnose_precipitation_hybrid(ns, g, D_crit=P.D_crit, k_precip=P.k_precip, orog_factor=fac,
+                                                                smooth_sigma=1.0, beta_div=P.p_betadiv, renorm=True)}
+    raise KeyError(scenario)
+
+
+def case_param_sweep(scenario):
+    """One reference run per row of tests/param_sweep_cases.py (that row's variable exported, its companions too) on the scenario's
+    seeded inputs; stored as a digest per (row, field): the values at the sampled cells, np.sum and max|.|.  Asserted here, on the
+    reference itself: the perturbed run differs from the reference's own baseline (same companions) -- a variable the reference
+    does not read fails the generation."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import param_sweep_cases as C
+    rows = C.fixture_rows(scenario)
+    sc = C.SCENARIOS[scenario]
+    fields = list(sc["fields"])
+    cells = C.sample_cells(n=sc.get("n_sample", C.N_SAMPLE))
+    vals = np.zeros((len(rows), len(fields), cells.size))
+    sums = np.zeros((len(rows), len(fields)))
+    maxs = np.zeros((len(rows), len(fields)))
+    base = {}
+    worst_oracle = 0.0
+    with np.errstate(all="ignore"):
+        for ri, r in enumerate(rows):
+            key = tuple(sorted(r["comp"].items()))
+            if key not in base:
+                base[key] = quiet(sweep_reference_run, C, scenario, r["comp"])
+            over = {**r["comp"], r["param"]: r["value"]}
+            ref = quiet(sweep_reference_run, C, scenario, over)
+            moved = {k: maxrel(ref[k], base[key][k]) for k in fields}
+            assert any(moved[k] >= C.live_threshold(sc["fields"][k]) for k in fields), \
+                f"{scenario} {r['id']}: the reference did not respond to {ENV_OF.get(r['param'], r['how'])}: {moved}"
+            orc = C.run_oracle(scenario, over)
+            dev = max(maxrel(orc[k], ref[k]) for k in fields)
+            worst_oracle = max(worst_oracle, dev)
+            print(f"    {r['id']:36s} reference moved {max(moved.values()):.1e}   oracle-vs-ref maxrel {dev:.1e}")
+            for fi, k in enumerate(fields):
+                vals[ri, fi], sums[ri, fi], maxs[ri, fi] = C.digest(ref[k], cells)
+    print(f"    worst oracle-vs-ref over {len(rows)} rows: {worst_oracle:.2e}")
+    save(C.fixture_name(scenario), dict(kind="param_sweep", scenario=scenario, nlat=C.SHAPE[0], nlon=C.SHAPE[1], dt=C.DT,
+                                        nsteps=sc["nsteps"], rows=[r["id"] for r in rows], fields=fields,
+                                        how=[r["how"] for r in rows]),
+         cells=cells, vals=vals, sums=sums, maxs=maxs)
+
+
 def main():
     only = sys.argv[1:]
 
@@ -801,6 +898,10 @@ def main():
         for (a, b, s) in ((19, 36, 51), (37, 72, 52)):
             print(f"[orography {a}x{b}]")
             case_orography(a, b, s)
+    for scn in ("column", "column_init", "ocean", "orog", "hydro"):
+        if want("param_sweep_" + scn):
+            print(f"[parameter sweep: {scn} 37x72]")
+            case_param_sweep(scn)
     if want("physics"):
         for (a, b, s) in ((19, 36, 31), (37, 72, 32)):
             print(f"[physics {a}x{b}]")

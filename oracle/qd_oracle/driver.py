@@ -218,10 +218,18 @@ class DriverOracle:
             _, SW_sfc, _ = col.shortwave(m.isr, albedo, cloud_eff, P)
             T_a = 288.0 + (9.81 / 1004.0) * m.h
             ice_frac2 = 1.0 - np.exp(-np.maximum(m.h_ice, 0.0) / max(1e-6, P.hice_ref))
+            # the driver's own EnergyParams copy (run_simulation.py:2242-2246): its autotuned lw_eps0 / lw_kc act on Q_net only
+            Pq = P
+            if is_set(getattr(P, "qnet_lw_eps0", float("nan"))) or is_set(getattr(P, "qnet_lw_kc", float("nan"))):
+                Pq = type(P)(**vars(P))
+                if is_set(P.qnet_lw_eps0):
+                    Pq.lw_eps0 = P.qnet_lw_eps0
+                if is_set(P.qnet_lw_kc):
+                    Pq.lw_kc = P.qnet_lw_kc
             if P.lw_v2:
-                _, LW_sfc, _, _, _ = col.longwave_v2(m.T_s, T_a, cloud_eff, col.surface_emissivity_map(self.land_mask, ice_frac2, P), P)
+                _, LW_sfc, _, _, _ = col.longwave_v2(m.T_s, T_a, cloud_eff, col.surface_emissivity_map(self.land_mask, ice_frac2, Pq), Pq)
             else:
-                _, LW_sfc, _, _, _ = col.longwave_v1(m.T_s, T_a, cloud_eff, P)
+                _, LW_sfc, _, _, _ = col.longwave_v1(m.T_s, T_a, cloud_eff, Pq)
             SH = col.sensible_heat(m.T_s, T_a, m.u, m.v, P)
             Q_net = SW_sfc - LW_sfc - SH - m.LH_last
             self.ocean.step(dt, m.u, m.v, Q_net=Q_net, ice_mask=ice_mask)
