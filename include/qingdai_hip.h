@@ -184,6 +184,12 @@ int qd_op_median_positive(qd_handle h, const double* x, double dflt, double* out
  * 1866-1874): 4 sites x 16 doubles {last median, -, -, valid, hits, misses, candidates of the last call, positives of the last
  * call, bracket lo, hi, -, ok, calls, last miss: call, centre, result}; site 1 = P_cond, 2 = convergence, 3 = precipitation */
 int qd_median_state(qd_handle h, double* out64);
+/* (new, diagnostics) the device scalars the launches of a step hand to each other: {P_ref of P_cond, eta mean of the last ocean
+ * sub-step, precipitation median, convergence scale (median of pos > 0), renormalisation s = <Pq> / <P_raw>, blend weight of the
+ * legacy precipitation, 2 x scratch} */
+int qd_step_scalars(qd_handle h, double* out8);
+/* (new, diagnostics) ocean sub-steps since create whose eta mean was left to the next momentum launch (QD_MEAN_IN_MOMENTUM) */
+int qd_ocean_mean_next_count(qd_handle h, int64_t* out);
 
 /* ---- ecology spectral sub-step, first stage (pygcm/ecology/spectral.py:304-426) --------------------
  * dual_star_insolation_to_bands on the resident ISR_A / ISR_B: specA/specB/tray are the NB host-computed band weights of the

@@ -337,6 +337,7 @@ extern "C" int qd_create(const qd_grid_desc* d, const qd_params* params, double 
     { const char* ef = std::getenv("QD_FUSED"); if (ef && ef[0] == '0') c->use_fused = 0; }
     { const char* ef = std::getenv("QD_FUSED_FAST"); if (ef) c->fused_fast = std::atoi(ef); }
     { const char* ef = std::getenv("QD_TAIL_ACC"); if (ef) c->tail_acc = std::atoi(ef); }
+    { const char* ef = std::getenv("QD_MEAN_IN_MOMENTUM"); if (ef) c->mean_in_momentum = ef[0] == '0' ? 0 : 1; }
     { const char* ef = std::getenv("QD_SHAPIRO_STREAM"); if (ef) c->shapiro_stream = std::atoi(ef); }
     { const char* ef = std::getenv("QD_OCN_TAIL"); if (ef) c->ocn_tail = std::atoi(ef); }   // 0: two launches (k_cont_sstadv, k_sst_outlier_fused); anything else: k_ocn_tail_fast (QD_TAIL_V=1: k_ocn_tail_stream).  The LDS-tile forms and the one-launch sub-step of round 3 (2, 3, 4) are retired: tools/retired/
     if (c->ocn_tail != 0) c->ocn_tail = 1;
@@ -372,8 +373,9 @@ extern "C" int qd_create(const qd_grid_desc* d, const qd_params* params, double 
     if ((e = hipMalloc(&c->red_partial, (size_t)c->red_blocks * sizeof(double))) != hipSuccess) return bail("hipMalloc", e);
     if ((e = hipMalloc(&c->dscal, QD_S_COUNT * sizeof(double))) != hipSuccess) return bail("hipMalloc", e);
     if ((e = hipMalloc(&c->dcount, 32 * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc(&c->eta_acc, 512 * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
-    hipMemsetAsync(c->eta_acc, 0, 512 * sizeof(unsigned long long), c->stream);
+    // (the ticketed set, and behind it the two sets of the sums the next launch finishes: QD_ACC_NEXT_SET, qd_wave.h)
+    if ((e = hipMalloc(&c->eta_acc, 1024 * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
+    hipMemsetAsync(c->eta_acc, 0, 1024 * sizeof(unsigned long long), c->stream);
     if ((e = hipMalloc(&c->hist, 2 * QD_HIST_BINS * sizeof(unsigned int))) != hipSuccess) return bail("hipMalloc", e);
     if ((e = hipMalloc(&c->sel_state, 8 * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
     hipMemsetAsync(c->dscal, 0, QD_S_COUNT * sizeof(double), c->stream);
@@ -899,6 +901,20 @@ extern "C" int qd_median_state(qd_handle c, double* out64) {
     if (!c->med_pred) return 0;
     QD_HIP(c, hipStreamSynchronize(c->stream));
     QD_HIP(c, hipMemcpy(out64, c->med_pred, sizeof(double) * 16 * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int qd_step_scalars(qd_handle c, double* out8) {
+    if (!c || !out8) return -1;
+    hipSetDevice(c->desc.device);
+    QD_HIP(c, hipStreamSynchronize(c->stream));
+    QD_HIP(c, hipMemcpy(out8, c->dscal, sizeof(double) * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int qd_ocean_mean_next_count(qd_handle c, int64_t* out) {
+    if (!c || !out) return -1;
+    *out = c->mean_next_count;
     return 0;
 }
 

@@ -109,3 +109,27 @@ __device__ __forceinline__ void qd_planes_by_wave(const double* __restrict__ par
     }
     __syncthreads();
 }
+
+// ---- the two scalars of the precipitation renormalisation from the row partials of k_precip_raw (partial[0 .. n) = sum Pq w,
+// partial[n .. 2n) = sum P_raw w): out[0] = s = num / den, out[1] = blend weight of the legacy field (p_blend when <Pq> < pq_min and
+// the fallback is on, else 0).  One workgroup of QD_BLOCK threads; block-strided shares, wave sums, thread 0 adds the wave results
+// from wave 0 on.  k_precip_scalars (one workgroup) and the precipitation k_gauss_pair (every workgroup for itself) both call it:
+// one order, one result.  out: LDS or global; every thread may read an LDS out on return.
+__device__ __forceinline__ void qd_precip_scalars_wg(const double* __restrict__ partial, int n, double wsum, double pq_min, double p_blend,
+                                                     int use_fb, double* out) {
+    __shared__ double sm[2][QD_BLOCK / 64];
+    double a = 0.0, b = 0.0;
+    for (int k = threadIdx.x; k < n; k += QD_BLOCK) { a += partial[k]; b += partial[n + k]; }
+    a = qd_wave_sum(a); b = qd_wave_sum(b);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { sm[0][wv] = a; sm[1][wv] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < QD_BLOCK / 64; ++k) { a += sm[0][k]; b += sm[1][k]; }
+        const double den = b + 1e-20;
+        out[0] = den > 0 ? a / den : 1.0;
+        const double pq_mean = a / (wsum + 1e-15);
+        out[1] = (use_fb && pq_mean < pq_min) ? p_blend : 0.0;
+    }
+    __syncthreads();
+}

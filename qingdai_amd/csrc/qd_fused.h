@@ -31,6 +31,12 @@ struct QdOcnArgs {
     double eta_cap;
     int fast;
     QdTileShape ts;
+    // k_ocn_stream only (qd_launch_ocn_stream on a whole-globe handle): the previous tail launch left its eta sum in this slot set and
+    // the kernel's eta waves finish it (qd_wave.h, qd_stream.h: qs_mean_handover); eta_mean is then not read
+    const unsigned long long* acc_read = nullptr;
+    const double* acc_partial = nullptr;
+    int acc_n = 0;
+    double acc_wsum = 0.0;
 };
 
 

@@ -849,6 +849,7 @@ int qd_launch_dyn_hyper(qd_ctx* c, QdDynArgs& P, int margin) {
 
 int qd_launch_ocn_hyper(qd_ctx* c, QdOcnArgs& P, int margin) {
     if (qd_ocn_stream_ok(c, margin)) return qd_launch_ocn_stream(c, P, margin);
+    if (P.acc_read) return qd_fail(c, "k_ocn_hyper: an unfinished eta mean needs the streaming kernel");
     qd_tile_init(c);
     P.ts = c->tile;
     P.fast = c->fused_fast != 0;

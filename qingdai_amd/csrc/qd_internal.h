@@ -288,6 +288,8 @@ struct qd_ctx {
     int use_fused = 1;              // QD_FUSED=0 selects the unfused reference-order kernels
     int fused_fast = 1;             // QD_FUSED_FAST: 1 row-streaming kernels (qd_stream.hip), FAST variant with per-wave EXACT fallback; 2 the same kernels,
                                     // every wave EXACT; 0 LDS-tiled kernels (qd_fused.hip), every tile EXACT; 3 LDS-tiled kernels with their FAST path
+    long long mean_next_count = 0;  // sub-steps whose tail launch left the mean to the next launch (qd_ocean_mean_next_count)
+    int mean_in_momentum = 1;       // QD_MEAN_IN_MOMENTUM=0: every tail launch finishes its own eta mean (tickets + finishing wave), none is left to the next k_ocn_stream
     int tail_acc = 1;               // QD_TAIL_ACC=0: the eta mean of a sub-step from k_eta_mean_tail instead of the tail kernel's own last workgroup
     unsigned long long* eta_acc = nullptr;   // accumulator + tickets of the tail kernel's strip sums (qd_wave.h: QD_ACC_WORDS)
     int shapiro_stream = 1;         // QD_SHAPIRO_STREAM=0: one k_shapiro_pass launch per pass
@@ -455,8 +457,12 @@ void qd_launch_divvort(qd_ctx* c, const double* u, const double* v, double* out,
 int  qd_gaussian(qd_ctx* c, const double* in, double* out, double* tmp, double sigma, int mode_wrap, int m_out, int clip01 = 0,
                  const double* scale_p = nullptr, double scale_k = 1.0);
 bool qd_gauss_pair_ok(const qd_ctx* c, double sigma);
+// the precipitation pair with k_precip_scalars folded in (qd_stencil.hip: QdGaussPairP): the row partials of k_precip_raw, what the
+// two scalars need, where workgroup (0, 0) stores them; field B is then the divergence slab and D_crit turns it into pos on load
+struct QdPrecipFold { const double* partial; int n; double wsum, pq_min, p_blend; int use_fb; double dcrit; double* out; };
 int  qd_gaussian_pair(qd_ctx* c, const double* inA, const double* inB, double sigma, int mode_wrap, const double* scA_p, double scA_k,
-                      double scB_k, const double* sc, int op, const double* blend5, double* outA, double* outB, double* out0, int m_out = 0);
+                      double scB_k, const double* sc, int op, const double* blend5, double* outA, double* outB, double* out0, int m_out = 0,
+                      const QdPrecipFold* fold = nullptr);
 int  qd_gaussian_swap(qd_ctx* c, double*& field, double*& tmp, double sigma, int mode_wrap, int m_out, int clip01 = 0,
                       const double* scale_p = nullptr, double scale_k = 1.0);
 bool qd_gauss_can_fuse(const qd_ctx* c, double sigma);

@@ -945,6 +945,17 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
     const bool use_fused1 = use_tail && !band && c->ocn_fused && c->ocn_tail == 1 && tail_acc && c->fused_fast == 1 && do_diff &&
                             p.ocean_k4_nsub == 1 && !do_shap && HP.use_q && HP.K_h > 0.0 && qd_ocn_fused_ok(c) &&
                             !c->k4_ocn_skip[0] && !c->k4_ocn_skip[1] && !c->k4_ocn_skip[2];
+    // QD_MEAN_IN_MOMENTUM: a storing k_ocn_tail_fast whose next launch is k_ocn_stream leaves its eta mean to that launch's eta waves
+    // (qd_wave.h): no wait for the adds, no tickets, no finishing wave.  Decided per sub-step: the last one of a step keeps the finishing
+    // wave (k_polar_clamp_inject reads the scalar), so does the fix-list form (its last arriver patches), and every other launcher.
+    // With the tickets gone the storing form beats the fix-list form in the young regime as well (721 x 1440, steps 24-264: 0.813
+    // against 0.820 ms/step; in the steady regime the list never paid: profiles/README.md), so a step that can leave its means to the
+    // next launch does not take the list at all; fix_dense still decides for every other handle and for n_sub = 1.
+    const bool mean_form_ok = c->mean_in_momentum && !band && G0.full && tail_acc && !use_fused1 && do_diff && c->use_fused && n_sub > 1 &&
+                              p.ocean_k4_nsub == 1 && !do_shap && qd_ocn_tail_is_fast(c) && qd_ocn_stream_ok(c, 0);
+    if (mean_form_ok) fix_now = false;
+    const bool mean_next_ok = mean_form_ok;
+    unsigned long long* acc_pending = nullptr;               // the slot set the previous tail launch left for this sub-step's momentum launch
     for (int s = 0; s < n_sub; ++s) {
         if (use_fused1) {
             QdOcnArgs O;
@@ -1000,6 +1011,7 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
             O.inv_2dlon = 1.0 / (2.0 * c->dlon); O.inv_2dlat = 1.0 / (2.0 * c->dlat); O.inv_a = 1.0 / p.a; O.inv_rhoH = 1.0 / (p.rho_w * H);
             O.eta_mean = (defer_eta && s > 0) ? mean_ptr : nullptr;
             O.eta_cap = p.eta_cap;
+            if (acc_pending) { O.acc_read = acc_pending; O.acc_partial = c->red_partial; O.acc_n = qd_ocn_tail_tiles(c, Gown); O.acc_wsum = c->wsum_ocean; }
             // Exchange overlapped with interior compute (peer exchange, QD_PEER_OVERLAP): the rows whose stencils stay inside the OLD
             // margins are launched between the push and the unpack -- the halo rows travel while they run -- and only the two
             // boundary strips wait for the neighbours.  Rows do not depend on the strip they are computed in: bit-identical.
@@ -1101,6 +1113,10 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
             } else {
             // uo'' / vo'' in place through the fix list (the launcher drops it when the kernel it picks has no finishing wave)
             if (fix_now) { A.fix_count = c->fix_count; A.fix_list = c->fix_list; }
+            A.acc_clear = acc_pending;                        // this sub-step's momentum launch has read it
+            acc_pending = (mean_next_ok && s + 1 < n_sub) ? QD_ACC_NEXT_SET(c->eta_acc, s & 1) : nullptr;
+            A.acc_next = acc_pending;
+            if (acc_pending) c->mean_next_count++;
             if (qd_launch_ocn_tail(c, Gown, A)) return -1;
             if (!tail_acc)
                 hipLaunchKernelGGL(k_eta_mean_tail, dim3(1), dim3(256), 0, c->stream, c->red_partial, qd_ocn_tail_tiles(c, Gown), c->wsum_ocean,

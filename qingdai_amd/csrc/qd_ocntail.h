@@ -22,11 +22,16 @@ struct QdTailArgs {
     // u bits, v bits} -- and the launch's finishing wave, which runs when every wave of every strip is done, patches uo', vo' in place
     unsigned int* fix_count = nullptr;
     unsigned long long* fix_list = nullptr;
+    // whole-globe k_ocn_tail_fast<false> in front of a k_ocn_stream launch (qd_wave.h: the sum finished by the next launch): the strips
+    // only add to this slot set, no ticket, no finishing wave; acc_clear: the set the momentum launch of THIS sub-step has read
+    unsigned long long* acc_next = nullptr;
+    unsigned long long* acc_clear = nullptr;
     QdPeerFold pf;                                           // latitude bands over the peer exchange: the finishing wave all-reduces the band's share itself (qd_peer_dev.h)
 };
 
 int qd_ocn_tail_tiles(const qd_ctx* c, const QdGeom& G);
 int qd_launch_ocn_tail(qd_ctx* c, const QdGeom& G, QdTailArgs& P);
+bool qd_ocn_tail_is_fast(const qd_ctx* c);               // the launcher picks k_ocn_tail_fast
 
 // the whole sub-step in one launch, streaming form (QD_OCN_FUSED=1; qd_ocntail.hip, k_ocn_fused)
 struct QdOcnArgs;

@@ -713,6 +713,11 @@ k_ocn_tail_fast(QdGeom G, QdTabs T, QdTailArgs P) {
     if (FIX) __syncthreads();
     acc = qd_wave_sum(acc);
     if (W.lane == 0) __hip_atomic_store(P.partial + w, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // coherent: the finisher may read it
+    if (!FIX && P.acc_clear && w == 0u) qd_acc_clear_set(P.acc_clear);      // the set this sub-step's momentum launch has read (it is over)
+    if (!FIX && P.acc_next) {                                // eta mean finished by the next momentum launch: add and leave
+        if (W.lane == 0) qd_acc_add(P.acc_next, w, acc);
+        return;
+    }
     if (P.acc) {                                             // eta mean inside this launch: the last workgroup to arrive finishes it
         const bool last = W.lane == 0 && qd_acc_arrive(P.acc, w, gridDim.x, acc);
         if (__builtin_amdgcn_ballot_w64(last) != 0ull) {
@@ -1047,6 +1052,7 @@ static int qt_rows(const qd_ctx* c) { return c->tune.tail_r > 0 ? c->tune.tail_r
 
 // the slim streaming form (k_ocn_tail_fast) unless QD_TAIL_V=1 asks for the round-3 kernel; its strip heights
 static bool qt_use_fast(const qd_ctx* c) { return !c->tune.tail_v && c->ocn_tail == 1; }
+bool qd_ocn_tail_is_fast(const qd_ctx* c) { return qt_use_fast(c); }
 // 240-step bench, 721 x 1440, ms per step (same box): R = 8 / 9 / 10 / 11 / 12 -> 0.926 / 0.895 / 0.894 / 0.907 / 0.896; pole strips of 3 / 4 / 5
 // rows: 0.894 / 0.893 / 0.893; the round-3 kernel on that box: 0.940
 // 1441 x 2880 (48 column groups): R = 10 / 14 / 20 / 28 / 40 / 56 -> 5.13 / 5.09 / 4.87 / 4.84 / 4.79 / 4.88 ms per step (round-3 kernel: 5.28).  Both optima
@@ -1099,6 +1105,8 @@ int qd_launch_ocn_tail(qd_ctx* c, const QdGeom& G, QdTailArgs& P) {
     if (!stamps) { hipMalloc(&stamps, stamp_words * 8); hipMemcpyToSymbol(HIP_SYMBOL(qt_stamp_buf), &stamps, sizeof(stamps)); }
     hipMemsetAsync(stamps, 0, stamp_words * 8, c->stream);
 #endif
+    if ((P.acc_next || P.acc_clear) && (!fast || P.fix_count || !G.full))        // only k_ocn_tail_fast<false> knows them (the caller decides the form)
+        return qd_fail(c, "k_ocn_tail: the mean of a sub-step can only be left to the next launch by the storing fast form");
     if (!fast || !P.acc) { P.fix_count = nullptr; P.fix_list = nullptr; }          // the fix list is applied by k_ocn_tail_fast's finishing wave
     if (fast && P.fix_count) QD_LAUNCH_TIMED(sc, k_ocn_tail_fast<true>, dim3(nrs * P.ntc), dim3(128), c->stream, G, c->tabs, P);
     else if (fast) QD_LAUNCH_TIMED(sc, k_ocn_tail_fast<false>, dim3(nrs * P.ntc), dim3(128), c->stream, G, c->tabs, P);

@@ -23,6 +23,10 @@ QdColP qd_make_colp(const qd_ctx* c, double dt);   // qd_atmos.hip
 
 
 // one workgroup per row: P_raw and the two weighted row sums (num = sum Pq w, den = sum P_raw w)
+// SLAB (whole-globe handles in front of the folded k_gauss_pair): the divergence is READ from the slab k_divvort stored for the median
+// two launches earlier (`u`; the same qd_divvort_point, so the same bits) instead of being formed again from u, v and their four
+// neighbours, and pos is not stored: the blur of the fallback blend forms it from the same slab on load, when it runs at all
+template <bool SLAB>
 __global__ void __launch_bounds__(QD_BLOCK)
 k_precip_raw(QdGeom G, QdTabs T, const double* __restrict__ u, const double* __restrict__ v,
              const double* __restrict__ pcond, double a, double dlat, double dlon, double D_crit, double beta,
@@ -37,7 +41,7 @@ k_precip_raw(QdGeom G, QdTabs T, const double* __restrict__ u, const double* __r
     const double scale = qd_max(*scale_p, 1e-12);
     double s_num = 0.0, s_den = 0.0;
     for (int j = threadIdx.x; j < G.nlon; j += QD_BLOCK) {
-        const double div = qd_divvort_point(G, T, u, v, i, j, a, dlat, dlon, 0);
+        const double div = SLAB ? u[b + j] : qd_divvort_point(G, T, u, v, i, j, a, dlat, dlon, 0);
         const double pos = qd_max(0.0, -(div - D_crit));
         const double F_div = anypos ? qd_clip(pos / scale, 0.0, 5.0) : 0.0;
         const double Pq = qd_max(0.0, pcond[b + j]);
@@ -45,7 +49,7 @@ k_precip_raw(QdGeom G, QdTabs T, const double* __restrict__ u, const double* __r
         const double F = (1.0 + beta * F_div) * F_orog;
         const double pr = Pq * F;
         praw[b + j] = pr;
-        pos_out[b + j] = pos;
+        if (!SLAB) pos_out[b + j] = pos;
         s_num += Pq * w;
         s_den += pr * w;
     }
@@ -86,20 +90,7 @@ k_orog_factor(QdGeom G, QdTabs T, const double* __restrict__ elev, const double*
 __global__ void __launch_bounds__(QD_BLOCK)
 k_precip_scalars(const double* __restrict__ partial, int n, double wsum, double pq_min, double p_blend, int use_fb,
                  double* __restrict__ out) {
-    __shared__ double sm[2][QD_BLOCK / 64];
-    double a = 0.0, b = 0.0;
-    for (int k = threadIdx.x; k < n; k += QD_BLOCK) { a += partial[k]; b += partial[n + k]; }
-    a = qd_wave_sum(a); b = qd_wave_sum(b);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { sm[0][wv] = a; sm[1][wv] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < QD_BLOCK / 64; ++k) { a += sm[0][k]; b += sm[1][k]; }
-        const double den = b + 1e-20;
-        out[0] = den > 0 ? a / den : 1.0;
-        const double pq_mean = a / (wsum + 1e-15);
-        out[1] = (use_fb && pq_mean < pq_min) ? p_blend : 0.0;
-    }
+    qd_precip_scalars_wg(partial, n, wsum, pq_min, p_blend, use_fb, out);      // qd_blockred.h
 }
 
 __global__ void __launch_bounds__(QD_BLOCK)
@@ -399,7 +390,7 @@ int qd_driver_physics_impl(qd_ctx* c, double dt, const QdForcingCall* fc, int pa
                 auto run = [&](int r0, int r1) {
                     if (r1 <= r0) return;
                     QdGeom g2 = G; g2.row0 = r0; g2.nrows = r1 - r0;
-                    hipLaunchKernelGGL(k_precip_raw, dim3(1, g2.nrows), blk, 0, c->stream, g2, c->tabs, F[QD_F_U], F[QD_F_V],
+                    hipLaunchKernelGGL(k_precip_raw<false>, dim3(1, g2.nrows), blk, 0, c->stream, g2, c->tabs, F[QD_F_U], F[QD_F_V],
                                        F[QD_F_PCOND], p.a, c->dlat, c->dlon, p.D_crit, p.p_betadiv, c->dscal + QD_S_PSCALE,
                                        c->dcount, praw, pos, rp + (size_t)2 * G0.lrows(), orog);
                 };
@@ -408,10 +399,19 @@ int qd_driver_physics_impl(qd_ctx* c, double dt, const QdForcingCall* fc, int pa
                 else { run(a0, std::max(a0, own0)); run(std::min(a1, own1), a1); }
             }
         }
-        hipLaunchKernelGGL(k_precip_raw, dim3(1, Gown.nrows), blk, 0, c->stream, Gown, c->tabs, F[QD_F_U], F[QD_F_V],
+        // whole-globe handles whose two blurs and blend are one launch: that launch also reduces the row sums (no k_precip_scalars), and
+        // the divergence slab of the median above stands for pos.  The orographic factor's blur has used the slab as its scratch by now:
+        // that path keeps the separate form.
+        const bool fold = !band && !orog && qd_gauss_pair_ok(c, 1.0);
+        if (fold)
+            hipLaunchKernelGGL(k_precip_raw<true>, dim3(1, Gown.nrows), blk, 0, c->stream, Gown, c->tabs, tmp, (const double*)nullptr,
+                               F[QD_F_PCOND], p.a, c->dlat, c->dlon, p.D_crit, p.p_betadiv, c->dscal + QD_S_PSCALE, c->dcount, praw,
+                               (double*)nullptr, rp, orog);
+        else
+        hipLaunchKernelGGL(k_precip_raw<false>, dim3(1, Gown.nrows), blk, 0, c->stream, Gown, c->tabs, F[QD_F_U], F[QD_F_V],
                            F[QD_F_PCOND], p.a, c->dlat, c->dlon, p.D_crit, p.p_betadiv, c->dscal + QD_S_PSCALE, c->dcount, praw,
                            pos, rp, orog);
-        qd_mark(c, {praw, pos}, m);
+        if (fold) qd_mark(c, {praw}, m); else qd_mark(c, {praw, pos}, m);
         if (band && qd_peer_hooks(c)) {
             // row sums -> all-reduce -> the two scalars in ONE launch (QdPeerHook: pre 2 = k_precip_rawsums, post 1 = k_precip_scalars_post)
             QdPeerHook H; H.pre = 2; H.partial = rp; H.n = Gown.nrows;
@@ -423,12 +423,20 @@ int qd_driver_physics_impl(qd_ctx* c, double dt, const QdForcingCall* fc, int pa
             if (qd_allreduce_f64(c, c->dscal + QD_S_TMP0, 2, 0)) return -1;
             hipLaunchKernelGGL(k_precip_scalars_post, dim3(1), dim3(64), 0, c->stream, c->dscal + QD_S_TMP0, c->wsum_all, p.pq_min,
                                p.p_blend, p.p_hybrid_fallback, c->dscal + QD_S_RENORM);
-        } else {
+        } else if (!fold) {
             hipLaunchKernelGGL(k_precip_scalars, dim3(1), blk, 0, c->stream, rp, Gown.nrows, c->wsum_all, p.pq_min,
                                p.p_blend, p.p_hybrid_fallback, c->dscal + QD_S_RENORM);
         }
         // P = gaussian(P_raw * s); P_dyn = gaussian(k_precip * pos): the two scalings ride on the blur's loads
-        if (qd_gauss_pair_ok(c, 1.0)) {
+        if (fold) {
+            // ... and the two scalars in front of them, in every workgroup; pass B (fallback blend on) reads the divergence slab
+            const int mg = qd_plan(c, {QD_IN(praw, R1), QD_IN(tmp, R1)});
+            if (mg < 0) return -1;
+            const QdPrecipFold PF{rp, Gown.nrows, c->wsum_all, p.pq_min, p.p_blend, p.p_hybrid_fallback, p.D_crit, c->dscal + QD_S_RENORM};
+            if (qd_gaussian_pair(c, praw, tmp, 1.0, 0, nullptr, 1.0, p.k_precip, nullptr, 1, nullptr, nullptr, nullptr,
+                                 F[QD_F_PRECIP], mg, &PF)) return -1;
+            qd_mark(c, {F[QD_F_PRECIP]}, mg);
+        } else if (qd_gauss_pair_ok(c, 1.0)) {
             // both blurs and the blend in one launch (the convergence field is not even read while the fallback is off)
             const int mg = qd_plan(c, {QD_IN(praw, R1), QD_IN(pos, R1)});
             if (mg < 0) return -1;

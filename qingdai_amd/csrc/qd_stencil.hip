@@ -13,6 +13,7 @@
 #include "qd_internal.h"
 #include "qd_device.h"
 #include "qd_wave.h"
+#include "qd_blockred.h"
 #include <cstdlib>
 
 // ------------------------------------------------------------------ Laplacian (device)
@@ -487,10 +488,19 @@ static bool qd_gauss_weights(double sigma, QdGaussW& W) {
 //   op 1 (precipitation, k_precip_blend): out0 = max((al != 0 ? (1 - al) a + al b : a), 0), al = sc[1]; field B is not even read
 //                                         when al == 0 (the fallback blend of physics.py:344-352 is off)
 //   op 2 (cloud, k_cloud_blend):          outA = a, outB = b (both clipped to [0, 1]), out0 = the blended cloud cover
-struct QdGaussPairP { int op; double w_mem, w_p, w_src, tend, c_floor; };
-template <int RR>
+//   op 1 with P.fold: the launch also stands for k_precip_scalars -- EVERY workgroup reduces the row partials of k_precip_raw itself
+//                     (qd_precip_scalars_wg: 2 x nrows doubles out of L2, the same strides and the same order, so the same bits) instead
+//                     of a one-workgroup launch in front of this one; workgroup (0, 0) stores the pair for later readers.  Field B is
+//                     then the DIVERGENCE slab, and pass B forms pos = max(0, -(div - D_crit)) on load (P.dcrit; qd_med_value's
+//                     transform 1): k_precip_raw does not store pos at all.
+struct QdGaussPairP {
+    int op; double w_mem, w_p, w_src, tend, c_floor;
+    int fold, fold_n, use_fb; const double* partial; double wsum, pq_min, p_blend, dcrit; double* scal_out;
+};
+template <int RR, bool POS>
 __device__ __forceinline__ void qd_gauss_rows_pass(const QdGeom& G, const double* __restrict__ in, double sc, const double (&w)[RR + 1],
-                                                   int mode_wrap, int i0, int nvalid, int jbase, double (*sm)[QD_BLOCK], double (&acc)[QD_GB]) {
+                                                   int mode_wrap, int i0, int nvalid, int jbase, double (*sm)[QD_BLOCK], double (&acc)[QD_GB],
+                                                   double dcrit = 0.0) {
     {
         const int s = threadIdx.x;
         const int jj = jbase - RR + s;
@@ -500,7 +510,8 @@ __device__ __forceinline__ void qd_gauss_rows_pass(const QdGeom& G, const double
 #pragma unroll
             for (int q = 0; q < QD_GB + 2 * RR; ++q) {
                 const int qq = q < nvalid + 2 * RR ? q : nvalid + 2 * RR - 1;
-                x[q] = in[(size_t)qd_lrow(G, qd_ext(i0 - RR + qq, G.nlat, mode_wrap)) * G.nlon + j] * sc;
+                const double v = in[(size_t)qd_lrow(G, qd_ext(i0 - RR + qq, G.nlat, mode_wrap)) * G.nlon + j];
+                x[q] = (POS ? qd_max(0.0, -(v - dcrit)) : v) * sc;
             }
 #pragma unroll
             for (int k = 0; k < QD_GB; ++k) {
@@ -538,12 +549,22 @@ k_gauss_pair(QdGeom G, const double* __restrict__ inA, const double* __restrict_
     double w[RR + 1];
 #pragma unroll
     for (int k = 0; k <= RR; ++k) w[k] = W.w[k];
-    const double al = (P.op == 1) ? sc[1] : 0.0;
+    double scA, al;
+    if (P.fold) {
+        __shared__ double s_sc[2];
+        qd_precip_scalars_wg(P.partial, P.fold_n, P.wsum, P.pq_min, P.p_blend, P.use_fb, s_sc);
+        if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) { P.scal_out[0] = s_sc[0]; P.scal_out[1] = s_sc[1]; }
+        scA = s_sc[0]; al = s_sc[1];
+    } else {
+        scA = scA_p ? *scA_p : scA_k;
+        al = (P.op == 1) ? sc[1] : 0.0;
+    }
     double a[QD_GB], b[QD_GB];
 #pragma unroll
     for (int k = 0; k < QD_GB; ++k) { a[k] = 0.0; b[k] = 0.0; }
-    qd_gauss_rows_pass<RR>(G, inA, scA_p ? *scA_p : scA_k, w, mode_wrap, i0, nvalid, jbase, sm, a);
-    if (P.op != 1 || al != 0.0) qd_gauss_rows_pass<RR>(G, inB, scB_k, w, mode_wrap, i0, nvalid, jbase, sm, b);
+    qd_gauss_rows_pass<RR, false>(G, inA, scA, w, mode_wrap, i0, nvalid, jbase, sm, a);
+    if (P.fold) { if (al != 0.0) qd_gauss_rows_pass<RR, true>(G, inB, scB_k, w, mode_wrap, i0, nvalid, jbase, sm, b, P.dcrit); }
+    else if (P.op != 1 || al != 0.0) qd_gauss_rows_pass<RR, false>(G, inB, scB_k, w, mode_wrap, i0, nvalid, jbase, sm, b);
     const int c0 = threadIdx.x;
     const int j = jbase + c0 - RR;
     if (c0 < RR || c0 >= QD_BLOCK - RR || j >= G.nlon) return;
@@ -573,11 +594,17 @@ bool qd_gauss_pair_ok(const qd_ctx* c, double sigma) {
     return c->use_fused && c->merge_pointwise && sigma > 1e-15 && c->geo.nlon > 2 * r && (r == 1 || r == 2 || r == 4);
 }
 int qd_gaussian_pair(qd_ctx* c, const double* inA, const double* inB, double sigma, int mode_wrap, const double* scA_p, double scA_k,
-                     double scB_k, const double* sc, int op, const double* blend5, double* outA, double* outB, double* out0, int m_out) {
+                     double scB_k, const double* sc, int op, const double* blend5, double* outA, double* outB, double* out0, int m_out,
+                     const QdPrecipFold* fold) {
     QdGaussW W;
     if (!qd_gauss_weights(sigma, W)) return qd_fail(c, "gaussian radius too large");
-    QdGaussPairP P{op, 0, 0, 0, 0, 0};
+    QdGaussPairP P{op, 0, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0, 0, 0, nullptr};
     if (blend5) { P.w_mem = blend5[0]; P.w_p = blend5[1]; P.w_src = blend5[2]; P.tend = blend5[3]; P.c_floor = blend5[4]; }
+    if (fold) {
+        if (op != 1 || !c->geo.full) return qd_fail(c, "qd_gaussian_pair: the folded scalars belong to the precipitation blend of a whole-globe handle");
+        P.fold = 1; P.fold_n = fold->n; P.use_fb = fold->use_fb; P.partial = fold->partial; P.wsum = fold->wsum; P.pq_min = fold->pq_min;
+        P.p_blend = fold->p_blend; P.dcrit = fold->dcrit; P.scal_out = fold->out;
+    }
     const int r = W.r;
     QD_ROWS(c, m_out, G,
         const dim3 grid((G.nlon + (QD_BLOCK - 2 * r) - 1) / (QD_BLOCK - 2 * r), (G.nrows + QD_GB - 1) / QD_GB);

@@ -35,6 +35,12 @@ struct QsOcnArgs {
     double eta_cap, sub_dt, g, r_bot, inv_2dlon, inv_2dlat, inv_a, inv_rhoH;
     int vb, ntc, nrs, exact;
     QsRec rec[3];                              // uo vo eta; aux = taux | tauy
+    // k_ocn_stream behind a tail launch that left its eta mean unfinished (qd_wave.h: the sum finished by the next launch): the slot
+    // set, the stored partials of the flagged fallback and their number, the ocean's area weight.  nullptr: *eta_mean as ever.
+    const unsigned long long* acc_read = nullptr;
+    const double* acc_partial = nullptr;
+    int acc_n = 0;
+    double acc_wsum = 0.0;
 };
 
 // ---------------------------------------------------------------- buffer access
@@ -136,6 +142,7 @@ template <int V, int PD> struct QsSrcPlain {                  // h, q, cloud: th
 #pragma unroll
         for (int k = 0; k < PD; ++k) { q[k] = qs_ld(p, ro, W.vo); ro += W.nlon; }
     }
+    __device__ __forceinline__ void settle(bool&) {}
     template <int K> __device__ __forceinline__ double get(int, bool&) { return qs_own(q[K % PD]); }
     template <int K> __device__ __forceinline__ double get_edge(int g, bool& bad) { return get<K>(g, bad); }
     template <int K> __device__ __forceinline__ void refill() { q[K % PD] = qs_ld(p, ro, W.vo); ro += W.nlon; }
@@ -158,6 +165,7 @@ template <bool PRIM, int V, int PD> struct QsSrcLat {
             hq[k] = qs_ld(H, ro, W.vo);
         }
     }
+    __device__ __forceinline__ void settle(bool&) {}
     template <int EDGE> __device__ __forceinline__ double eval(int g, double hn, double x0, double y0, double f0, bool& bad) {
         double dh = (hn - hm) * A.inv_2dlat;
         if (EDGE) { if (g == 0) dh = (hn - hc) * A.inv_dlat; if (g == W.n - 1) dh = (hc - hm) * A.inv_dlat; }
@@ -198,6 +206,7 @@ template <bool PRIM, int V, int PD, bool EC> struct QsSrcLon {
         ro = qs_off(A.G, g0);
         load<0>(); if (PD > 1) load<1>(); if (PD > 2) { load<2>(); load<3>(); }
     }
+    __device__ __forceinline__ void settle(bool&) {}
     __device__ __forceinline__ double eval(int g, double hc, double x0, double y0, double f0, bool& bad) {
         const double hw = qd_west(hc), he = qd_east(hc);
         // np.gradient is one-sided at both ends of the longitude axis (not periodic: SURVEY 0.6)
@@ -235,13 +244,29 @@ template <int V> __device__ __forceinline__ double qs_eta(double raw, bool defer
     return fmin(fmax(e, -cap), cap);
 }
 
+// The mean of the previous sub-step when the tail launch left it unfinished (QsOcnArgs::acc_read): settle() runs in every wave of
+// the workgroup right BEHIND the wave's first row loads (start()) and in front of the first row step.  The eta wave reduces the slot
+// set in registers (qd_acc_read: lane = slot, nothing stored) and puts the mean into the workgroup's LDS word; ONE barrier, reached by
+// all three waves exactly once per launch, hands it to the U and V waves.  `sy` = that LDS word, nullptr = `em` is valid already
+// (*eta_mean, or the EXACT re-run of a wave: it keeps the mean its FAST pass got and must not meet the barrier again).
+__device__ __forceinline__ double qs_mean_handover(const QsOcnArgs& A, double* sy, bool reader) {
+    if (reader) {
+        const double m = qd_acc_read(A.acc_read, A.acc_partial, A.acc_n, A.acc_wsum);
+        if ((threadIdx.x & 63) == 0) __hip_atomic_store(sy, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0): the LDS store is done before this wave signals the barrier
+    }
+    __builtin_amdgcn_s_barrier();
+    return __hip_atomic_load(sy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 template <int V, int PD> struct QsSrcEta {
-    const QsOcnArgs& A; const QsW& W; qs_rsrc E; bool defer; double em, cap; double q[PD]; unsigned ro;
+    const QsOcnArgs& A; const QsW& W; qs_rsrc E; bool defer; double em, cap; double q[PD]; unsigned ro; double* sy = nullptr;
     __device__ __forceinline__ void start(int g0, bool&) {
         ro = qs_off(A.G, g0);
 #pragma unroll
         for (int k = 0; k < PD; ++k) { q[k] = qs_ld(E, ro, W.vo); ro += W.nlon; }
     }
+    __device__ __forceinline__ void settle(bool&) { if (sy) em = qs_mean_handover(A, sy, true); }
     template <int K> __device__ __forceinline__ double get(int, bool& bad) { return qs_eta<V>(qs_own(q[K % PD]), defer, em, cap, bad); }
     template <int K> __device__ __forceinline__ double get_edge(int g, bool& bad) { return get<K>(g, bad); }
     template <int K> __device__ __forceinline__ void refill() { q[K % PD] = qs_ld(E, ro, W.vo); ro += W.nlon; }
@@ -250,7 +275,8 @@ template <int V, int PD> struct QsSrcEta {
 // uo: zonal pressure gradient (ocean.py:306-336)
 template <int V, int PD> struct QsSrcOcnU {
     const QsOcnArgs& A; const QsW& W; qs_rsrc E, U, Vv, T, L; bool defer; double em, cap;
-    double e[PD], u0[PD], v0[PD], tx[PD]; int ld[PD]; unsigned ro;
+    double e[PD], u0[PD], v0[PD], tx[PD]; int ld[PD]; unsigned ro; double* sy = nullptr;
+    __device__ __forceinline__ void settle(bool&) { if (sy) em = qs_mean_handover(A, sy, false); }
     template <int K> __device__ __forceinline__ void load() {
         e[K % PD] = qs_ld(E, ro, W.vo); u0[K % PD] = qs_ld(U, ro, W.vo); v0[K % PD] = qs_ld(Vv, ro, W.vo); tx[K % PD] = qs_ld(T, ro, W.vo);
         ld[K % PD] = qs_ld8(L, ro, W.vo8);
@@ -280,17 +306,23 @@ template <int V, int PD> struct QsSrcOcnV {
     const QsOcnArgs& A; const QsW& W; qs_rsrc E, U, Vv, T, L; bool defer; double em, cap;
     double es, ec, en[PD], u0[PD], v0[PD], ty[PD]; int ld[PD];  // es, ec: eta rows g-1, g (as the kernel sees them); en: raw rows g+1 .. g+4
     unsigned ro;                                                               // row g+4
+    double* sy = nullptr;
     template <int K> __device__ __forceinline__ void load() {
         u0[K % PD] = qs_ld(U, ro, W.vo); v0[K % PD] = qs_ld(Vv, ro, W.vo); ty[K % PD] = qs_ld(T, ro, W.vo);
         ld[K % PD] = qs_ld8(L, ro, W.vo8);
         ro += W.nlon;
         en[K % PD] = qs_ld(E, ro, W.vo);
     }
-    __device__ __forceinline__ void start(int g0, bool& bad) {
-        es = qs_eta<V>(qs_ld(E, qs_off_roll(A.G, g0 - 1), W.vo), defer, em, cap, bad);      // g0 = 0: the other pole's row
+    __device__ __forceinline__ void start(int g0, bool&) {
+        es = qs_ld(E, qs_off_roll(A.G, g0 - 1), W.vo);                                     // g0 = 0: the other pole's row
         ro = qs_off(A.G, g0);
-        ec = qs_eta<V>(qs_ld(E, ro, W.vo), defer, em, cap, bad);
+        ec = qs_ld(E, ro, W.vo);                                                            // (both raw until settle())
         load<0>(); if (PD > 1) load<1>(); if (PD > 2) { load<2>(); load<3>(); }
+    }
+    __device__ __forceinline__ void settle(bool& bad) {
+        if (sy) em = qs_mean_handover(A, sy, false);
+        es = qs_eta<V>(es, defer, em, cap, bad);
+        ec = qs_eta<V>(ec, defer, em, cap, bad);
     }
     template <int EDGE> __device__ __forceinline__ double eval(int g, double enr, double u, double v, double t, int land, bool& bad) {
         if (EDGE) { if (g == W.n - 1) enr = qs_ld(E, qs_off_roll(A.G, g + 1), W.vo); }            // row n is row 0
@@ -398,7 +430,7 @@ __device__ __forceinline__ bool qs_del4_stream(SRC& S, const QdGeom& G, const Qs
     const int n = W.n, o0 = W.o0, o1 = W.o1;
     bool bad = false;
     if (fp->skip) {                                          // k4 <= 0 early-out of _hyperdiffuse: the field passes through
-        S.start(o0, bad);
+        S.start(o0, bad); S.settle(bad);
 #define QS_PASS(K) if (g + K < o1) { const int gg = g + K; \
             const double x = (gg == 0 || gg == n - 1) ? S.template get_edge<K>(gg, bad) : S.template get<K>(gg, bad); \
             out.put(x); QS_REFILL(S, K); }
@@ -411,7 +443,7 @@ __device__ __forceinline__ bool qs_del4_stream(SRC& S, const QdGeom& G, const Qs
     QsPipe p{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, (qd_cptr)(unsigned long long)tab + 4u * (unsigned)o0};
     if (!top) {
         // rows o0-4 .. o0+3: four rows of F, then two with Gb, two with D, two with Gb(D)
-        S.start(o0 - 4, bad);
+        S.start(o0 - 4, bad); S.settle(bad);
         qs_step<0, 0, V>(S, p, o0 - 4, W, tab, dt, out, bad);
         qs_step<0, 1, V>(S, p, o0 - 3, W, tab, dt, out, bad);
         qs_step<1, 2, V>(S, p, o0 - 2, W, tab, dt, out, bad);
@@ -423,7 +455,7 @@ __device__ __forceinline__ bool qs_del4_stream(SRC& S, const QdGeom& G, const Qs
     } else {
         // south pole: rows 0 .. 3; the one-sided difference pA0 (X_1 - X_0) stands in for Ga of rows 0 and 1, in both stages
         const double pA0 = qd_sload(poleA, 0);
-        S.start(0, bad);
+        S.start(0, bad); S.settle(bad);
         const double x0 = qs_nn<V>(S.template get_edge<0>(0, bad));
         QS_REFILL(S, 0);
         const double x1 = qs_nn<V>(S.template get<1>(1, bad));
@@ -560,21 +592,39 @@ __device__ __forceinline__ bool qs_dyn_wave(const QsDynArgs& A, const QsW& W, in
 }
 
 // fp: the wave's field record (kernarg segment of the calling kernel); out: where its rows go
+// sy / em_io: only k_ocn_stream passes them, and only it may be launched with A.acc_read (the mean handed over inside the workgroup:
+// see qs_mean_handover).  sy: the workgroup's LDS word on a wave's first pass, nullptr on its EXACT re-run, which takes *em_io.
 template <int V, class OUT>
-__device__ __forceinline__ bool qs_ocn_wave(const QsOcnArgs& A, const QsW& W, int wv, const QsRec QD_CONST* fp, OUT& out) {
-    const bool defer = A.eta_mean != nullptr;
-    const double em = defer ? *A.eta_mean : 0.0;
+__device__ __forceinline__ bool qs_ocn_wave(const QsOcnArgs& A, const QsW& W, int wv, const QsRec QD_CONST* fp, OUT& out,
+                                            double* sy = nullptr, double* em_io = nullptr) {
+    const bool handover = em_io != nullptr && A.acc_read != nullptr;
+    const bool defer = handover || A.eta_mean != nullptr;
+    const double em = handover ? *em_io : (defer ? *A.eta_mean : 0.0);
+    if (!handover) sy = nullptr;
     const double cap = (V == QS_EXACT || defer) ? A.eta_cap : __builtin_inf();
     const unsigned sb = W.slab_bytes;
     const qs_rsrc E = qs_make_rsrc(A.eta, sb);
+    bool bad;
     if (wv <= 1) {
         const qs_rsrc U = qs_make_rsrc(A.uo, sb), Vv = qs_make_rsrc(A.vo, sb), T = qs_make_rsrc(fp->aux, sb), L = qs_make_rsrc(A.land, sb / 8u);
-        if (wv == 0) { QsSrcOcnU<V, QS_PD_OCN> S{A, W, E, U, Vv, T, L, defer, em, cap}; return qs_del4_stream<V>(S, A.G, W, A.poleA, fp, A.sub_dt, out); }
+        if (wv == 0) {
+            QsSrcOcnU<V, QS_PD_OCN> S{A, W, E, U, Vv, T, L, defer, em, cap};
+            S.sy = sy;
+            bad = qs_del4_stream<V>(S, A.G, W, A.poleA, fp, A.sub_dt, out);
+            if (handover) *em_io = S.em;
+            return bad;
+        }
         QsSrcOcnV<V, QS_PD_OCN> S{A, W, E, U, Vv, T, L, defer, em, cap};
-        return qs_del4_stream<V>(S, A.G, W, A.poleA, fp, A.sub_dt, out);
+        S.sy = sy;
+        bad = qs_del4_stream<V>(S, A.G, W, A.poleA, fp, A.sub_dt, out);
+        if (handover) *em_io = S.em;
+        return bad;
     }
     QsSrcEta<V, QS_PD_OCN> S{A, W, E, defer, em, cap};
-    return qs_del4_stream<V>(S, A.G, W, A.poleA, fp, A.sub_dt, out);
+    S.sy = sy;
+    bad = qs_del4_stream<V>(S, A.G, W, A.poleA, fp, A.sub_dt, out);
+    if (handover) *em_io = S.em;
+    return bad;
 }
 
 

@@ -77,13 +77,17 @@ k_ocn_stream(QsOcnArgs A) {
     if (wv <= 1) __builtin_amdgcn_s_setprio(2);             // the momentum waves are the long ones of a strip (measured: -5 % on k_ocn_stream)
     const QsOcnArgs QD_CONST* Ak = (const QsOcnArgs QD_CONST*)__builtin_amdgcn_kernarg_segment_ptr();
     const QsRec QD_CONST* fp = &Ak->rec[wv];
+    // A.acc_read: the eta wave finishes the previous sub-step's mean and hands it over in s_em (qd_stream.h: qs_mean_handover).  Every
+    // wave meets the hand-over's barrier in its FIRST pass over the strip, whichever that is; a re-run carries the mean in `em`.
+    __shared__ double s_em;
+    double em = 0.0;
     if (!A.exact) {
         QsOutGlobal out{qs_make_rsrc(fp->out, W.slab_bytes), qs_off(A.G, W.o0), W.vs, (unsigned)W.nlon};
-        const bool bad = qs_ocn_wave<QS_FAST>(A, W, wv, fp, out);
+        const bool bad = qs_ocn_wave<QS_FAST>(A, W, wv, fp, out, &s_em, &em);
         if (__builtin_amdgcn_ballot_w64(bad) == 0ull) return;
     }
     QsOutGlobal out{qs_make_rsrc(fp->out, W.slab_bytes), qs_off(A.G, W.o0), W.vs, (unsigned)W.nlon};
-    qs_ocn_wave<QS_EXACT>(A, W, wv, fp, out);
+    qs_ocn_wave<QS_EXACT>(A, W, wv, fp, out, A.exact ? &s_em : (double*)nullptr, &em);
 }
 
 // =========================================================================================
@@ -292,6 +296,7 @@ int qd_launch_ocn_stream(qd_ctx* c, const QdOcnArgs& P, int margin) {
     double* out[3] = {P.uo_out, P.vo_out, P.eta_out};
     for (int f = 0; f < 3; ++f) A.rec[f] = QsRec{in[f], aux[f], out[f], tab + (size_t)f * c->geo.nlat * 4, P.skip[f], 0};
     A.eta_mean = P.eta_mean; A.eta_cap = P.eta_cap; A.sub_dt = P.sub_dt; A.g = P.g; A.r_bot = P.r_bot;
+    A.acc_read = P.acc_read; A.acc_partial = P.acc_partial; A.acc_n = P.acc_n; A.acc_wsum = P.acc_wsum;      // only this launcher starts k_ocn_stream itself
     A.inv_2dlon = P.inv_2dlon; A.inv_2dlat = P.inv_2dlat; A.inv_a = P.inv_a; A.inv_rhoH = P.inv_rhoH;
     A.exact = c->fused_fast == 2;
     QdScope sc(c, "k_ocn_hyper", c->geo.full != 0);

@@ -91,21 +91,40 @@ __device__ __forceinline__ bool qd_acc_arrive(unsigned long long* acc, unsigned 
     if (__hip_atomic_fetch_add(a + 2, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != in_slot - 1u) return false;
     return __hip_atomic_fetch_add(acc + QD_ACC_SLOTS * QD_ACC_STRIDE, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == slots - 1u;
 }
-// the finishing wave (all 64 lanes): total / (wsum + 1e-15) -- wsum < 0: the raw total (latitude bands all-reduce it first) -- and
-// everything cleared for the next launch
-__device__ __forceinline__ double qd_acc_finish(unsigned long long* acc, const double* partial, int n, double wsum) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long* s = acc + QD_ACC_STRIDE * lane;
-    long long hi = (long long)__hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    long long lo = (long long)__hip_atomic_load(s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long fl = __hip_atomic_load(s + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// ---- the same sum FINISHED BY THE NEXT LAUNCH (whole-globe ocean sub-steps whose next launch is k_ocn_stream) ----------------------
+// The four dependent round trips at the end of the producing launch (wait for the adds, slot ticket, launch ticket, the finisher's
+// loads) run while one wave works and the rest of the chip waits.  A consumer whose workgroups are all resident in one round can
+// do without them: the producer only issues its two fire-and-forget adds (qd_acc_add) -- the kernel boundary completes them -- and
+// one wave of EVERY workgroup of the consumer reads the 64 slots for itself (qd_acc_read: three loads per lane, lane = slot) behind
+// its first row loads.  Nobody is last, so nobody can clear: the slots come in two sets, used in turn, and a designated workgroup
+// of the launch AFTER the reader clears the set that reader saw (qd_acc_clear_set).  One reduction (qd_acc_reduce) for both forms:
+// the mean cannot differ by a bit.
+#define QD_ACC_SET_WORDS (QD_ACC_SLOTS * QD_ACC_STRIDE)
+#define QD_ACC_NEXT_SET(acc, k) ((acc) + 512 + (k) * QD_ACC_SET_WORDS)     // the two sets behind the ticketed one (host: 1024 words)
+__device__ __forceinline__ void qd_acc_add(unsigned long long* acc, unsigned w, double p) {
+    unsigned long long* a = acc + QD_ACC_STRIDE * (w & (QD_ACC_SLOTS - 1));
+    if (fabs(p) < 0x1p62) {                     // false for NaN
+        const double fl = floor(p);
+        __hip_atomic_fetch_add(a, (unsigned long long)(long long)fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(a + 1, (unsigned long long)(long long)((p - fl) * 0x1p50), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        __hip_atomic_fetch_or(a + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// all 64 lanes of one wave: every word of the set back to zero
+__device__ __forceinline__ void qd_acc_clear_set(unsigned long long* acc) {
+    unsigned long long* s = acc + QD_ACC_STRIDE * (threadIdx.x & 63);
 #pragma unroll
     for (int k = 0; k < QD_ACC_STRIDE; ++k) __hip_atomic_store(s + k, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (lane == 0) __hip_atomic_store(acc + QD_ACC_SLOTS * QD_ACC_STRIDE, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// all 64 lanes, lane = slot: (hi, lo, flag) of the lane's slot -> total / (wsum + 1e-15) in every lane (wsum < 0: the raw total).
+// Integer sums: any order gives the same total; the conversion and the division happen once, here.
+__device__ __forceinline__ double qd_acc_reduce(long long hi, long long lo, unsigned long long fl, const double* partial, int n, double wsum) {
+    const int lane = threadIdx.x & 63;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { hi += __shfl_down(hi, o, 64); lo += __shfl_down(lo, o, 64); fl |= __shfl_down(fl, o, 64); }
-    hi = __shfl(hi, 0, 64); lo = __shfl(lo, 0, 64); fl = __shfl(fl, 0, 64);
-    if (fl) {                                   // some partial was not representable: the f64 sum of the stored partials (coherent loads)
+    for (int o = 32; o > 0; o >>= 1) { hi += __shfl_down(hi, o, 64); lo += __shfl_down(lo, o, 64); }
+    hi = __shfl(hi, 0, 64); lo = __shfl(lo, 0, 64);
+    if (__builtin_amdgcn_ballot_w64(fl != 0ull) != 0ull) {   // some partial was not representable: the f64 sum of the stored partials (coherent loads)
         double a = 0.0;
         for (int k = lane; k < n; k += 64) a += __hip_atomic_load(partial + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
@@ -115,5 +134,26 @@ __device__ __forceinline__ double qd_acc_finish(unsigned long long* acc, const d
     }
     const double tot = (double)hi + (double)lo * 0x1p-50;
     return wsum < 0.0 ? tot : tot / (wsum + 1e-15);
+}
+// the reader of the next launch (all 64 lanes of one wave per workgroup): nothing is stored
+__device__ __forceinline__ double qd_acc_read(const unsigned long long* acc, const double* partial, int n, double wsum) {
+    const unsigned long long* s = acc + QD_ACC_STRIDE * (threadIdx.x & 63);
+    const long long hi = (long long)__hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const long long lo = (long long)__hip_atomic_load(s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long fl = __hip_atomic_load(s + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return qd_acc_reduce(hi, lo, fl, partial, n, wsum);
+}
+// the finishing wave (all 64 lanes): total / (wsum + 1e-15) -- wsum < 0: the raw total (latitude bands all-reduce it first) -- and
+// everything cleared for the next launch
+__device__ __forceinline__ double qd_acc_finish(unsigned long long* acc, const double* partial, int n, double wsum) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long* s = acc + QD_ACC_STRIDE * lane;
+    const long long hi = (long long)__hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const long long lo = (long long)__hip_atomic_load(s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long fl = __hip_atomic_load(s + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int k = 0; k < QD_ACC_STRIDE; ++k) __hip_atomic_store(s + k, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) __hip_atomic_store(acc + QD_ACC_SLOTS * QD_ACC_STRIDE, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return qd_acc_reduce(hi, lo, fl, partial, n, wsum);
 }
 

@@ -609,6 +609,18 @@ class Device:
         self.lib.qd_last_ocean_nsub(self.h, ctypes.byref(n))
         return n.value
 
+    def step_scalars(self):
+        """The device scalars a step's launches hand to each other (include/qingdai_hip.h: qd_step_scalars), by name."""
+        out = np.zeros(8)
+        self._chk(self.lib.qd_step_scalars(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "qd_step_scalars")
+        return dict(zip(("PREF", "ETA_MEAN", "MED_OUT", "PSCALE", "RENORM", "BLEND_W", "TMP0", "TMP1"), out))
+
+    def ocean_mean_next_count(self):
+        """Ocean sub-steps since create whose eta mean the next momentum launch finished (QD_MEAN_IN_MOMENTUM)."""
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.qd_ocean_mean_next_count(self.h, ctypes.byref(n)), "qd_ocean_mean_next_count")
+        return n.value
+
     def counters(self):
         a, o = ctypes.c_int64(0), ctypes.c_int64(0)
         self.lib.qd_get_step_counter(self.h, ctypes.byref(a), ctypes.byref(o))
