@@ -690,6 +690,26 @@ int qd_budget_diag_schedule(qd_handle h, int n, const int32_t* fire);
 int qd_budget_diag_log(qd_handle h, double* out, int max, int* n);   /* drains the log: *n records of QD_BUDGET_LOG_W doubles */
 int qd_budget_diag_reset(qd_handle h);                                /* log, schedule and the SST snapshot (ocean.py:476-479) forgotten */
 
+/* ---- time-mean history accumulators (QD_HISTORY), whole-globe handles ----------------------------------------------------
+ * Nothing the reference has: its loop leaves snapshots, no time means.  A span lane without a flag bit and without a log, like the
+ * budget diagnostics: a schedule given before a qd_step_n span turns it on for that span, and on every sampled step each entry's
+ * value is added to its resident sum plane, sum = sum + x in f64, in step order (no compensation; a NaN sample makes the cell
+ * NaN).  The value of a field for step s is what qd_download returns after a span that ends with step s: the entries that read
+ * PRECIP are sampled in front of the ocean step, inside which the next step's precipitation block may already run, every other
+ * entry behind the step's last launch -- at most two launches per sampled step, none on the others.  When an entry reads one of
+ * the lazily stored diagnostics (P_RAIN, S_SNOW_NEXT, MELT, C_SNOW, GLACIER, ISR_A, ISR_B, EFLUX, LHREL, OLR) a sampled step stores
+ * them.  The host divides the sums by the sample count (qingdai_amd/history.py). */
+#define QD_HISTORY_MAX_ENTRIES 32
+/* n entries: op[k] 0 = the f64 plane a[k]; 1 = sqrt(a*a + b*b) of the planes a[k], b[k], rounded as np.sqrt(u*u + v*v).  Allocates
+ * [n][n_lat][n_lon] sums, zeroed, and zeroes the sample count; forgets an earlier configuration; n == 0 only releases.  Refused:
+ * latitude bands, n > 32, an unknown op, a field id that is not an f64 plane (masks, maps the ecology keeps as f32), op 1 without
+ * b, op 1 that pairs PRECIP with another field. */
+int qd_history_configure(qd_handle h, int n, const int32_t* op, const int32_t* a, const int32_t* b);
+int qd_history_schedule(qd_handle h, int steps, const int32_t* sample);   /* the next qd_step_n span: non-zero = the step is sampled */
+int qd_history_sample(qd_handle h);                                      /* one sample of every entry now, outside a span (one launch) */
+int qd_history_read(qd_handle h, double* sums, int64_t* count);          /* the sums [n][n_lat][n_lon] and the samples in them */
+int qd_history_reset(qd_handle h);                                       /* sums and count back to zero */
+
 /* ---- reductions for diagnostics (energy.py:494-538, ocean.py:535-561) -------------- */
 /* compute_energy_diagnostics (energy.py:494-538) from the resident state, with the flux formulas of the driver's
  * coupling block (run_simulation.py:2199-2239): out[10] = cos-weighted global means of

@@ -54,6 +54,7 @@ SYMBOLS = [
     "qd_stateframe_configure", "qd_stateframe_scan", "qd_stateframe_render", "qd_stateframe_download",
     "qd_tiles_configure", "qd_tiles_set_plane", "qd_tiles_available", "qd_tiles_scan", "qd_tiles_order_stats", "qd_tiles_render", "qd_tiles_download",
     "qd_budget_diag_configure", "qd_budget_diag_schedule", "qd_budget_diag_log", "qd_budget_diag_reset",
+    "qd_history_configure", "qd_history_schedule", "qd_history_sample", "qd_history_read", "qd_history_reset",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
     "qd_route_download", "qd_route_events",
     "qd_hydronet_build", "qd_hydronet_sweeps",
@@ -150,6 +151,7 @@ PHYTO_DAILY_LOG_W = 4        # doubles per [PhytoDiag] record
 ECO_DAILY_LOG_W = 4          # doubles per daily vegetation record {firings, LAI_min, LAI_mean, LAI_max}
 INDIV_DAILY_LOG_W = 4        # doubles per record of the individuals' daily step {firings, beta_hint, n_cells, levels}
 BUDGET_LOG_W = 40           # doubles per budget diagnostics record (QD_BUDGET_LOG_W; budget_diag.REC names the slots)
+HISTORY_MAX_ENTRIES = 32     # QD_HISTORY_MAX_ENTRIES
 ROUTE_LOG_W = 8              # doubles per routing event record (routing.LOG_KEYS)
 
 # qd_step_n flags (include/qingdai_hip.h): bit k switches STEP_BITS[k], named as Device.step_n's keywords
@@ -280,6 +282,11 @@ def load():
     lib.qd_budget_diag_schedule.argtypes = [vp, i32, ip]
     lib.qd_budget_diag_log.argtypes = [vp, dp, i32, ip]
     lib.qd_budget_diag_reset.argtypes = [vp]
+    lib.qd_history_configure.argtypes = [vp, i32, ip, ip, ip]
+    lib.qd_history_schedule.argtypes = [vp, i32, ip]
+    lib.qd_history_sample.argtypes = [vp]
+    lib.qd_history_read.argtypes = [vp, dp, ctypes.POINTER(i64)]
+    lib.qd_history_reset.argtypes = [vp]
     lib.qd_comm_unique_id.argtypes = [vp, sz]
     lib.qd_comm_init.argtypes = [vp, vp, sz]
     lib.qd_comm_barrier.argtypes = [vp]

@@ -1,0 +1,206 @@
+// qd_history.hip -- time-mean history files: per-step accumulation of selected fields as a span lane, gfx950 (QD_HISTORY).
+//
+// An entry is an f64 plane (op 0) or sqrt(a*a + b*b) of two planes (op 1); its sum plane receives sum = sum + x on every sampled step
+// of a qd_step_n span (qd_history_schedule: one value per step, non-zero = sampled).  The lane has no flag bit and no log: a schedule
+// given before the span turns it on, the sums stay resident until the host reads them (qd_history_read) and divides by the sample
+// count, once (qingdai_amd/history.py).  A cell of a sum has one writer and the adds of a window come in step order, so the sums do
+// not depend on how a run is cut into spans: ((0 + x_1) + x_2) + ..., f64, no compensation, a NaN sample makes the cell NaN.
+//
+// A sample of step s is what qd_download returns after a span that ends with step s.  With the precipitation block of step s + 1
+// queued inside the ocean step of step s (QD_HOIST_PRECIP, qd_api.hip) PRECIP is overwritten before step s is over, so the entries
+// that read PRECIP -- the only field that block stores -- form the EARLY group, accumulated in front of the ocean step; every other
+// entry is in the LATE group, accumulated behind the last launch of the step.  A sampled step adds at most these two launches, an
+// unsampled step none.
+//
+// k_hist_accum: one launch for a whole group.  The table of (a, b, sum) pointers comes by value in the kernel arguments (32 x 24
+// bytes).  Grid-stride over PAIRS of cells, 16-byte loads and stores per lane (every plane starts 16-byte aligned: the fields are
+// allocations of their own, the sum planes have an even stride); an odd cell count leaves one cell to a scalar tail.  The entry loop
+// is unrolled by four: the loads of four entries are in flight before the first add.  The grid is sized from the CU count.  No LDS,
+// no atomics.  Whole-globe handles only.
+#include "qd_span.h"
+#include <algorithm>
+
+#define QD_HISTORY_MAX 32          // entries (include/qingdai_hip.h: QD_HISTORY_MAX_ENTRIES)
+#define QD_HIST_UNROLL 4
+
+struct QdHistEntry { const double* a; const double* b; double* sum; };        // b == nullptr: op 0
+struct QdHistTab { QdHistEntry e[QD_HISTORY_MAX]; int n; };
+
+__device__ __forceinline__ double hist_value(double a, double b, bool pair) { return pair ? sqrt(a * a + b * b) : a; }
+
+__global__ void __launch_bounds__(QD_BLOCK)
+k_hist_accum(QdHistTab T, size_t npairs, size_t cells) {
+    const size_t stride = (size_t)gridDim.x * QD_BLOCK;
+    for (size_t p = (size_t)blockIdx.x * QD_BLOCK + threadIdx.x; p < npairs; p += stride) {
+        for (int e0 = 0; e0 < T.n; e0 += QD_HIST_UNROLL) {
+            double2 x[QD_HIST_UNROLL], y[QD_HIST_UNROLL], s[QD_HIST_UNROLL];
+#pragma unroll
+            for (int k = 0; k < QD_HIST_UNROLL; ++k) {
+                if (e0 + k < T.n) {
+                    const QdHistEntry E = T.e[e0 + k];
+                    x[k] = reinterpret_cast<const double2*>(E.a)[p];
+                    y[k] = E.b ? reinterpret_cast<const double2*>(E.b)[p] : make_double2(0.0, 0.0);
+                    s[k] = reinterpret_cast<const double2*>(E.sum)[p];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < QD_HIST_UNROLL; ++k) {
+                if (e0 + k < T.n) {
+                    const QdHistEntry E = T.e[e0 + k];
+                    const bool pair = E.b != nullptr;
+                    double2 r;
+                    r.x = s[k].x + hist_value(x[k].x, y[k].x, pair);
+                    r.y = s[k].y + hist_value(x[k].y, y[k].y, pair);
+                    reinterpret_cast<double2*>(E.sum)[p] = r;
+                }
+            }
+        }
+    }
+    // odd cell count: the last cell, one thread per entry
+    if ((cells & 1) && blockIdx.x == 0 && (int)threadIdx.x < T.n) {
+        const QdHistEntry E = T.e[threadIdx.x];
+        const size_t o = cells - 1;
+        E.sum[o] = E.sum[o] + hist_value(E.a[o], E.b ? E.b[o] : 0.0, E.b != nullptr);
+    }
+}
+
+struct QdHistory {
+    int n = 0;
+    int op[QD_HISTORY_MAX], a[QD_HISTORY_MAX], b[QD_HISTORY_MAX];
+    bool early[QD_HISTORY_MAX];       // the entry reads PRECIP: sampled in front of the ocean step
+    bool lazy = false;                // an entry reads one of the lazily stored diagnostics (QD_LAZY_DIAG)
+    double* sums = nullptr;           // [n][stride]
+    size_t stride = 0;                // cells rounded up to even: every sum plane starts 16-byte aligned
+    int64_t count = 0;                // samples in the sums
+    QdSpanLane lane;                  // width 0: no log
+};
+
+static QdSpanLane* hist_lane(qd_ctx* c) { return c && c->history ? &c->history->lane : nullptr; }
+
+void qd_history_release(qd_ctx* c) {
+    QdHistory* h = c->history;
+    if (!h) return;
+    if (c->stream) hipStreamSynchronize(c->stream);
+    if (h->sums) hipFree(h->sums);
+    delete h;
+    c->history = nullptr;
+}
+
+// the fields nothing inside a span reads and only a span's last step stores (qd_internal.h: lazy_diag)
+static bool hist_lazy_field(int f) {
+    static const int L[] = {QD_F_P_RAIN, QD_F_S_SNOW_NEXT, QD_F_MELT, QD_F_C_SNOW, QD_F_GLACIER, QD_F_ISR_A, QD_F_ISR_B, QD_F_EFLUX, QD_F_LHREL, QD_F_OLR};
+    return std::find(std::begin(L), std::end(L), f) != std::end(L);
+}
+static bool hist_plane(const qd_ctx* c, int f) { return f >= 0 && f < QD_F_COUNT_F64 && !qd_eco_is_f32(c, f); }
+
+extern "C" int qd_history_configure(qd_handle c, int n, const int32_t* op, const int32_t* a, const int32_t* b) {
+    if (!c || n < 0 || (n && (!op || !a))) return -1;
+    if (!qd_whole_globe(c))
+        return qd_fail(c, "qd_history_configure: the history accumulators need a whole-globe handle (world == 1, n_rows == n_lat); "
+                          "latitude bands are not supported");
+    if (n > QD_HISTORY_MAX) return qd_fail(c, "qd_history_configure: at most 32 entries");
+    QdHistory t;
+    for (int k = 0; k < n; ++k) {
+        if (op[k] != 0 && op[k] != 1) return qd_fail(c, "qd_history_configure: unknown op (0 = field a, 1 = sqrt(a*a + b*b))");
+        if (!hist_plane(c, a[k])) return qd_fail(c, "qd_history_configure: field a is not an f64 plane");
+        if (op[k] == 1 && !b) return qd_fail(c, "qd_history_configure: op 1 needs a second field b");
+        if (op[k] == 1 && !hist_plane(c, b[k])) return qd_fail(c, "qd_history_configure: field b is not an f64 plane");
+        t.op[k] = op[k]; t.a[k] = a[k]; t.b[k] = op[k] == 1 ? b[k] : -1;
+        t.early[k] = a[k] == QD_F_PRECIP || t.b[k] == QD_F_PRECIP;
+        if (t.early[k] && op[k] == 1 && a[k] != b[k])
+            return qd_fail(c, "qd_history_configure: op 1 cannot pair PRECIP with another field (they are sampled at different places of a step)");
+        t.lazy = t.lazy || hist_lazy_field(a[k]) || (op[k] == 1 && hist_lazy_field(b[k]));
+    }
+    hipSetDevice(c->desc.device);
+    qd_history_release(c);
+    if (n == 0) return 0;
+    QdHistory* h = new QdHistory(t);
+    h->n = n;
+    h->stride = (c->geo.cells() + 1) & ~(size_t)1;
+    const size_t bytes = (size_t)n * h->stride * sizeof(double);
+    const bool ok = hipMalloc(&h->sums, bytes) == hipSuccess && hipMemsetAsync(h->sums, 0, bytes, c->stream) == hipSuccess &&
+                    hipStreamSynchronize(c->stream) == hipSuccess;
+    c->history = h;
+    if (!ok) { qd_history_release(c); return qd_fail(c, "qd_history_configure: device allocation failed"); }
+    return 0;
+}
+
+extern "C" int qd_history_schedule(qd_handle c, int steps, const int32_t* sample) {
+    return qd_lane_schedule(c, hist_lane(c), steps, sample, "qd_history_schedule", "not configured (qd_history_configure first)");
+}
+
+bool qd_history_scheduled(const qd_ctx* c) { return c->history && !c->history->lane.sched.empty(); }
+bool qd_history_reads_lazy(const qd_ctx* c) { return c->history && c->history->lazy; }
+
+// the ecology may have turned a selected map into an f32 slab since the configure (qd_eco_params.map_f32)
+static bool hist_stale(const qd_ctx* c) {
+    const QdHistory* h = c->history;
+    for (int k = 0; h && k < h->n; ++k)
+        if (!hist_plane(c, h->a[k]) || (h->op[k] == 1 && !hist_plane(c, h->b[k]))) return true;
+    return false;
+}
+
+QdSpanLane* qd_history_span_begin(qd_ctx* c, int n) {
+    static const QdSpanTexts T = {
+        "qd_step_n: the history accumulators need a whole-globe handle; latitude bands are not supported",
+        "qd_step_n: qd_history_configure has not been called",
+        "qd_step_n: a qd_history_schedule must cover exactly the n steps of the span",
+        "qd_step_n: a span samples the history at most QD_SPAN_LOG_CAP times"};
+    QdSpanLane* l = qd_lane_span_begin(c, hist_lane(c), n, T, nullptr,
+                                       hist_stale(c) ? "qd_step_n: a history field is no longer an f64 plane (qd_history_configure again)" : nullptr);
+    if (!l && c->history) c->history->lane.clear_schedule();      // refused: the span guard never sees this lane, and a schedule serves one span
+    return l;
+}
+
+// group 0: the early entries, 1: the late entries (the sample count moves on with them), 2: all of them (the class seam)
+int qd_history_accumulate(qd_ctx* c, int group) {
+    QdHistory* h = c->history;
+    QdHistTab T;
+    T.n = 0;
+    for (int k = 0; k < h->n; ++k) {
+        if (group != 2 && h->early[k] != (group == 0)) continue;
+        T.e[T.n++] = QdHistEntry{c->f[h->a[k]], h->op[k] == 1 ? c->f[h->b[k]] : (const double*)nullptr, h->sums + (size_t)k * h->stride};
+    }
+    for (int k = T.n; k < QD_HISTORY_MAX; ++k) T.e[k] = QdHistEntry{nullptr, nullptr, nullptr};
+    if (group != 0) h->count++;
+    if (T.n == 0) return 0;
+    QdScope sc(c, "history", true);                       // one launch: timed from the dispatch itself
+    const size_t cells = c->geo.cells(), npairs = cells / 2;
+    const size_t want = std::max<size_t>(1, (npairs + QD_BLOCK - 1) / QD_BLOCK);
+    const int blocks = (int)std::min<size_t>(want, (size_t)std::max(1, c->n_cu) * 8);
+    QD_LAUNCH_TIMED(sc, k_hist_accum, dim3(blocks), dim3(QD_BLOCK), c->stream, T, npairs, cells);
+    return 0;
+}
+
+extern "C" int qd_history_sample(qd_handle c) {
+    if (!c) return -1;
+    if (!c->history) return qd_fail(c, "qd_history_sample: not configured (qd_history_configure first)");
+    if (hist_stale(c)) return qd_fail(c, "qd_history_sample: a history field is no longer an f64 plane (qd_history_configure again)");
+    hipSetDevice(c->desc.device);
+    if (int rc = qd_history_accumulate(c, 2)) return rc;
+    return qd_launch_check(c, "qd_history_sample");
+}
+
+extern "C" int qd_history_read(qd_handle c, double* sums, int64_t* count) {
+    if (!c || !sums || !count) return -1;
+    QdHistory* h = c->history;
+    if (!h) return qd_fail(c, "qd_history_read: not configured (qd_history_configure first)");
+    hipSetDevice(c->desc.device);
+    const size_t row = c->geo.cells() * sizeof(double);
+    QD_HIP(c, hipMemcpy2DAsync(sums, row, h->sums, h->stride * sizeof(double), row, (size_t)h->n, hipMemcpyDeviceToHost, c->stream));
+    QD_HIP(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return qd_fail(c, "qd_history_read: kernel", e);
+    *count = h->count;
+    return 0;
+}
+
+extern "C" int qd_history_reset(qd_handle c) {
+    if (!c) return -1;
+    QdHistory* h = c->history;
+    if (!h) return qd_fail(c, "qd_history_reset: not configured (qd_history_configure first)");
+    hipSetDevice(c->desc.device);
+    QD_HIP(c, hipMemsetAsync(h->sums, 0, (size_t)h->n * h->stride * sizeof(double), c->stream));
+    h->count = 0;
+    return 0;
+}

@@ -212,6 +212,7 @@ struct qd_ctx {
     struct QdTiles* tiles = nullptr;         // tile renderer of the ecology / plankton / ISR figures: mosaic, select state, host stack (qd_tiles.hip)
     struct QdStateFrame* sframe = nullptr;   // 15-panel state frame: parameters, mosaic, vorticity plane, partials (qd_stateframe.hip)
     struct QdBudget* budget = nullptr;       // periodic budget diagnostics: schedule, SST snapshot, row partials, log (qd_budget_diag.hip)
+    struct QdHistory* history = nullptr;     // time-mean history: entry table, sum planes, sample count, schedule (qd_history.hip)
     double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
     int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
     double topogen_ms = -1.0;        // device time (events) of the kernels of the last qd_topogen_build on this handle (qd_topogen.hip)
@@ -516,6 +517,13 @@ int  qd_budget_ocean_energy(qd_ctx* c, double dt, int use_ice_mask);            
 int  qd_budget_ocean(qd_ctx* c, double fire);
 int  qd_budget_humidity(qd_ctx* c, double fire);
 int  qd_budget_water(qd_ctx* c, double fire, int with_route);
+// qd_history.hip: the lane is on for a span when a schedule has been given; group 0 = the entries that read PRECIP (in front of the
+// ocean step), 1 = the others (behind the step's last launch; the sample count moves on with them)
+void qd_history_release(qd_ctx* c);
+bool qd_history_scheduled(const qd_ctx* c);
+bool qd_history_reads_lazy(const qd_ctx* c);                                    // an entry reads a lazily stored diagnostic (lazy_diag)
+struct QdSpanLane* qd_history_span_begin(qd_ctx* c, int n);
+int  qd_history_accumulate(qd_ctx* c, int group);
 const double* qd_route_last_record(const qd_ctx* c);                             // qd_route.hip: the last event's record on the device, or nullptr
 const double* qd_route_flow(const qd_ctx* c);                                    // qd_route.hip: the resident flow map [cells], or nullptr
 bool qd_phyto_daily_bands(const qd_ctx* c, const double** bands, int* n_bands, int64_t* n_steps);   // qd_phyto_daily.hip: the resident band stack, when configured

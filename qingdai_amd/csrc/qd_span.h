@@ -2,7 +2,8 @@
 // device log the host drains afterwards.  Three lanes: river routing (bit7, qd_route.hip), the daily phytoplankton step (bit8,
 // qd_phyto_daily.hip), the daily vegetation step (bit9, qd_eco_daily.hip); the individuals' daily step
 // (qd_indiv_daily.hip) fires with bit9 and keeps a log of its own; the budget diagnostics (qd_budget_diag.hip) have no flag bit:
-// a schedule given before the span turns them on.
+// a schedule given before the span turns them on; so it is with the history accumulators (qd_history.hip), which keep sum planes
+// instead of a log (width 0).
 //   qd_X_schedule           qd_lane_schedule: one value per step of the NEXT span, 0 = the step does not fire
 //   qd_step_n, before work  qd_lane_span_begin: exactly n steps scheduled, and their firings fit into the log behind the cursor
 //   qd_step_n, step s       at(s) != 0: X runs (not when full()) and writes its record at next()
@@ -13,7 +14,7 @@
 #include "qd_internal.h"
 
 #define QD_SPAN_LOG_CAP 4096        // records a lane holds between two drains (qingdai_amd/_lib.py: SPAN_LOG_CAP is the same number)
-enum { QD_LANE_ROUTE = 0, QD_LANE_PHYTO_DAILY, QD_LANE_ECO_DAILY, QD_LANE_INDIV_DAILY, QD_LANE_BUDGET, QD_N_LANES };
+enum { QD_LANE_ROUTE = 0, QD_LANE_PHYTO_DAILY, QD_LANE_ECO_DAILY, QD_LANE_INDIV_DAILY, QD_LANE_BUDGET, QD_LANE_HISTORY, QD_N_LANES };
 
 struct QdSpanLane {
     double* log = nullptr;          // device, [QD_SPAN_LOG_CAP][width]; the subsystem sets width, allocates and frees it

@@ -130,7 +130,7 @@ class Device:
         self._chk(self.lib.qd_hydrology_commit(self.h, float(dt)), "qd_hydrology_commit")
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
-               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None):
+               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  `routing`: a RiverRouting on this handle -- bit7, after the
         hydrology commit (which it needs); the host's t_accum schedule names the event steps, and the span's
@@ -140,12 +140,14 @@ class Device:
         ecology.PopulationDaily on this handle -- bit9 (needs `ecology`); its day accumulator names the firing steps, and the span's
         LAI summaries stay in the device log (eco_daily_log) until the caller drains them.  `budget`: a budget_diag.BudgetDiag on
         this handle -- no flag bit: its schedule (run-local step index, the ocean's step count) turns the lane on for the span, and
-        the records stay in the device log (budget_diag_log) until the caller drains them."""
+        the records stay in the device log (budget_diag_log) until the caller drains them.  `history`: a history.History on this
+        handle -- no flag bit either: its window clock names the sampled steps, whose fields are added to the resident sums
+        (history_read)."""
         self.flush()
         st = np.ascontiguousarray(stars, dtype=np.float64)
         assert st.ndim == 2 and st.shape[1] == 7
         n = int(st.shape[0])
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget) if p is not None]          # the span's participants (csrc/qd_span.h)
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history) if p is not None]          # the span's participants (csrc/qd_span.h)
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -246,6 +248,37 @@ class Device:
 
     def budget_diag_reset(self):
         self._chk(self.lib.qd_budget_diag_reset(self.h), "qd_budget_diag_reset")
+
+    # ---- time-mean history accumulators (qd_history.hip)
+    def history_configure(self, entries):
+        """entries: [(op, a, b)] with a, b field names as `get` takes them (b None for op 0): op 0 = the plane a,
+        1 = sqrt(a*a + b*b).  An empty list releases the accumulators."""
+        ip = ctypes.POINTER(ctypes.c_int32)
+        op = _c([e[0] for e in entries], np.int32)
+        a = _c([F[e[1]] for e in entries], np.int32)
+        b = _c([F[e[2]] if e[2] is not None else -1 for e in entries], np.int32)
+        self._chk(self.lib.qd_history_configure(self.h, len(entries), op.ctypes.data_as(ip), a.ctypes.data_as(ip), b.ctypes.data_as(ip)),
+                  "qd_history_configure")
+        self._history_n = len(entries)
+
+    def history_schedule(self, sample):
+        f = _c(sample, np.int32)
+        self._chk(self.lib.qd_history_schedule(self.h, int(f.size), f.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "qd_history_schedule")
+
+    def history_sample(self):
+        """One sample of every entry from the fields as they stand (the class seam)."""
+        self.flush()
+        self._chk(self.lib.qd_history_sample(self.h), "qd_history_sample")
+
+    def history_read(self):
+        """-> (sums [n][n_lat][n_lon], sample count)"""
+        out = np.empty((getattr(self, "_history_n", 0),) + self.shape, dtype=np.float64)
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.qd_history_read(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(n)), "qd_history_read")
+        return out, int(n.value)
+
+    def history_reset(self):
+        self._chk(self.lib.qd_history_reset(self.h), "qd_history_reset")
 
     # ---- daily phytoplankton step (qd_phyto_daily.hip)
     def phyto_daily_configure(self, params, band_tab, species_tab, shape):

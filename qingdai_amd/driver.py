@@ -80,6 +80,17 @@ and its ocean's [OceanE] on the ocean's own step count % QD_OCEAN_DIAG_EVERY, se
 QD_OCEAN_DIAG, QD_OCEAN_ENERGY_DIAG, QD_HUMIDITY_DIAG, QD_WATER_DIAG (all default 1) and QD_OCEAN_POLAR_LAT.  A fourth span lane
 (qingdai_amd/budget_diag.py, qd_budget_diag_*): chunks are NOT cut at firing steps; the device reduces at the reference's positions
 inside the step and each chunk's lines are printed after it, in the reference's order and formats.
+Time-mean history files (QD_HISTORY=1, default 0; nothing the reference has): every QD_HISTORY_SAMPLE_EVERY-th (default 1) step of a
+window of QD_HISTORY_EVERY_DAYS (default 10) planet-days -- S = max(1, int(days * day / dt + 0.5)) steps, counted on the run-local
+step index from where the lane is enabled, so after a resume the windows start again at the resumed step and an open window does not
+survive an autosave -- the fields of QD_HISTORY_FIELDS (f64 planes by their Device.get names, WIND_SPEED, CURRENT_SPEED; default TS,
+H, U, V, Q, CLOUD, HICE, PRECIP, ALBEDO, ISR, OLR, EFLUX, PCOND, W_LAND, S_SNOW, RUNOFF, WIND_SPEED and with the ocean SST, UO, VO, ETA,
+QNET, CURRENT_SPEED; an unknown name or a field of a subsystem that is off is refused at start-up) are added into resident sums by a
+fifth span lane (qingdai_amd/history.py, qd_history_*).  A chunk ends with a window's last step, behind which
+<QD_OUTPUT_DIR>/history/history_day_{a}_{b}.nc (the means, n_samples, t_start_seconds, t_end_seconds, dt_seconds, sample_every,
+complete) is written and one [History] line printed; a and b are the start times over `day` of the first and last sampled step,
+`05.1f` like the frames (more decimals for windows shorter than 0.1 day).  The normal end of main writes the open window with
+complete = 0; the signal path does not.
 State frames (QD_STATE_PLOT=1, default 0; the same plot clock; plot_state, run_simulation.py:330-537, 2426-2428): the reference's
 15-panel status figure as a mosaic of 5 x 3 tiles of n_lat x n_lon pixels -- every tile its contourf sampled at the cell centres,
 with the coast, river, lake and star-position overlays, no titles, axes or colourbars -- composed on the device from the resident
@@ -337,6 +348,7 @@ class Simulation:
             if diag:
                 print("[Phyto] Manager initialized.")
         self.budget = None                                     # enable_budget_diag (QD_BUDGET_DIAG=1)
+        self.history = None                                    # enable_history (QD_HISTORY=1)
         # banded initial surface temperature (run_simulation.py:310-328)
         if int(env.get("QD_INIT_BANDED", "0")) == 1:
             T_eq, T_pole = float(env.get("QD_INIT_T_EQ", "295.0")), float(env.get("QD_INIT_T_POLE", "265.0"))
@@ -738,7 +750,7 @@ class Simulation:
                 self.eco.banded_alpha()
             self._export_genes(t_i, float(a))
         lane.struck = int(fire[0])
-        self._run_lanes(1, energy_diag)
+        self._run_cut(1, energy_diag)
 
     def _export_genes(self, t_i, accum_after):
         """QD_ECO_GENES_EXPORT=1: genes_day_*.json of one firing, named by (t_i - accum_after) / day (run_simulation.py:1847-1861:
@@ -757,11 +769,32 @@ class Simulation:
             if k is None:
                 break
             if k > 0:
-                self._run_lanes(k, energy_diag)
+                self._run_cut(k, energy_diag)
             self._speciation_step(energy_diag)
             n -= k + 1
         if n > 0:
-            self._run_lanes(n, energy_diag)
+            self._run_cut(n, energy_diag)
+
+    def _run_cut(self, n, energy_diag=False):
+        """n steps through _run_lanes; under QD_HISTORY=1 cut so that a chunk ends with a window's last step, behind which the
+        window's file is written (the sums then start the next window from zero)."""
+        hist = getattr(self, "history", None)
+        while n > 0:
+            k = n if hist is None else min(n, hist.steps_to_window_end())
+            self._run_lanes(k, energy_diag)
+            n -= k
+            if hist is not None and hist.window_closed():
+                self.flush_history()
+
+    def flush_history(self, complete=1):
+        """Write the history window that stands in the accumulators -> the path or None.  A failure is reported and the window is
+        dropped (the next one starts from zero): output never stops the run."""
+        try:
+            return self.history.flush(complete=complete)
+        except Exception as e:      # noqa: BLE001
+            print(f"[History] window skipped: {e}")
+            self.history.drop()
+            return None
 
     def _run_lanes(self, n, energy_diag=False):
         origin = self._t_origin
@@ -776,6 +809,8 @@ class Simulation:
         if budget is not None:
             budget.routed = routing is not None
             lanes["budget"] = budget
+        if getattr(self, "history", None) is not None:
+            lanes["history"] = self.history                    # samples into the resident sums; nothing to drain behind the span
         try:
             self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
                             with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto_transport,
@@ -822,6 +857,15 @@ class Simulation:
         self.budget = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
                                routed=getattr(self, "routing", None) is not None)
         return self.budget
+
+    def enable_history(self, env=None):
+        """QD_HISTORY=1: time means of the selected fields over windows of QD_HISTORY_EVERY_DAYS planet-days, accumulated by a device
+        lane and written to <QD_OUTPUT_DIR>/history/ (qingdai_amd/history.py) -> the History or None.  The run-local step index the
+        windows count on starts where this is called.  An unknown field name raises here, before the loop."""
+        from .history import from_env
+        self.history = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
+                                dt=float(self.dt), day=self.day_seconds)
+        return self.history
 
     def enable_routing(self, env=None):
         """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
@@ -1054,6 +1098,7 @@ def main(argv=None):
             sim.t = float(env["QD_ORBIT_EPOCH_DAYS"]) * day
     sim.enable_routing(env)
     sim.enable_budget_diag(env)
+    sim.enable_history(env)
     sim.bootstrap_ecology()
     t0 = sim.t
     n_total = len(np.arange(t0, t0 + duration, sim.dt))
@@ -1124,6 +1169,8 @@ def main(argv=None):
             state["saved"] = False
             while next_autosave_t <= sim.t + 1e-9 * sim.dt:
                 next_autosave_t += autosave_dt
+    if sim.history is not None:                                # the open window, marked incomplete (the signal path does not get here)
+        sim.flush_history(complete=0)
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")
