@@ -247,6 +247,9 @@ class BudgetDiag:
         self._pending.extend(fired)
         self.i += n
 
+    def span_deliver(self, dt):
+        self.take(self.dev.budget_diag_log(), dt)      # the span's budget lines, oldest first
+
     def take(self, records, dt):
         """The drained records, oldest first -> printed lines (returned too)."""
         if len(records) != len(self._pending):

@@ -23,6 +23,10 @@ def _c(a, dtype=np.float64):
 
 
 class Device:
+    _history_n = 0            # entries of the last history_configure
+    _tiles_n = 1              # tiles of the last tile configuration
+    _div_shape = None         # [S, lat, lon] of the last eco_diversity call
+
     def __init__(self, grid, params: QdParams | None = None, device=0, row0=0, n_rows=None, halo=0, rank=0, world=1):
         self.lib = _lib.load()
         self.grid = grid
@@ -132,22 +136,26 @@ class Device:
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
                ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
-        scalars from ThermalForcing.star_table().  `routing`: a RiverRouting on this handle -- bit7, after the
-        hydrology commit (which it needs); the host's t_accum schedule names the event steps, and the span's
-        event records stay in the device log (route_events) until the caller drains them.  `phyto_daily`: a phyto.PhytoDaily on
-        this handle -- bit8; its firing clock turns the span's times (t0 + dt * arange(n), or t0 itself when it is the n times) into the schedule, and the span's
-        [PhytoDiag] records stay in the device log (phyto_daily_log) until the caller drains them.  `eco_daily`: an
-        ecology.PopulationDaily on this handle -- bit9 (needs `ecology`); its day accumulator names the firing steps, and the span's
-        LAI summaries stay in the device log (eco_daily_log) until the caller drains them.  `budget`: a budget_diag.BudgetDiag on
-        this handle -- no flag bit: its schedule (run-local step index, the ocean's step count) turns the lane on for the span, and
-        the records stay in the device log (budget_diag_log) until the caller drains them.  `history`: a history.History on this
-        handle -- no flag bit either: its window clock names the sampled steps, whose fields are added to the resident sums
-        (history_read)."""
+        scalars from ThermalForcing.star_table().  The span lanes, each a participant on this handle whose records stay in its
+        device log until the caller has it deliver them: `routing`, a RiverRouting -- bit7, after the hydrology commit (which it
+        needs); its t_accum names the event steps.  `phyto_daily`, a phyto.PhytoDaily -- bit8; its firing clock turns the span's
+        times (t0 + dt * arange(n), or t0 itself when it is the n times) into the schedule.  `eco_daily`, an
+        ecology.PopulationDaily -- bit9 (needs `ecology`); its day accumulator names the firing steps.  `budget`, a
+        budget_diag.BudgetDiag -- no flag bit: its schedule (run-local step index, the ocean's step count) turns the lane on for
+        the span.  `history`, a history.History -- no flag bit either: its window clock names the sampled steps, whose fields are
+        added to the resident sums (history_read)."""
         self.flush()
         st = np.ascontiguousarray(stars, dtype=np.float64)
         assert st.ndim == 2 and st.shape[1] == 7
         n = int(st.shape[0])
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history) if p is not None]          # the span's participants (csrc/qd_span.h)
+        # The span's participants (csrc/qd_span.h), one protocol for all of them:
+        #   dev                       the handle the lane is configured on
+        #   span_clock()              -> the host clock as it stands before the span
+        #   span_schedule(t0, dt, n)  advance that clock over the n steps, upload their schedule -> what _fired is to be told
+        #   span_restore(clock)       nothing ran (an upload or qd_step_n raised): the clock back to what span_clock gave
+        #   _fired(k)                 the span ran: k is what span_schedule returned
+        #   span_deliver(dt)          drain the lane's device log and deliver it (print, keep); the caller's move, once per span
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history) if p is not None]
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -165,8 +173,7 @@ class Device:
                 p.span_restore(clock)
             raise
         for p, k in zip(lanes, fired):
-            if p is not routing:
-                p._fired(k)
+            p._fired(k)
 
     def sync(self):
         self._chk(self.lib.qd_sync(self.h), "qd_sync")
@@ -272,7 +279,7 @@ class Device:
 
     def history_read(self):
         """-> (sums [n][n_lat][n_lon], sample count)"""
-        out = np.empty((getattr(self, "_history_n", 0),) + self.shape, dtype=np.float64)
+        out = np.empty((self._history_n,) + self.shape, dtype=np.float64)
         n = ctypes.c_int64(0)
         self._chk(self.lib.qd_history_read(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(n)), "qd_history_read")
         return out, int(n.value)
@@ -437,7 +444,7 @@ class Device:
     def eco_diversity_get(self, name):
         """A result of the last eco_diversity call: "ECO_DIV_LS" [S, lat, lon], "ECO_DIV_ALPHA", "ECO_DIV_BC" [lat, lon],
         "ECO_DIV_SUMMARY" [3]."""
-        shp = getattr(self, "_div_shape", None)
+        shp = self._div_shape
         shape = (3,) if name == "ECO_DIV_SUMMARY" else (None if shp is None else (shp if name == "ECO_DIV_LS" else shp[1:]))
         out = np.empty(shape if shape is not None else (1,), dtype=np.float64)
         self._chk(self.lib.qd_eco_diversity_download(self.h, F[name], out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.size),
@@ -597,20 +604,20 @@ class Device:
 
     def tiles_image(self):
         """The u8 mosaic [lat + 2 gutters, n lon + (n + 1) gutters, 3] of the last render."""
-        g, n = _lib.STATEFRAME_GUTTER, getattr(self, "_tiles_n", 1)
+        g, n = _lib.STATEFRAME_GUTTER, self._tiles_n
         out = np.empty((self.shape[0] + 2 * g, n * self.shape[1] + (n + 1) * g, 3), dtype=np.uint8)
         self._chk(self.lib.qd_tiles_download(self.h, 0, out.ctypes.data, out.size), "qd_tiles_download")
         return out
 
     def tiles_bands(self):
         """The int8 band indices [n, lat, lon] of the last render (want_stacks=True); -1 = white."""
-        out = np.empty((getattr(self, "_tiles_n", 1),) + self.shape, dtype=np.int8)
+        out = np.empty((self._tiles_n,) + self.shape, dtype=np.int8)
         self._chk(self.lib.qd_tiles_download(self.h, 1, out.ctypes.data, out.size), "qd_tiles_download")
         return out
 
     def tiles_planes(self):
         """The f64 planes [n, lat, lon] handed to the band search by the last render (want_stacks=True)."""
-        out = np.empty((getattr(self, "_tiles_n", 1),) + self.shape, dtype=np.float64)
+        out = np.empty((self._tiles_n,) + self.shape, dtype=np.float64)
         self._chk(self.lib.qd_tiles_download(self.h, 2, out.ctypes.data, out.size), "qd_tiles_download")
         return out
 

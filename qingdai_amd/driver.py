@@ -131,6 +131,7 @@ import numpy as np
 
 from . import SphericalGrid, SpectralModel, WindDrivenSlabOcean, OrbitalSystem, ThermalForcing, QdParams
 from . import topography as topo
+from .truecolor import plot_interval_steps, firing_steps      # the plot clock of the state frame, the true-colour frame and the figures
 
 PLANET_OMEGA = 8.726646259971648e-5
 
@@ -205,8 +206,16 @@ def load_ocean(path):
 # ------------------------------------------------------------------------------------- simulation
 class Simulation:
     """The reference driver's state + loop, device resident."""
+    # optional members: off until __init__ or an enable_* call turns them on
+    eco = indiv = daily_hook = eco_daily = indiv_daily = None
     speciation = None                      # a Speciation under QD_ECO_SPECIATION=1
     genes_export = False                   # QD_ECO_GENES_EXPORT=1 with it
+    diversity_on, diversity_every, diversity_next_day = False, 10.0, 0.0
+    phyto = phyto_daily = None
+    routing = budget = history = None      # enable_routing, enable_budget_diag (QD_BUDGET_DIAG=1), enable_history (QD_HISTORY=1)
+    truecolor = stateframe = figures = None
+    plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
+    _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
 
     def __init__(self, n_lat=None, n_lon=None, params: QdParams | None = None, use_ocean=None, quiet=False, device=0,
                  ecology=None, individuals=None, daily_hook=None, phyto=None, speciation_rng=None):
@@ -270,7 +279,6 @@ class Simulation:
         self._step_index = 0
         self.dt = int(env.get("QD_DT_SECONDS", "300"))
         # ecology (run_simulation.py:1324-1423): adapter + canopy population + sampled individuals, state on the device
-        self.eco = self.indiv = None
         self.daily_hook = daily_hook
         self.day_seconds = 2 * np.pi / PLANET_OMEGA
         self._accum_day = 0.0
@@ -287,17 +295,14 @@ class Simulation:
                 print(f"[Ecology] device sub-step: NB={self.eco.bands.nbands}, alpha_leaf={self.eco.alpha_leaf_scalar:.3f}, "
                       f"{lai}, individuals {self.indiv.n_indiv if self.indiv else 0}")
         # QD_ECO_DAILY=1: the daily population step as a span lane (no caller hook: a hook keeps precedence and today's behaviour)
-        self.eco_daily = None
         if eco_on and self.eco.pop is not None and daily_hook is None and eco_daily_enabled(env):
             from .ecology import PopulationDaily
             self.eco_daily = PopulationDaily(self.eco.pop, day_seconds=self.day_seconds)
-            self.eco_diag = int(env.get("QD_ECO_DIAG", "1")) == 1
+            self.eco_daily.diag = int(env.get("QD_ECO_DIAG", "1")) == 1
             if not quiet:
                 print(f"[Ecology] daily step on the device: K={self.eco.pop.K}, Ns={self.eco.pop.Ns}, "
                       f"spread {'on' if self.eco_daily.params.spread else 'off'}")
         # QD_ECO_SPECIATION=1: the reference's mutation draw behind every firing of that lane, the split on its resident stack
-        self.speciation = None
-        self.genes_export = False
         if speciation_enabled(env, eco_daily=self.eco_daily is not None, daily_hook=daily_hook is not None):
             from .ecology import Speciation
             self.speciation = Speciation(rng=speciation_rng, env=env)
@@ -306,28 +311,22 @@ class Simulation:
                 print(f"[Ecology] speciation on the device: mut_rate={self.speciation.mut_rate:g}, mut_eps={self.speciation.mut_eps:g}, "
                       f"species_max={self.speciation.species_max}, genes export {'on' if self.genes_export else 'off'}")
         # QD_ECO_INDIV_DAILY=1: IndividualPool.step_daily behind every firing of that lane
-        self.indiv_daily = None
         if indiv_daily_enabled(env, eco_daily=self.eco_daily is not None, ecology=eco_on, population=eco_on and self.eco.pop is not None,
                                individuals=self.indiv is not None, daily_hook=daily_hook is not None):
             from .ecology import IndividualDaily
-            self.indiv_daily = IndividualDaily(self.indiv, self.eco.pop)
+            self.indiv_daily = self.eco_daily.indiv_daily = IndividualDaily(self.indiv, self.eco.pop)
             if not quiet:
                 print(f"[EcoIndiv] daily step on the device: {self.indiv.n_cells} cells x {self.indiv.per_cell} indiv, "
                       f"{self.indiv_daily.n_levels} levels")
         elif self.eco_daily is not None and self.indiv is not None and not quiet:
             print("[Ecology] note: IndividualPool.step_daily is not run by the device daily step.")
         # diversity diagnostics (run_simulation.py:1425-1429, 1741): the switch, the cadence, the clock's threshold in days
-        self.diversity_on, self.diversity_every = False, 10.0
-        self.diversity_next_day = 0.0
-        self._diversity_failed = False
         if self.eco is not None and self.eco.pop is not None:
             from .ecology import diversity_env
             self.diversity_on, self.diversity_every = diversity_env(env)
         # phytoplankton tracers (run_simulation.py:1346-1364): their transport by the currents (needs the ocean), and under
         # QD_PHYTO_DAILY=1 the daily growth / optics step with its ocean-colour albedo, which the reference runs with or without the
         # ocean or the transport
-        self.phyto = None
-        self.phyto_daily = None
         if phyto is None:
             phyto = int(env.get("QD_PHYTO_ENABLE", "1")) == 1 and int(env.get("QD_PHYTO_ADVECTION", "1")) == 1
         self.phyto_transport = bool(phyto) and self.ocean is not None
@@ -347,8 +346,6 @@ class Simulation:
             self.phyto_daily = PhytoDaily(self.phyto, H_mld_m=H_phyto, diag=diag, dev=self.dev, day_seconds=2 * np.pi / PLANET_OMEGA)
             if diag:
                 print("[Phyto] Manager initialized.")
-        self.budget = None                                     # enable_budget_diag (QD_BUDGET_DIAG=1)
-        self.history = None                                    # enable_history (QD_HISTORY=1)
         # banded initial surface temperature (run_simulation.py:310-328)
         if int(env.get("QD_INIT_BANDED", "0")) == 1:
             T_eq, T_pole = float(env.get("QD_INIT_T_EQ", "295.0")), float(env.get("QD_INIT_T_POLE", "265.0"))
@@ -548,7 +545,21 @@ class Simulation:
             self._t_origin = (t0, k + n, float(self.dt))
         return t0 + (k + np.arange(n)) * delta, float(t0 + (k + n) * delta)
 
-    # -- diversity diagnostics (run_simulation.py:2404-2414)
+    # -- outputs that fire behind a chunk's last step (run_simulation.py:2404-2490)
+    def _nonfatal(self, fn, note, key=None, cleanup=None):
+        """An output never stops the run, like the reference's plotting: fn() -> its result, or None after a failure.  `note`
+        (a format of the exception; None = silent) is printed once per `key`, every time without one; `cleanup` runs behind it."""
+        try:
+            return fn()
+        except Exception as e:      # noqa: BLE001
+            if note is not None and key not in self._failed:
+                print(note.format(e))
+            if key is not None:
+                self._failed |= {key}
+            if cleanup is not None:
+                cleanup()
+            return None
+
     def diversity_due(self, n_max):
         """Looks at the next n_max steps with the reference's clock -> (steps up to and including the first firing step, that
         step's start time in days), or (None, None) when none of them fires or the diagnostics are off."""
@@ -566,119 +577,76 @@ class Simulation:
         <output_dir>/ecology/ named by t_days, the clock's next threshold.  A failure is reported once and never stops the run."""
         from .ecology import write_diversity_files, diversity_line
         self.diversity_next_day = t_days + self.diversity_every
-        try:
+        diag = int(os.environ.get("QD_ECO_DIAG", "1")) == 1
+
+        def fire():
             alpha_map, bc_local, L_s, summary = self.eco.pop.diversity()
             out = output_dir if output_dir is not None else os.environ.get("QD_OUTPUT_DIR", "output")
             write_diversity_files(out, t_days, alpha_map, bc_local, L_s, summary, self.land_mask)
-            if int(os.environ.get("QD_ECO_DIAG", "1")) == 1:
+            if diag:
                 print(diversity_line(t_days, summary))
             return summary
-        except Exception as e:      # noqa: BLE001  (non-fatal, like the reference)
-            if not self._diversity_failed and int(os.environ.get("QD_ECO_DIAG", "1")) == 1:
-                print(f"[Diversity] diagnostics skipped: {e}")
-            self._diversity_failed = True
-            return None
+        return self._nonfatal(fire, "[Diversity] diagnostics skipped: {}" if diag else None, "diversity")
 
-    # -- true-colour frames (run_simulation.py:1649-1651, 2426-2429)
     def enable_truecolor(self, env=None):
         """QD_TRUECOLOR=1: the renderer on this run's device and the reference's plot interval -> the TrueColor or None."""
         env = os.environ if env is None else env
         self.truecolor = None
         if int(env.get("QD_TRUECOLOR", "0")) == 1:
-            from .truecolor import TrueColor, plot_interval_steps
+            from .truecolor import TrueColor
             self.truecolor = TrueColor(self)
-            self.truecolor_every = plot_interval_steps(env, self.dt)
-            self._truecolor_failed = False
+            self.plot_every = plot_interval_steps(env, self.dt)
         return self.truecolor
 
-    def truecolor_due(self, i0, n_max):
-        """Looks at the next n_max steps, the first of which has the run-local index i0 -> (steps up to and including the first
-        firing step, that step's start time in days), or (None, None)."""
-        if getattr(self, "truecolor", None) is None or n_max <= 0:
-            return None, None
-        from .truecolor import firing_steps
-        fired = firing_steps(i0, n_max, self.truecolor_every)
-        if not fired:
-            return None, None
-        times, _ = self._span_times(fired[0] + 1, advance=False)
-        return fired[0] + 1, float(times[fired[0]]) / self.day_seconds
-
-    def run_truecolor(self, t_days, output_dir=None):
-        """One firing on the state as it stands (the end of the firing step): the frame file and the [TrueColor] line.  A failure
-        is reported and never stops the run, like the reference's plotting."""
-        try:
-            path, line = self.truecolor.write_frame(t_days, output_dir)
-            print(line)
-            return path
-        except Exception as e:      # noqa: BLE001
-            if not self._truecolor_failed:
-                print(f"[TrueColor] frame skipped: {e}")
-            self._truecolor_failed = True
-            return None
-
-    # -- 15-panel state frames (run_simulation.py:330-537, 2426-2428)
     def enable_stateframe(self, env=None):
         """QD_STATE_PLOT=1: the state-frame renderer on this run's device, configured at once (a latitude-band handle is refused
         here), and the reference's plot interval -> the StateFrame or None."""
         env = os.environ if env is None else env
         self.stateframe = None
         if int(env.get("QD_STATE_PLOT", "0")) == 1:
-            from .stateframe import StateFrame, plot_interval_steps
+            from .stateframe import StateFrame
             sf = StateFrame(self, env=env)                     # QD_PLOT_PS_MODE and the river variables from the same mapping
             sf.configure()
             self.stateframe = sf
-            self.stateframe_every = plot_interval_steps(env, self.dt)
-            self._stateframe_failed = False
+            self.plot_every = plot_interval_steps(env, self.dt)
         return self.stateframe
 
-    def stateframe_due(self, i0, n_max):
-        """As truecolor_due, for the state frame: the same plot clock."""
-        if getattr(self, "stateframe", None) is None or n_max <= 0:
-            return None, None
-        from .stateframe import firing_steps
-        fired = firing_steps(i0, n_max, self.stateframe_every)
-        if not fired:
-            return None, None
-        times, _ = self._span_times(fired[0] + 1, advance=False)
-        return fired[0] + 1, float(times[fired[0]]) / self.day_seconds
-
-    def run_stateframe(self, t_days, output_dir=None):
-        """One firing on the state as it stands (the end of the firing step): state_day_*.png and its .json.  A failure is reported
-        once and never stops the run, like the reference's plotting."""
-        try:
-            return self.stateframe.write_frame(t_days, output_dir)
-        except Exception as e:      # noqa: BLE001
-            if not self._stateframe_failed:
-                print(f"[StatePlot] frame skipped: {e}")
-            self._stateframe_failed = True
-            return None
-
-    # -- ecology, plankton and ISR figures (run_simulation.py:828-1060, 2430-2490)
     def enable_figures(self, env=None):
         """QD_FIGURES=1: the tile renderer on this run's device, configured at once (a latitude-band handle is refused here), and
         the reference's plot interval -> the Figures or None.  QD_PLOT_PHYTO, QD_ECO_PLOT and QD_PLOT_ISR then pick the figures."""
         env = os.environ if env is None else env
         self.figures = None
-        from .figures import figures_enabled
+        from .figures import Figures, figures_enabled
         if figures_enabled(env):
-            from .figures import Figures, plot_interval_steps
             fg = Figures(self, env=env)
             fg.configure()
             self.figures = fg
-            self.figures_every = plot_interval_steps(env, self.dt)
-            self._figures_failed = set()
+            self.plot_every = plot_interval_steps(env, self.dt)
         return self.figures
 
-    def figures_due(self, i0, n_max):
-        """As truecolor_due, for the three figures: the same plot clock."""
-        if getattr(self, "figures", None) is None or n_max <= 0:
+    def plot_due(self, i0, n_max):
+        """Looks at the next n_max steps, the first of which has the run-local index i0, with the plot clock the state frame, the
+        true-colour frame and the figures share -> (steps up to and including the first firing step, that step's start time in
+        days), or (None, None) when none of them fires or none of the three is on."""
+        if self.plot_every is None or n_max <= 0:
             return None, None
-        from .figures import firing_steps
-        fired = firing_steps(i0, n_max, self.figures_every)
+        fired = firing_steps(i0, n_max, self.plot_every)
         if not fired:
             return None, None
         times, _ = self._span_times(fired[0] + 1, advance=False)
         return fired[0] + 1, float(times[fired[0]]) / self.day_seconds
+
+    def run_truecolor(self, t_days, output_dir=None):
+        """One firing on the state as it stands (the end of the firing step): the frame file and the [TrueColor] line."""
+        def fire():
+            path, line = self.truecolor.write_frame(t_days, output_dir)
+            print(line)
+            return path
+        return self._nonfatal(fire, "[TrueColor] frame skipped: {}", "truecolor")
+
+    def run_stateframe(self, t_days, output_dir=None):
+        """One firing on the state as it stands (the end of the firing step): state_day_*.png and its .json."""
+        return self._nonfatal(lambda: self.stateframe.write_frame(t_days, output_dir), "[StatePlot] frame skipped: {}", "stateframe")
 
     def figure_names(self, env=None):
         """The figures this run writes, in their order (run_simulation.py:2431, 2469, 2489)."""
@@ -694,21 +662,38 @@ class Simulation:
         fg = self.figures
         names, e = self.figure_names()
         done = []
-
-        def attempt(name, fn, note):
-            try:
-                done.append(fn())
-            except Exception as ex:      # noqa: BLE001
-                if name not in self._figures_failed and note is not None:
-                    print(note.format(ex))
-                self._figures_failed.add(name)
-        if "plankton" in names:
-            attempt("plankton", lambda: fg.write_plankton(t_days, output_dir), "[PlanktonViz] skipped: {}" if e["phyto_diag"] else None)
-        if "ecology" in names:
-            attempt("ecology", lambda: fg.write_ecology(t_days, output_dir), "[EcologyViz] skipped: {}" if e["eco_diag"] else None)
-        if "ISR" in names:
-            attempt("ISR", lambda: fg.write_isr(t_days, output_dir, echo=print)[0], "[ISRViz] figure skipped: {}")
+        for name, fn, note in (("plankton", lambda: fg.write_plankton(t_days, output_dir), "[PlanktonViz] skipped: {}" if e["phyto_diag"] else None),
+                               ("ecology", lambda: fg.write_ecology(t_days, output_dir), "[EcologyViz] skipped: {}" if e["eco_diag"] else None),
+                               ("ISR", lambda: fg.write_isr(t_days, output_dir, echo=print)[0], "[ISRViz] figure skipped: {}")):
+            if name in names:
+                self._nonfatal(lambda: done.append(fn()), note, name)
         return done
+
+    def outputs_due(self, i0, n_max):
+        """The outputs that fire within the next n_max steps, the first of which has the run-local index i0, in the order the
+        reference writes them (run_simulation.py:2404-2490: diversity, plot_state, plot_true_color, then the plankton, ecology
+        and ISR figures) -> [(steps up to and including the firing step, that step's start time in days, the run_* to call)]."""
+        plot = self.plot_due(i0, n_max)
+        due = [(self.diversity_due(n_max), self.run_diversity)]
+        due += [(plot, run) for on, run in ((self.stateframe, self.run_stateframe), (self.truecolor, self.run_truecolor),
+                                            (self.figures, self.run_figures)) if on is not None]
+        return [(k, day, run) for (k, day), run in due if k is not None]
+
+    def run_loop(self, n_total, next_autosave_t=None, after_chunk=None):
+        """n_total steps in chunks of at most 200 (chunk_until), each ending no later than the next autosave threshold's step and
+        the first step that fires an output; the outputs due on a chunk's last step run behind it, in outputs_due's order (two
+        cadences may fall on one step).  after_chunk(done, next_autosave_t) -> the threshold for the chunks that follow."""
+        done = 0
+        while done < n_total:
+            due = self.outputs_due(done, min(200, n_total - done))
+            n = chunk_until(self.t, self.dt, next_autosave_t, n_total - done, fire_in=min((k for k, _, _ in due), default=None))
+            self.run_steps(n)
+            done += n
+            for k, t_days, run in due:
+                if n == k:                                     # the chunk ended with the firing step
+                    run(t_days)
+            if after_chunk is not None:
+                next_autosave_t = after_chunk(done, next_autosave_t)
 
     # -- speciation (adapter.py:437-466 inside run_simulation.py:1786-1864)
     def speciation_due(self, n_max):
@@ -734,7 +719,7 @@ class Simulation:
         BEFORE the rest of the step, as in the reference, whose day-boundary block then refreshes the banded alpha
         (run_simulation.py:1837-1846; here under QD_ECO_BANDS_COUPLE=1, on a hit).  The step then runs with these firings struck
         out of the lane's schedule; the day accumulator advances as always."""
-        from .ecology import daily_counts, eco_daily_line
+        from .ecology import daily_counts
         lane, spec = self.eco_daily, self.speciation
         fire, _ = daily_counts(lane.accum_day, float(self.dt), 1, lane.day_seconds)
         a = np.float64(lane.accum_day) + np.float64(self.dt)
@@ -743,9 +728,7 @@ class Simulation:
             a = a - np.float64(lane.day_seconds)
             self.dev.eco_daily_step(None)
             lane._fired(1)
-            for rec in self.dev.eco_daily_log():
-                if self.eco_diag:
-                    print(eco_daily_line(rec))
+            lane.span_deliver(float(self.dt))
             if spec.event(self.eco) is not None and self.eco.params.bands_couple:
                 self.eco.banded_alpha()
             self._export_genes(t_i, float(a))
@@ -778,7 +761,7 @@ class Simulation:
     def _run_cut(self, n, energy_diag=False):
         """n steps through _run_lanes; under QD_HISTORY=1 cut so that a chunk ends with a window's last step, behind which the
         window's file is written (the sums then start the next window from zero)."""
-        hist = getattr(self, "history", None)
+        hist = self.history
         while n > 0:
             k = n if hist is None else min(n, hist.steps_to_window_end())
             self._run_lanes(k, energy_diag)
@@ -789,65 +772,50 @@ class Simulation:
     def flush_history(self, complete=1):
         """Write the history window that stands in the accumulators -> the path or None.  A failure is reported and the window is
         dropped (the next one starts from zero): output never stops the run."""
-        try:
-            return self.history.flush(complete=complete)
-        except Exception as e:      # noqa: BLE001
-            print(f"[History] window skipped: {e}")
-            self.history.drop()
-            return None
+        return self._nonfatal(lambda: self.history.flush(complete=complete), "[History] window skipped: {}", cleanup=self.history.drop)
 
     def _run_lanes(self, n, energy_diag=False):
+        """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
+        individuals')."""
         origin = self._t_origin
         times, t_next = self._span_times(n)
         stars = self.forcing.star_table(times)
-        routing = getattr(self, "routing", None)
-        daily = self.phyto_daily
         eco_daily = self.eco_daily if self.daily_hook is None else None
-        budget = getattr(self, "budget", None)
-        accum0, struck0 = (eco_daily.accum_day, eco_daily.struck) if eco_daily is not None else (0.0, 0)
-        lanes = {}
-        if budget is not None:
-            budget.routed = routing is not None
-            lanes["budget"] = budget
-        if getattr(self, "history", None) is not None:
-            lanes["history"] = self.history                    # samples into the resident sums; nothing to drain behind the span
+        if self.budget is not None:
+            self.budget.routed = self.routing is not None
+        lanes = {k: p for k, p in (("phyto_daily", self.phyto_daily), ("routing", self.routing), ("budget", self.budget),
+                                   ("eco_daily", eco_daily), ("history", self.history)) if p is not None}
+        eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         try:
             self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
                             with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto_transport,
-                            routing=routing, phyto_daily=daily, t0=times, eco_daily=eco_daily, **lanes)
+                            t0=times, **lanes)
         except Exception:
             self._t_origin = origin                            # nothing ran: the clock stays where it was, like the lanes' clocks
             raise
         self._t = t_next
         self._step_index += n
-        if daily is not None:
-            daily.print_diag(self.dev.phyto_daily_log())      # the span's [PhytoDiag] lines, oldest first
-        if routing is not None:
-            routing.take_events(self.dev.route_events())      # the span's events, oldest first
-        if budget is not None:
-            budget.take(self.dev.budget_diag_log(), float(self.dt))       # the span's budget lines, oldest first
-        if eco_daily is not None:
-            from .ecology import eco_daily_line
-            recs = self.dev.eco_daily_log()
-            for rec in recs:                                   # the span's firings, oldest first (adapter.py:434-436)
-                if self.eco_diag:
-                    print(eco_daily_line(rec))
-            if self.speciation is not None and len(recs):      # none of them was a hit; weights and genes are the chunk's
-                self.speciation.passed(len(recs))
-                if self.genes_export:
-                    from .ecology import daily_counts
-                    fire, _ = daily_counts(accum0, float(self.dt), n, eco_daily.day_seconds)
-                    a = np.float64(accum0)
-                    for i in range(n):
-                        a = a + np.float64(self.dt)
-                        for q in range(int(fire[i])):
-                            a = a - np.float64(eco_daily.day_seconds)
-                            if not (i == 0 and q < struck0):
-                                self._export_genes(float(times[i]), float(a))
-            if getattr(self, "indiv_daily", None) is not None:     # the reference's line per firing (individuals.py:358-361)
-                for line in self.indiv_daily.lines():
-                    if self.eco_diag:
-                        print(line)
+        for p in lanes.values():
+            recs = p.span_deliver(float(self.dt))              # the span's lines, oldest first
+            if p is eco_daily and self.speciation is not None and len(recs):
+                self._firings_passed(len(recs), times, *eco_clock)
+
+    def _firings_passed(self, n_fired, times, accum0, struck0):
+        """Behind a span's eco-daily firings under QD_ECO_SPECIATION=1: none of them was a hit, and the weights and genes are the
+        chunk's -- so QD_ECO_GENES_EXPORT=1 writes every firing's file now, but for those the host ran before the span."""
+        self.speciation.passed(n_fired)
+        if not self.genes_export:
+            return
+        from .ecology import daily_counts
+        day = self.eco_daily.day_seconds
+        fire, _ = daily_counts(accum0, float(self.dt), len(times), day)
+        a = np.float64(accum0)
+        for i in range(len(times)):
+            a = a + np.float64(self.dt)
+            for q in range(int(fire[i])):
+                a = a - np.float64(day)
+                if not (i == 0 and q < struck0):
+                    self._export_genes(float(times[i]), float(a))
 
     def enable_budget_diag(self, env=None):
         """QD_BUDGET_DIAG=1: the reference's periodic budget lines ([EnergyDiag], [OceanE], [OceanDiag], [HumidityDiag],
@@ -855,7 +823,7 @@ class Simulation:
         step index the reference's `i % 200` counts starts where this is called."""
         from .budget_diag import from_env
         self.budget = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
-                               routed=getattr(self, "routing", None) is not None)
+                               routed=self.routing is not None)
         return self.budget
 
     def enable_history(self, env=None):
@@ -1016,15 +984,15 @@ def plots_line(stateframe, truecolor, sim, figures=None):
         what = [w for w, on in (("the 15-panel state frame (state_day_*.png + .json, no axes)", stateframe is not None),
                                 ("the true-colour frame", truecolor is not None)) if on]
         what.append(("the " + ", ".join(names) + " figures (tiles + .json, no axes)") if names else "no further figure (every QD_FIGURES switch is off)")
-        return (f"[Plots] {'; '.join(what)}: produced by the device driver, every {sim.figures_every} steps; the reference's plot_ocean "
+        return (f"[Plots] {'; '.join(what)}: produced by the device driver, every {sim.plot_every} steps; the reference's plot_ocean "
                 "is never called and is not.")
     if stateframe is None:
         if truecolor is None:
             return "[Plots] matplotlib panels are not produced by the device driver (out of the hot path)."
-        return (f"[Plots] only the true-colour frame is produced by the device driver, every {sim.truecolor_every} steps; "
+        return (f"[Plots] only the true-colour frame is produced by the device driver, every {sim.plot_every} steps; "
                 "the matplotlib panels are not.")
     what = "the 15-panel state frame (state_day_*.png + .json, no axes)" + (" and the true-colour frame" if truecolor is not None else "")
-    return (f"[Plots] {what} produced by the device driver, every {sim.stateframe_every} steps; the ocean, plankton, ISR and ecology "
+    return (f"[Plots] {what} produced by the device driver, every {sim.plot_every} steps; the ocean, plankton, ISR and ecology "
             "figures are not.")
 
 
@@ -1139,36 +1107,22 @@ def main(argv=None):
     signal.signal(signal.SIGTERM, _on_signal)
     atexit.register(lambda: _autosave("atexit"))
 
-    done = 0
     wall0 = time.perf_counter()
-    while done < n_total:
-        fire_in, fire_day = sim.diversity_due(min(200, n_total - done))
-        frame_in, frame_day = sim.truecolor_due(done, min(200, n_total - done))
-        state_in, state_day = sim.stateframe_due(done, min(200, n_total - done))
-        figs_in, figs_day = sim.figures_due(done, min(200, n_total - done))
-        n = chunk_until(sim.t, sim.dt, next_autosave_t if autosave_on else None, n_total - done,
-                        fire_in=min((k for k in (fire_in, frame_in, state_in, figs_in) if k is not None), default=None))
-        sim.run_steps(n)
-        done += n
-        if fire_in is not None and n == fire_in:               # the chunk ended with the firing step
-            sim.run_diversity(fire_day)
-        if state_in is not None and n == state_in:             # plot_state, then plot_true_color (run_simulation.py:2428-2429)
-            sim.run_stateframe(state_day)
-        if frame_in is not None and n == frame_in:             # (both cadences may fall on one step: diversity first, as in the reference)
-            sim.run_truecolor(frame_day)
-        if figs_in is not None and n == figs_in:               # plankton, ecology, ISR behind the two frames (run_simulation.py:2430-2490)
-            sim.run_figures(figs_day)
+
+    def _after_chunk(done, next_autosave_t):
         if int(env.get("QD_DYN_DIAG_PRINT", "1")) == 1:
             dg = sim.diagnostics()
             el = time.perf_counter() - wall0
             print(f"t={sim.t / day:8.2f} d | " + " ".join(f"{k}={v:.4g}" for k, v in dg.items()) +
                   f" | {done / max(el, 1e-9):.0f} steps/s")
-        if autosave_on and next_autosave_t is not None and sim.t >= next_autosave_t - 1e-9 * sim.dt and done < n_total:
+        if next_autosave_t is not None and sim.t >= next_autosave_t - 1e-9 * sim.dt and done < n_total:
             state["saved"] = False
             _autosave("periodic")
             state["saved"] = False
             while next_autosave_t <= sim.t + 1e-9 * sim.dt:
                 next_autosave_t += autosave_dt
+        return next_autosave_t
+    sim.run_loop(n_total, next_autosave_t if autosave_on else None, _after_chunk)
     if sim.history is not None:                                # the open window, marked incomplete (the signal path does not get here)
         sim.flush_history(complete=0)
     if env.get("QD_RESTART_OUT"):

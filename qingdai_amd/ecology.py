@@ -74,6 +74,8 @@ def _peaks_from_env(prefix):
 
 class PopulationCanopy:
     """LAI layers + daily energy buffer + canopy cache of PopulationManager, resident on the device."""
+    daily = None                           # a PopulationDaily once the daily step runs on the device
+    indiv_daily = None                     # an IndividualDaily once the individuals' daily step runs on the device
 
     def __init__(self, dev, land_mask, diag=False):
         self._dev = dev
@@ -103,8 +105,6 @@ class PopulationCanopy:
             for k in range(self.K):
                 self.LAI_layers_SK[s, k] = float(self.species_weights[s]) * (lai0 / float(self.K))
         self._species_R_leaf = None
-        self.daily = None                  # a PopulationDaily once the daily step runs on the device
-        self.indiv_daily = None            # an IndividualDaily once the individuals' daily step runs on the device
         self.push_layers(init=True)
 
     def _stack_clock(self):
@@ -114,7 +114,7 @@ class PopulationCanopy:
     # -- species weights: recomputed on the device by every firing of the individuals' daily step (population.py:343-359)
     @property
     def species_weights(self):
-        if getattr(self, "indiv_daily", None) is not None:
+        if self.indiv_daily is not None:
             fired = self._dev.indiv_daily_firings()
             if fired and fired != self._weights_at:
                 self._weights, self._weights_at = self._dev.indiv_daily_weights(self._weights.size), fired
@@ -123,13 +123,13 @@ class PopulationCanopy:
     @species_weights.setter
     def species_weights(self, w):
         self._weights = w
-        self._weights_at = self._dev.indiv_daily_firings() if getattr(self, "indiv_daily", None) is not None else 0
+        self._weights_at = self._dev.indiv_daily_firings() if self.indiv_daily is not None else 0
 
     # -- LAI
     @property
     def LAI_layers_SK(self):
         """[S, K, lat, lon]; with a device daily step the resident stack is the truth and is downloaded."""
-        if getattr(self, "daily", None) is not None:
+        if self.daily is not None:
             fired = self._stack_clock()                        # the device's own counts: firings of a span or of a direct call alike
             if fired != self._layers_at:
                 self._layers, self._layers_at = self._dev.eco_daily_get_layers(self.Ns, self.K), fired
@@ -138,7 +138,7 @@ class PopulationCanopy:
     @LAI_layers_SK.setter
     def LAI_layers_SK(self, layers):
         self._layers = layers
-        self._layers_at = self._stack_clock() if getattr(self, "daily", None) is not None else 0
+        self._layers_at = self._stack_clock() if self.daily is not None else 0
 
     def push_layers(self, layers=None, init=False):
         """Hand the (changed) [S, K, lat, lon] stack to the device: what the daily step does once per planet-day."""
@@ -402,6 +402,8 @@ class PopulationDaily:
     accumulator on the host names the firing steps, rolled back when the span does not run."""
 
     struck = 0                             # firings of the next span's first step the host has already run through the class seam
+    diag = False                           # QD_ECO_DIAG: print the line of every firing a span delivers (the driver sets it)
+    indiv_daily = None                     # the IndividualDaily whose line per firing follows this lane's (the driver sets it)
 
     def __init__(self, pop, day_seconds=None, species_modes=None):
         self.pop, self.dev = pop, pop._dev
@@ -502,6 +504,16 @@ class PopulationDaily:
 
     def span_restore(self, clock):
         self.accum_day, self.struck = clock
+
+    def span_deliver(self, dt):
+        """-> the records of the span's firings, oldest first; under `diag` their lines (adapter.py:434-436) and, behind them, the
+        individuals' line per firing (individuals.py:358-361): they fire together."""
+        recs = self.dev.eco_daily_log()
+        lines = [eco_daily_line(rec) for rec in recs] + (self.indiv_daily.lines() if self.indiv_daily is not None else [])
+        if self.diag:
+            for line in lines:
+                print(line)
+        return recs
 
     def log(self):
         """Drain the device log -> list of summary() dicts, oldest first."""

@@ -23,7 +23,6 @@ import numpy as np
 
 from . import _lib
 from .stateframe import auto_levels, band_colours, is_constant, GUTTER, MAX_LEVELS
-from .truecolor import plot_interval_steps, firing_steps      # noqa: F401  (the same plot clock)
 
 MAX_TILES = _lib.TILES_MAX
 MARK_X, MARK_PLUS = 1, 2                                       # cyan x, yellow +

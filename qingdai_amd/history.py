@@ -156,6 +156,9 @@ class History:
             self.t_last = span[1]
             self.n_open += count
 
+    def span_deliver(self, dt):
+        pass                                         # the samples went into the resident sums: nothing to drain behind a span
+
     # -- windows
     def steps_to_window_end(self, i=None):
         """Steps from step i (default: the next step) up to and including its window's last step."""

@@ -363,7 +363,7 @@ class PhytoDaily:
         fire, self.phyto_next_time = daily_schedule(self.phyto_next_time, t0, dt, n, self.day_seconds)
         return fire
 
-    # ---- span participant (Device.step_n): the host clock before the span, this span's schedule to the device, the clock put back
+    # ---- span participant (the protocol is stated in Device.step_n)
     def span_clock(self):
         return self.phyto_next_time
 
@@ -374,6 +374,9 @@ class PhytoDaily:
 
     def span_restore(self, clock):
         self.phyto_next_time = clock
+
+    def span_deliver(self, dt):
+        self.print_diag(self.dev.phyto_daily_log())    # the span's [PhytoDiag] lines, oldest first
 
     def print_diag(self, records):
         if self.diag:

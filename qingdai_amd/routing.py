@@ -353,7 +353,7 @@ class RiverRouting:
         self._steps += n
         return ev
 
-    # ---- span participant (Device.step_n): the host clock before the span, this span's schedule to the device, the clock put back
+    # ---- span participant (the protocol is stated in Device.step_n)
     def span_clock(self):
         return self.t_accum, self._steps
 
@@ -362,6 +362,12 @@ class RiverRouting:
 
     def span_restore(self, clock):
         self.t_accum, self._steps = clock
+
+    def _fired(self, k):
+        pass                                   # schedule() has already counted the span's steps
+
+    def span_deliver(self, dt):
+        self.take_events(self.dev.route_events())      # the span's events, oldest first
 
     def step(self, R_land_flux, dt_seconds, precip_flux=None, evap_flux=None):
         """routing.py:199-312 on host arrays: upload, accumulate on the device, route when the window is full."""

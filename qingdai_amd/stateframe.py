@@ -25,7 +25,6 @@ import os
 import numpy as np
 
 from . import _lib
-from .truecolor import plot_interval_steps, firing_steps      # noqa: F401  (the same plot clock)
 
 N_PANELS = _lib.STATEFRAME_PANELS
 MAX_LEVELS = _lib.STATEFRAME_MAX_LEVELS

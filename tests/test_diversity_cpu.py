@@ -10,6 +10,7 @@ import pytest
 
 import diversity_ref as ref
 from qingdai_amd import _lib
+from qingdai_amd.driver import Simulation
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDENS = sorted(glob.glob(os.path.join(HERE, "golden", "diversity_*_19x36.npz")))
@@ -103,33 +104,28 @@ def _reference_loop(t0, n_steps, dt, every):
     return fired
 
 
-class _Sim:
-    """The clock half of driver.Simulation without a device."""
+class _Sim(Simulation):
+    """driver.Simulation with the device taken out: a chunk only advances the clock, a firing only moves the threshold."""
     def __init__(self, t0, dt, on, every):
-        from qingdai_amd.driver import Simulation
         self.dt, self.day_seconds = dt, DAY
-        self.diversity_on, self.diversity_every, self.diversity_next_day = on, every, 0.0
-        self._t = float(t0)
-        self._t_origin = (float(t0), 0, None)
-        self._span_times = Simulation._span_times.__get__(self)
-        self.diversity_due = Simulation.diversity_due.__get__(self)
+        self.diversity_on, self.diversity_every = on, every
+        self.t = t0
+        self.chunks, self.fired = [], []
+
+    def run_steps(self, n):
+        _, self._t = self._span_times(n)
+        self.chunks.append(n)
+
+    def run_diversity(self, t_days):
+        self.fired.append((sum(self.chunks) - 1, t_days))
+        self.diversity_next_day = t_days + self.diversity_every
 
 
 def _drive(t0, n_total, dt, on, every, next_autosave=None):
-    """driver.main's loop with the device taken out -> (chunk lengths, [(step, t_days)] of the firings)."""
-    from qingdai_amd.driver import chunk_until
+    """The driver's own loop (Simulation.run_loop) -> (chunk lengths, [(step, t_days)] of the firings)."""
     sim = _Sim(t0, dt, on, every)
-    done, chunks, fired = 0, [], []
-    while done < n_total:
-        fire_in, fire_day = sim.diversity_due(min(200, n_total - done))
-        n = chunk_until(sim._t, dt, next_autosave, n_total - done, fire_in=fire_in)
-        _, sim._t = sim._span_times(n)
-        done += n
-        chunks.append(n)
-        if fire_in is not None and n == fire_in:
-            fired.append((done - 1, fire_day))
-            sim.diversity_next_day = fire_day + every
-    return chunks, fired
+    sim.run_loop(n_total, next_autosave)
+    return sim.chunks, sim.fired
 
 
 @pytest.mark.parametrize("every", [10.0, 0.5, 0.0, 1.0 / 3.0, -1.0])

@@ -224,8 +224,7 @@ def ctypes_size(t):
 
 def test_plots_line_wordings():
     from qingdai_amd.driver import plots_line
-    sim = types.SimpleNamespace(truecolor_every=3, stateframe_every=3, figures_every=3,
-                                figure_names=lambda: (["plankton", "ecology", "ISR"], {}))
+    sim = types.SimpleNamespace(plot_every=3, figure_names=lambda: (["plankton", "ecology", "ISR"], {}))
     assert plots_line(None, None, sim) == "[Plots] matplotlib panels are not produced by the device driver (out of the hot path)."
     assert plots_line(None, object(), sim) == ("[Plots] only the true-colour frame is produced by the device driver, every 3 steps; "
                                                "the matplotlib panels are not.")

@@ -214,9 +214,10 @@ def test_read_env_and_pack_table(monkeypatch):
 
 
 def test_plot_clock_and_driver_order(monkeypatch):
-    """The state frame fires on the true-colour frame's clock and is written first (run_simulation.py:2426-2429)."""
+    """The state frame fires on the true-colour frame's clock and is written first (run_simulation.py:2426-2429), behind the
+    diversity diagnostics and before the figures (:2404-2490): the calls recorded through the driver's own loop."""
     from qingdai_amd import driver
-    from qingdai_amd.stateframe import firing_steps, plot_interval_steps
+    from qingdai_amd.truecolor import firing_steps, plot_interval_steps
     assert plot_interval_steps({"QD_PLOT_EVERY_DAYS": "0.085"}, 2400) == 3 and firing_steps(4, 6, 3) == [2, 5]
     calls = []
 
@@ -226,37 +227,35 @@ def test_plot_clock_and_driver_order(monkeypatch):
             return "path", "[TrueColor] line"
 
     sim = driver.Simulation.__new__(driver.Simulation)
-    sim.dt, sim.day_seconds, sim.diversity_on = 2400, 86400.0, False
+    sim.dt, sim.day_seconds = 2400, 86400.0
     sim.t = 0.0
-    sim._step_index = 0
     sim.stateframe, sim.truecolor = Stub(), Stub()
     sim.stateframe.name, sim.truecolor.name = "state", "truecolor"
-    sim.stateframe_every = sim.truecolor_every = 3
-    sim._stateframe_failed = sim._truecolor_failed = False
-    assert sim.stateframe_due(0, 7) == (1, 0.0) and sim.stateframe_due(1, 7) == sim.truecolor_due(1, 7)
+    sim.plot_every = 3
+    assert sim.plot_due(0, 7) == (1, 0.0)
+    assert [(k, day, run.__name__) for k, day, run in sim.outputs_due(1, 7)] == [(3, 2 * 2400 / 86400, "run_stateframe"), (3, 2 * 2400 / 86400, "run_truecolor")]
     monkeypatch.setattr(driver.Simulation, "run_steps", lambda self, n: (calls.append(("steps", n)), self._span_times(n)) and None)
-
-    def loop(n_total):                                          # the firing part of main()'s loop
-        done = 0
-        while done < n_total:
-            frame_in, frame_day = sim.truecolor_due(done, min(200, n_total - done))
-            state_in, state_day = sim.stateframe_due(done, min(200, n_total - done))
-            n = driver.chunk_until(sim.t, sim.dt, None, n_total - done, fire_in=min(k for k in (frame_in, state_in, n_total) if k is not None))
-            sim.run_steps(n)
-            done += n
-            if state_in is not None and n == state_in:
-                sim.run_stateframe(state_day)
-            if frame_in is not None and n == frame_in:
-                with redirect_stdout(io.StringIO()):
-                    sim.run_truecolor(frame_day)
-    loop(5)
+    with redirect_stdout(io.StringIO()):
+        sim.run_loop(5)
     assert calls == [("steps", 1), ("frame", "state", 0.0), ("frame", "truecolor", 0.0), ("steps", 3), ("frame", "state", round(3 * 2400 / 86400, 6)),
                      ("frame", "truecolor", round(3 * 2400 / 86400, 6)), ("steps", 1)]
-    import inspect
-    src = inspect.getsource(driver.main)
-    assert src.index("sim.run_diversity(") < src.index("sim.run_stateframe(") < src.index("sim.run_truecolor(")
+    # every cadence on one step: diversity, the state frame, the true-colour frame, the figures
+    monkeypatch.setattr(driver.Simulation, "run_diversity", lambda self, t_days: calls.append(("diversity", round(t_days, 6))) or
+                        setattr(self, "diversity_next_day", t_days + self.diversity_every))
+    monkeypatch.setattr(driver.Simulation, "run_figures", lambda self, t_days: calls.append(("figures", round(t_days, 6))))
+    sim.t = 0.0
+    sim.figures, sim.diversity_on, sim.diversity_every = object(), True, 6 * 2400 / 86400
+    del calls[:]
+    with redirect_stdout(io.StringIO()):
+        sim.run_loop(7)
+    both = [("diversity", 0.0), ("frame", "state", 0.0), ("frame", "truecolor", 0.0), ("figures", 0.0)]
+    d3, d6 = round(3 * 2400 / 86400, 6), round(6 * 2400 / 86400, 6)
+    assert calls == [("steps", 1)] + both + [("steps", 3)] + [c[:-1] + (d3,) for c in both[1:]] + [("steps", 3)] + [c[:-1] + (d6,) for c in both]
     sim.stateframe = None
-    assert sim.stateframe_due(0, 7) == (None, None)
+    assert [run for _, _, run in sim.outputs_due(0, 7)] == [sim.run_diversity, sim.run_truecolor, sim.run_figures]
+    sim.truecolor = sim.figures = None                          # the clock may stand; with no output on it nothing is due
+    sim.diversity_on = False
+    assert sim.outputs_due(0, 7) == []
 
 
 def test_plots_line_with_the_switch_off_is_todays(monkeypatch):
@@ -266,10 +265,9 @@ def test_plots_line_with_the_switch_off_is_todays(monkeypatch):
     ref.set_env(monkeypatch, {})
     assert sim.enable_stateframe() is None and sim.stateframe is None
     assert driver.plots_line(None, None, sim) == "[Plots] matplotlib panels are not produced by the device driver (out of the hot path)."
-    sim.truecolor_every = 288
+    sim.plot_every = 288
     assert driver.plots_line(None, object(), sim) == ("[Plots] only the true-colour frame is produced by the device driver, every 288 steps; "
                                                      "the matplotlib panels are not.")
-    sim.stateframe_every = 288
     on = driver.plots_line(object(), object(), sim)
     assert "15-panel state frame" in on and "true-colour frame" in on and "every 288 steps" in on
     assert "true-colour" not in driver.plots_line(object(), None, sim)

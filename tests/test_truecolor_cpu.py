@@ -180,13 +180,21 @@ def test_plot_clock_against_hand_listed_steps():
     assert firing_steps(0, 4, 1) == [0, 1, 2, 3]
     assert firing_steps(10, 20, 9) == [8, 17]                   # run-local index 18 and 27
     assert firing_steps(1, 5, 9) == []
-    # the chunks of a 20-step run at interval 9: each ends with a firing step
-    done, chunks = 0, []
-    while done < 20:
-        fired = firing_steps(done, min(200, 20 - done), 9)
-        n = chunk_until(0.0, 300.0, None, 20 - done, fire_in=fired[0] + 1 if fired else None)
-        chunks.append(n)
-        done += n
-    assert chunks == [1, 9, 9, 1]
+    # the chunks of a 20-step run at interval 9 through the driver's loop: each ends with a firing step, behind which the frame runs
+    from qingdai_amd.driver import Simulation
+    chunks, frames = [], []
+
+    class Sim(Simulation):
+        def run_steps(self, n):
+            chunks.append(n)
+            _, self._t = self._span_times(n)
+
+        def run_truecolor(self, t_days):
+            frames.append((sum(chunks) - 1, t_days))
+    sim = Sim.__new__(Sim)
+    sim.dt, sim.day_seconds, sim.truecolor, sim.plot_every = 300.0, 86400.0, object(), 9
+    sim.t = 0.0
+    sim.run_loop(20)
+    assert chunks == [1, 9, 9, 1] and frames == [(0, 0.0), (9, 9 * 300.0 / 86400.0), (18, 18 * 300.0 / 86400.0)]
     # the earlier of two cadences ends the chunk; both on one step end it once
     assert chunk_until(0.0, 300.0, None, 50, fire_in=min(7, 3)) == 3 and chunk_until(0.0, 300.0, None, 50, fire_in=min(4, 4)) == 4
