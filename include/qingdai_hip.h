@@ -611,6 +611,9 @@ int qd_route_event(qd_handle h, double event_dt, int with_pe);   /* route the bu
 int qd_route_schedule(qd_handle h, int n, const double* event_dt);   /* the next qd_step_n span: event_dt per step, 0 = none */
 int qd_route_download(qd_handle h, int which, double* host, size_t n);   /* 0 flow map kg/s [n_cells], 1 lake volumes [n_lakes], 2 buffer */
 int qd_route_events(qd_handle h, double* out, int max, int* n);   /* drains the event log: *n records of 8 doubles */
+/* the inverse of qd_route_download, for an exact resume (QD_CHECKPOINT; the reference's restart does not carry the buffer): buffer
+ * and flow map [n_cells], lake volumes [n_lakes] (null without lakes), the accumulations so far; log and schedule are left alone */
+int qd_route_restore(qd_handle h, const double* buffer, const double* flow, const double* lakes, int64_t steps);
 
 /* ---- river network generation (P014, scripts/generate_hydrology_maps.py:64-311), whole-globe handles ------------------
  * pit_fill(elevation, land_mask, max_iters, eps), compute_flow_to_index, identify_lakes, compute_lake_outlets and
@@ -709,6 +712,36 @@ int qd_history_schedule(qd_handle h, int steps, const int32_t* sample);   /* the
 int qd_history_sample(qd_handle h);                                      /* one sample of every entry now, outside a span (one launch) */
 int qd_history_read(qd_handle h, double* sums, int64_t* count);          /* the sums [n][n_lat][n_lon] and the samples in them */
 int qd_history_reset(qd_handle h);                                       /* sums and count back to zero */
+/* the inverse of qd_history_read, for an exact resume (QD_CHECKPOINT): an open window's sums and sample count put back */
+int qd_history_restore(qd_handle h, const double* sums, int64_t count);
+
+/* ---- state digest and exact resume (QD_CHECKPOINT), whole-globe handles ---------------------------------------------------
+ * Nothing the reference has: its restart file holds 14 planes as f4 and a resumed run does not continue the run that was stopped.
+ * qd_state_digest: a 64-bit digest of resident planes, all of them in ONE launch.  The digest of a plane of n elements is
+ *     D = sum_{i = 0 .. n-1} mix64(w_i + (i + 1) * 0x9E3779B97F4A7C15)  mod 2^64
+ * with w_i the element's stored bits zero-extended to 64 (f64 8 bytes, f32 4, u8 1; NaN payloads and the sign of zero count; a map
+ * the ecology keeps as f32 is digested as the f32 slab it is), i the element's row-major index in the global plane, and mix64 the
+ * splitmix64 finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31).  Integer
+ * addition is associative: the value does not depend on the launch shape or on the order in which the workgroups finish.
+ * A ref is a qd_field id (every f64 field, QD_F_LAND_MASK, QD_F_ICE_MASK) or one of the resident planes that have no field id: */
+enum qd_state_ref {
+    QD_SR_PHYTO_TRACER = 200,      /* + s: the tracer of species s (< 64), [n_lat][n_lon] */
+    QD_SR_ROUTE_BUFFER = 300, QD_SR_ROUTE_FLOW = 301,   /* what qd_route keeps: the buffer and the flow map [n_lat][n_lon] ... */
+    QD_SR_ROUTE_LAKES = 302,       /* ... and the lake volumes [n_lakes] */
+    QD_SR_ECO_LAI_STACK = 310,     /* the LAI stack of the daily vegetation step, [n_species * n_layers][n_lat][n_lon] as ONE plane */
+    QD_SR_INDIV_E_DAY = 320, QD_SR_INDIV_STRESS = 321,   /* the individuals' buffers [n_indiv] */
+    QD_SR_HISTORY_SUM = 400        /* + k: the sum plane of history entry k (< 32) */
+};
+#define QD_STATE_DIGEST_MAX 64
+/* n <= 64 refs -> out[n].  Refused: latitude bands, an unknown ref, a ref whose subsystem is not configured (the line names it). */
+int qd_state_digest(qd_handle h, int n, const int32_t* refs, uint64_t* out);
+/* The host-side scalars a step reads besides the planes and the two step counters -- cloud_eff_valid, the ecology sub-step's clock,
+ * cache flags and versions, the accumulator of the individuals' sub-step, the firing counts of the daily lanes, the last span's
+ * energy-budget means -- as n = QD_STATE_SCALARS_N doubles (csrc/qd_digest.hip names the slots); set puts them back on a fresh
+ * handle that was configured like the one they were read from. */
+#define QD_STATE_SCALARS_N 32
+int qd_state_scalars_get(qd_handle h, double* out, int n);
+int qd_state_scalars_set(qd_handle h, const double* in, int n);
 
 /* ---- reductions for diagnostics (energy.py:494-538, ocean.py:535-561) -------------- */
 /* compute_energy_diagnostics (energy.py:494-538) from the resident state, with the flux formulas of the driver's

@@ -54,9 +54,10 @@ SYMBOLS = [
     "qd_stateframe_configure", "qd_stateframe_scan", "qd_stateframe_render", "qd_stateframe_download",
     "qd_tiles_configure", "qd_tiles_set_plane", "qd_tiles_available", "qd_tiles_scan", "qd_tiles_order_stats", "qd_tiles_render", "qd_tiles_download",
     "qd_budget_diag_configure", "qd_budget_diag_schedule", "qd_budget_diag_log", "qd_budget_diag_reset",
-    "qd_history_configure", "qd_history_schedule", "qd_history_sample", "qd_history_read", "qd_history_reset",
+    "qd_history_configure", "qd_history_schedule", "qd_history_sample", "qd_history_read", "qd_history_reset", "qd_history_restore",
+    "qd_state_digest", "qd_state_scalars_get", "qd_state_scalars_set",
     "qd_route_configure", "qd_route_free", "qd_route_reset", "qd_route_accumulate", "qd_route_event", "qd_route_schedule",
-    "qd_route_download", "qd_route_events",
+    "qd_route_download", "qd_route_events", "qd_route_restore",
     "qd_hydronet_build", "qd_hydronet_sweeps",
     "qd_topogen_smooth", "qd_topogen_build", "qd_topogen_last_ms",
     "qd_copy_ceiling", "qd_timing_enable", "qd_timing_select", "qd_timing_get", "qd_timing_reset",
@@ -153,6 +154,27 @@ INDIV_DAILY_LOG_W = 4        # doubles per record of the individuals' daily step
 BUDGET_LOG_W = 40           # doubles per budget diagnostics record (QD_BUDGET_LOG_W; budget_diag.REC names the slots)
 HISTORY_MAX_ENTRIES = 32     # QD_HISTORY_MAX_ENTRIES
 ROUTE_LOG_W = 8              # doubles per routing event record (routing.LOG_KEYS)
+STATE_DIGEST_MAX = 64        # QD_STATE_DIGEST_MAX: refs per qd_state_digest call
+STATE_SCALARS_N = 32         # QD_STATE_SCALARS_N
+# the slots of qd_state_scalars_get / set the host reads by name (csrc/qd_digest.hip lists all of them)
+STATE_SCALAR_SLOT = {"cloud_eff_valid": 0, "has_elevation": 1, "phyto_daily_steps": 17, "eco_daily_fired": 18, "indiv_daily_fired": 19, "last_nsub": 20}
+# enum qd_state_ref: the resident planes without a field id, as Device.digest names them ("PHYTO_TRACER:3", "HISTORY_SUM:0")
+STATE_REFS = {"PHYTO_TRACER": 200, "ROUTE_BUFFER": 300, "ROUTE_FLOW": 301, "ROUTE_LAKES": 302, "ECO_LAI_STACK": 310,
+              "INDIV_E_DAY": 320, "INDIV_STRESS": 321, "HISTORY_SUM": 400}
+STATE_REF_COUNT = {"PHYTO_TRACER": 64, "HISTORY_SUM": 32}     # the indexed ones: name:k with k below this
+
+
+def state_ref(name):
+    """A plane's name -> the ref qd_state_digest takes: a field name of F (f64 fields and the two masks), a name of STATE_REFS, or
+    an indexed one, "PHYTO_TRACER:s" / "HISTORY_SUM:k"."""
+    if name in FIELDS or name in ("LAND_MASK", "ICE_MASK"):
+        return F[name]
+    base, _, idx = str(name).partition(":")
+    if base in STATE_REF_COUNT and idx.isdigit() and int(idx) < STATE_REF_COUNT[base]:
+        return STATE_REFS[base] + int(idx)
+    if base in STATE_REFS and base not in STATE_REF_COUNT and not idx:
+        return STATE_REFS[base]
+    raise KeyError(f"'{name}' names no resident plane (a field of FIELDS, LAND_MASK, ICE_MASK, {', '.join(STATE_REFS)})")
 
 # qd_step_n flags (include/qingdai_hip.h): bit k switches STEP_BITS[k], named as Device.step_n's keywords
 STEP_BITS = ("with_ocean", "with_physics", "pass_albedo", "with_hydrology", "energy_diag", "ecology", "phyto", "routing", "phyto_daily", "eco_daily")
@@ -287,6 +309,10 @@ def load():
     lib.qd_history_sample.argtypes = [vp]
     lib.qd_history_read.argtypes = [vp, dp, ctypes.POINTER(i64)]
     lib.qd_history_reset.argtypes = [vp]
+    lib.qd_history_restore.argtypes = [vp, dp, i64]
+    lib.qd_state_digest.argtypes = [vp, i32, ip, ctypes.POINTER(ctypes.c_uint64)]
+    lib.qd_state_scalars_get.argtypes = [vp, dp, i32]
+    lib.qd_state_scalars_set.argtypes = [vp, dp, i32]
     lib.qd_comm_unique_id.argtypes = [vp, sz]
     lib.qd_comm_init.argtypes = [vp, vp, sz]
     lib.qd_comm_barrier.argtypes = [vp]
@@ -326,6 +352,7 @@ def load():
     lib.qd_route_schedule.argtypes = [vp, i32, dp]
     lib.qd_route_download.argtypes = [vp, i32, dp, sz]
     lib.qd_route_events.argtypes = [vp, dp, i32, ip]
+    lib.qd_route_restore.argtypes = [vp, dp, dp, dp, i64]
     lib.qd_hydronet_build.argtypes = [vp, i32, i32, u8p, dp, dbl, i32, dp, dp, dp, dbl, dp, ip, ip, u8p, ip, ip, i32,
                                       ip, ip]
     lib.qd_hydronet_sweeps.argtypes = [vp, ip]

@@ -506,6 +506,7 @@ extern "C" int qd_destroy(qd_handle c) {
     if (c->dcount) hipFree(c->dcount); if (c->hist) hipFree(c->hist); if (c->sel_state) hipFree(c->sel_state);
     if (c->zonal_tw) hipFree(c->zonal_tw);
     if (c->bands) hipFree(c->bands);
+    if (c->digest_out) hipFree(c->digest_out);
     qd_eco_free(c);
     if (c->sel_cand) hipFree(c->sel_cand); if (c->sel_ccount) hipFree(c->sel_ccount);
     if (c->med_pred) hipFree(c->med_pred);

@@ -31,6 +31,29 @@ __device__ __forceinline__ double qd_wave_fmax(double x) {
     return x;
 }
 
+// ---- the integer family (qd_digest.hip): sums mod 2^64.  Integer addition is associative, so unlike everything above the result
+// does NOT depend on the form, the launch shape or the order in which workgroups arrive.
+//   wave       the same five halvings, the 64-bit value moved as its two 32-bit halves (a DPP / permute lane move is 32 bits wide)
+//   workgroup  lane 0 of every wave -> LDS, one barrier, thread 0 adds the QD_BLOCK / 64 wave results; valid in thread 0
+__device__ __forceinline__ unsigned long long qd_wave_sum_u64(unsigned long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned int lo = __shfl_down((unsigned int)x, o, 64), hi = __shfl_down((unsigned int)(x >> 32), o, 64);
+        x += ((unsigned long long)hi << 32) | (unsigned long long)lo;
+    }
+    return x;
+}
+__device__ __forceinline__ unsigned long long qd_block_sum_u64(unsigned long long x) {      // every thread of the workgroup calls it
+    __shared__ unsigned long long sm[QD_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    x = qd_wave_sum_u64(x);
+    if (lane == 0) sm[wv] = x;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 1; k < QD_BLOCK / 64; ++k) x += sm[k];
+    return x;
+}
+
 // x ** e as NumPy evaluates it for a scalar exponent: 1, 2 and 0.5 take its exact fast paths
 __device__ __forceinline__ double qd_pow_np(double x, double e) {
     return e == 1.0 ? x : (e == 2.0 ? x * x : (e == 0.5 ? sqrt(x) : pow(x, e)));

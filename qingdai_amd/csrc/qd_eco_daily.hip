@@ -421,6 +421,12 @@ extern "C" int qd_eco_daily_log(qd_handle c, double* out, int max, int* n) {
     return qd_lane_drain(c, ed_lane(c), out, max, n, "qd_eco_daily_log", ED_MISSING);
 }
 
+int64_t qd_eco_daily_fired(qd_ctx* c, int64_t set) {
+    if (!c->edaily) return 0;
+    if (set >= 0) c->edaily->n_fired = set;
+    return c->edaily->n_fired;
+}
+
 extern "C" int qd_eco_daily_state(qd_handle c, int64_t* n_firings) {
     if (!c || !n_firings) return -1;
     *n_firings = c->edaily ? c->edaily->n_fired : 0;

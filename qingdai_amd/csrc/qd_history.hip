@@ -195,6 +195,27 @@ extern "C" int qd_history_read(qd_handle c, double* sums, int64_t* count) {
     return 0;
 }
 
+bool qd_history_planes(const qd_ctx* c, const double** sums, size_t* stride, int* n) {
+    const QdHistory* h = c->history;
+    if (!h) return false;
+    *sums = h->sums; *stride = h->stride; *n = h->n;
+    return true;
+}
+
+// the inverse of qd_history_read for an exact resume: an open window's sums [n][n_lat][n_lon] and its sample count
+extern "C" int qd_history_restore(qd_handle c, const double* sums, int64_t count) {
+    if (!c || !sums) return -1;
+    QdHistory* h = c->history;
+    if (!h) return qd_fail(c, "qd_history_restore: not configured (qd_history_configure first)");
+    if (count < 0) return qd_fail(c, "qd_history_restore: negative sample count");
+    hipSetDevice(c->desc.device);
+    const size_t row = c->geo.cells() * sizeof(double);
+    QD_HIP(c, hipMemcpy2DAsync(h->sums, h->stride * sizeof(double), sums, row, row, (size_t)h->n, hipMemcpyHostToDevice, c->stream));
+    QD_HIP(c, hipStreamSynchronize(c->stream));                // the host buffer is only borrowed for the call
+    h->count = count;
+    return 0;
+}
+
 extern "C" int qd_history_reset(qd_handle c) {
     if (!c) return -1;
     QdHistory* h = c->history;

@@ -479,6 +479,12 @@ extern "C" int qd_indiv_daily_weights(qd_handle c, double* w, int n_species) {
     return 0;
 }
 
+int64_t qd_indiv_daily_fired(qd_ctx* c, int64_t set) {
+    if (!c->idaily) return 0;
+    if (set >= 0) c->idaily->n_fired = set;
+    return c->idaily->n_fired;
+}
+
 extern "C" int qd_indiv_daily_state(qd_handle c, int64_t* n_firings) {
     if (!c || !n_firings) return -1;
     *n_firings = c->idaily ? c->idaily->n_fired : 0;

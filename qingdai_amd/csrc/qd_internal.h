@@ -213,6 +213,7 @@ struct qd_ctx {
     struct QdStateFrame* sframe = nullptr;   // 15-panel state frame: parameters, mosaic, vorticity plane, partials (qd_stateframe.hip)
     struct QdBudget* budget = nullptr;       // periodic budget diagnostics: schedule, SST snapshot, row partials, log (qd_budget_diag.hip)
     struct QdHistory* history = nullptr;     // time-mean history: entry table, sum planes, sample count, schedule (qd_history.hip)
+    unsigned long long* digest_out = nullptr; // [64] results of qd_state_digest, allocated at its first call (qd_digest.hip)
     double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
     int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
     double topogen_ms = -1.0;        // device time (events) of the kernels of the last qd_topogen_build on this handle (qd_topogen.hip)
@@ -524,7 +525,14 @@ bool qd_history_scheduled(const qd_ctx* c);
 bool qd_history_reads_lazy(const qd_ctx* c);                                    // an entry reads a lazily stored diagnostic (lazy_diag)
 struct QdSpanLane* qd_history_span_begin(qd_ctx* c, int n);
 int  qd_history_accumulate(qd_ctx* c, int group);
-const double* qd_route_last_record(const qd_ctx* c);                             // qd_route.hip: the last event's record on the device, or nullptr
+// what qd_state_digest and the exact resume (qd_digest.hip) need from the feature modules: their resident planes, and their firing
+// counts (set >= 0 stores it; -> the count as it then stands, 0 when the module is not configured)
+bool qd_route_planes(const qd_ctx* c, const double** buf, const double** flow, const double** lakes, int* n_lakes);    // qd_route.hip
+bool qd_history_planes(const qd_ctx* c, const double** sums, size_t* stride, int* n);                                 // qd_history.hip
+int64_t qd_phyto_daily_steps(qd_ctx* c, int64_t set);                            // qd_phyto_daily.hip
+int64_t qd_eco_daily_fired(qd_ctx* c, int64_t set);                              // qd_eco_daily.hip
+int64_t qd_indiv_daily_fired(qd_ctx* c, int64_t set);                            // qd_indiv_daily.hip
+const double* qd_route_last_record(const qd_ctx* c);                           // qd_route.hip: the last event's record on the device, or nullptr
 const double* qd_route_flow(const qd_ctx* c);                                    // qd_route.hip: the resident flow map [cells], or nullptr
 bool qd_phyto_daily_bands(const qd_ctx* c, const double** bands, int* n_bands, int64_t* n_steps);   // qd_phyto_daily.hip: the resident band stack, when configured
 bool qd_phyto_daily_couples(const qd_ctx* c);                               // the albedo launches blend WATER_ALPHA into the ocean

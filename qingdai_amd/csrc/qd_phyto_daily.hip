@@ -338,6 +338,12 @@ extern "C" int qd_phyto_daily_download_bands(qd_handle c, double* host, size_t n
     return 0;
 }
 
+int64_t qd_phyto_daily_steps(qd_ctx* c, int64_t set) {
+    if (!c->pdaily) return 0;
+    if (set >= 0) c->pdaily->n_steps = set;
+    return c->pdaily->n_steps;
+}
+
 extern "C" int qd_phyto_daily_state(qd_handle c, int64_t* n_steps) {
     if (!c || !n_steps) return -1;
     *n_steps = c->pdaily ? c->pdaily->n_steps : 0;

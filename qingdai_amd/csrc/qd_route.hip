@@ -381,6 +381,30 @@ int qd_route_step_impl(qd_ctx* c, double dt, int s) {
     return ev != 0.0 ? qr_event(c, ev, 1) : 0;
 }
 
+bool qd_route_planes(const qd_ctx* c, const double** buf, const double** flow, const double** lakes, int* n_lakes) {
+    const QdRoute* r = c->route;
+    if (!r) return false;
+    *buf = r->buf; *flow = r->flow; *lakes = r->lake_vol; *n_lakes = r->n_lakes;
+    return true;
+}
+
+// the inverse of qd_route_download for an exact resume: buffer and flow map [cells], lake volumes [n_lakes] (may be null without
+// lakes), the accumulations so far.  The event log and the schedule are left alone
+extern "C" int qd_route_restore(qd_handle c, const double* buffer, const double* flow, const double* lakes, int64_t steps) {
+    if (!c || !buffer || !flow) return -1;
+    QdRoute* r = c->route;
+    if (!r) return qd_fail(c, "qd_route_restore: no network configured (qd_route_configure first)");
+    if (r->n_lakes > 0 && !lakes) return qd_fail(c, "qd_route_restore: the network has lakes and no lake volumes were given");
+    if (steps < 0) return qd_fail(c, "qd_route_restore: negative step count");
+    hipSetDevice(c->desc.device);
+    QD_HIP(c, hipMemcpyAsync(r->buf, buffer, r->cells * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    QD_HIP(c, hipMemcpyAsync(r->flow, flow, r->cells * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (r->n_lakes > 0) QD_HIP(c, hipMemcpyAsync(r->lake_vol, lakes, (size_t)r->n_lakes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    QD_HIP(c, hipStreamSynchronize(c->stream));                // the host buffers are only borrowed for the call
+    r->steps = steps;
+    return 0;
+}
+
 const double* qd_route_flow(const qd_ctx* c) { return c->route ? c->route->flow : nullptr; }
 const double* qd_route_last_record(const qd_ctx* c) { return c->route ? c->route->last_rec : nullptr; }
 

@@ -33,6 +33,7 @@ class Device:
         self.params = params or QdParams.from_env()
         self.shape = (grid.n_lat, grid.n_lon)
         n_rows = grid.n_lat if n_rows is None else n_rows
+        self.whole_globe = row0 == 0 and n_rows == grid.n_lat and halo == 0 and world == 1     # not a latitude band
         desc = _lib.qd_grid_desc(grid.n_lat, grid.n_lon, row0, n_rows, halo, device, rank, world)
         h = ctypes.c_void_p()
         ps = self.params.to_struct()
@@ -668,6 +669,47 @@ class Device:
 
     def set_counters(self, a, o):
         self.lib.qd_set_step_counter(self.h, int(a), int(o))
+
+    # ---- state digest and the scalars of an exact resume (qd_digest.hip)
+    def digest(self, names):
+        """The 64-bit digests of resident planes (include/qingdai_hip.h: qd_state_digest), one launch per 64 of them -> np.uint64[n].
+        names: what _lib.state_ref takes -- field names, LAND_MASK, ICE_MASK, ROUTE_BUFFER, ROUTE_FLOW, ROUTE_LAKES, ECO_LAI_STACK,
+        INDIV_E_DAY, INDIV_STRESS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
+        self.flush()
+        refs = _c([_lib.state_ref(n) for n in names], np.int32)
+        out = np.zeros(refs.size, dtype=np.uint64)
+        for k in range(0, int(refs.size), _lib.STATE_DIGEST_MAX):
+            r, o = refs[k:k + _lib.STATE_DIGEST_MAX], out[k:k + _lib.STATE_DIGEST_MAX]
+            self._chk(self.lib.qd_state_digest(self.h, int(r.size), r.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                               o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))), "qd_state_digest")
+        return out
+
+    def state_scalars(self):
+        """The host-side scalars a step reads besides the planes and the step counters -> float64[STATE_SCALARS_N]."""
+        out = np.zeros(_lib.STATE_SCALARS_N, dtype=np.float64)
+        self._chk(self.lib.qd_state_scalars_get(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(out.size)), "qd_state_scalars_get")
+        return out
+
+    def set_state_scalars(self, values):
+        v = _c(values)
+        self._chk(self.lib.qd_state_scalars_set(self.h, v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(v.size)), "qd_state_scalars_set")
+
+    def route_restore(self, buffer, flow, lakes, steps):
+        """The inverse of route_download("BUFFER" / "FLOW" / "LAKES") plus the accumulation count."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        b, f = _c(buffer).ravel(), _c(flow).ravel()
+        lk = None if lakes is None or np.size(lakes) == 0 else _c(lakes).ravel()
+        if b.size != self._route_n[0] or f.size != self._route_n[0] or (0 if lk is None else lk.size) != self._route_n[1]:
+            raise ValueError("route_restore: the arrays do not have the configured network's cell and lake counts")
+        self._chk(self.lib.qd_route_restore(self.h, b.ctypes.data_as(dp), f.ctypes.data_as(dp), None if lk is None else lk.ctypes.data_as(dp),
+                                            int(steps)), "qd_route_restore")
+
+    def history_restore(self, sums, count):
+        """The inverse of history_read: an open window's sums [n][n_lat][n_lon] and its sample count."""
+        a = _c(sums)
+        if a.shape != (self._history_n,) + self.shape:
+            raise ValueError(f"history_restore: expected sums of shape {(self._history_n,) + self.shape}, got {a.shape}")
+        self._chk(self.lib.qd_history_restore(self.h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(count)), "qd_history_restore")
 
     def reduce(self, name, op):
         self.flush()

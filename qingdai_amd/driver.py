@@ -83,7 +83,7 @@ inside the step and each chunk's lines are printed after it, in the reference's 
 Time-mean history files (QD_HISTORY=1, default 0; nothing the reference has): every QD_HISTORY_SAMPLE_EVERY-th (default 1) step of a
 window of QD_HISTORY_EVERY_DAYS (default 10) planet-days -- S = max(1, int(days * day / dt + 0.5)) steps, counted on the run-local
 step index from where the lane is enabled, so after a resume the windows start again at the resumed step and an open window does not
-survive an autosave -- the fields of QD_HISTORY_FIELDS (f64 planes by their Device.get names, WIND_SPEED, CURRENT_SPEED; default TS,
+survive an autosave (QD_CHECKPOINT=1, below, carries it) -- the fields of QD_HISTORY_FIELDS (f64 planes by their Device.get names, WIND_SPEED, CURRENT_SPEED; default TS,
 H, U, V, Q, CLOUD, HICE, PRECIP, ALBEDO, ISR, OLR, EFLUX, PCOND, W_LAND, S_SNOW, RUNOFF, WIND_SPEED and with the ocean SST, UO, VO, ETA,
 QNET, CURRENT_SPEED; an unknown name or a field of a subsystem that is off is refused at start-up) are added into resident sums by a
 fifth span lane (qingdai_amd/history.py, qd_history_*).  A chunk ends with a window's last step, behind which
@@ -91,6 +91,25 @@ fifth span lane (qingdai_amd/history.py, qd_history_*).  A chunk ends with a win
 complete) is written and one [History] line printed; a and b are the start times over `day` of the first and last sampled step,
 `05.1f` like the frames (more decimals for windows shorter than 0.1 day).  The normal end of main writes the open window with
 complete = 0; the signal path does not.
+Exact resume (QD_CHECKPOINT=1, default 0; nothing the reference has: its restart holds 14 planes as f4 and t_seconds, and the step
+counters, routing buffers, tracers, carry-over planes, autotuned parameters and history window start again): every autosave --
+periodic, signal, atexit, final -- also writes <QD_DATA_DIR>/checkpoint.nc (QD_CHECKPOINT_PATH names another file) behind the
+reference's files, which are written exactly as before: every f64 plane as f8, the masks, the tracers, the routing buffers, the
+history sums, the ecology's qd_* variables, every clock and counter, the qd_params struct and a 64-bit digest of every plane taken
+on the device in one launch (qingdai_amd/checkpoint.py, qd_state_digest).  With QD_AUTOSAVE_LOAD=1 and no QD_RESTART_IN an existing
+checkpoint wins over atmosphere.nc, ocean.nc, ecology.nc and plankton.nc; the file is checked on the host against its own digests,
+and after the upload the device digests every plane again.  The step index continues, so the plot clock, the budget cadence, the
+autotuner and the history windows fire on the steps of the uncut run, whose state the resumed run reproduces bit for bit.  A file
+whose grid, ABI version, subsystem set or digests do not fit prints `[Checkpoint] refused '<path>': <reason>` and main returns 2,
+unless QD_CHECKPOINT_STRICT=0 takes the load order above instead (a file refused for its subsystem set is refused behind the
+routing, budget and history lanes, whose set it is checked against: those loads then run behind the lanes too, which hold nothing
+the loads touch).  A checkpoint is written at span boundaries only: a SIGINT / SIGTERM that arrives inside a chunk of the device
+loop is acted on behind that chunk (at most 200 steps), when the device and every host clock stand at the same step, and a save
+that finds the device elsewhere than the host clocks -- atexit after an error inside a span -- prints `[Checkpoint] (reason)
+skipped: ...` and leaves the last good file; the file records the step index and the device counter of the last span's end, and a
+load refuses a file in which they disagree.  Refused at start-up: QD_ECO_SPECIATION=1 and a daily_hook.  With
+the ecology on, ecology.nc and genes.json are written and read as under QD_ECO_PERSIST=2.  The open history window is not written
+as an incomplete file at the end of main: the checkpoint carries it.
 State frames (QD_STATE_PLOT=1, default 0; the same plot clock; plot_state, run_simulation.py:330-537, 2426-2428): the reference's
 15-panel status figure as a mosaic of 5 x 3 tiles of n_lat x n_lon pixels -- every tile its contourf sampled at the cell centres,
 with the coast, river, lake and star-position overlays, no titles, axes or colourbars -- composed on the device from the resident
@@ -216,6 +235,11 @@ class Simulation:
     truecolor = stateframe = figures = None
     plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
     _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
+    _in_span = _in_chunk = False           # a span is in flight (_run_lanes) / a chunk of run_loop is
+    _span_mark = (0, 0)                    # (step index, the device's atm counter as the host counts it) behind the bookkeeping of the
+                                           # last span; a save holds the device's own counter against it (checkpoint.span_consistent)
+    _stop_request = None                   # request_stop's callable
+    _index_base = 0                        # the step index a resumed run started from (load_checkpoint): run_loop's clocks count on from it
 
     def __init__(self, n_lat=None, n_lon=None, params: QdParams | None = None, use_ocean=None, quiet=False, device=0,
                  ecology=None, individuals=None, daily_hook=None, phyto=None, speciation_rng=None):
@@ -277,6 +301,7 @@ class Simulation:
         self.forcing = ThermalForcing(self.grid, OrbitalSystem())
         self.t = 0.0
         self._step_index = 0
+        self._span_mark = (0, 0)                               # a fresh handle counts from zero
         self.dt = int(env.get("QD_DT_SECONDS", "300"))
         # ecology (run_simulation.py:1324-1423): adapter + canopy population + sampled individuals, state on the device
         self.daily_hook = daily_hook
@@ -369,6 +394,25 @@ class Simulation:
 
     def save(self, path):
         save_restart(path, self.grid, self.dev, self.t, self.land_mask, with_ocean=self.ocean is not None)
+
+    # -- exact resume (qingdai_amd/checkpoint.py)
+    def save_checkpoint(self, path, reason=None):
+        """Write the whole resident state, every clock and the device digests to `path` (temporary name, then os.replace) -> the run
+        digest.  Unlike `save`, a fresh Simulation that loads the file continues this run bit for bit."""
+        from . import checkpoint
+        return checkpoint.save(self, path, reason=reason)
+
+    def load_checkpoint(self, path, env=None):
+        """Put `path` back into this freshly built Simulation (its routing, budget and history lanes enabled as in the saved run) ->
+        the run digest.  Raises checkpoint.CheckpointRefused, with nothing touched, when the file does not fit the run."""
+        from . import checkpoint
+        return checkpoint.load(self, path, env=env)
+
+    def digest(self):
+        """{plane name: 64-bit digest} of every resident plane of the checkpoint set, taken on the device in one call, plus "run",
+        the digest of the digests: two runs are in the same state exactly when these agree."""
+        from . import checkpoint
+        return checkpoint.simulation_digest(self)
 
     def load_ocean_override(self, path):
         """run_simulation.py:1497-1509 / 1542-1553: QD_LOAD_OCEAN=1 (default) lets a standardized data/ocean.nc override the ocean
@@ -685,15 +729,31 @@ class Simulation:
         cadences may fall on one step).  after_chunk(done, next_autosave_t) -> the threshold for the chunks that follow."""
         done = 0
         while done < n_total:
-            due = self.outputs_due(done, min(200, n_total - done))
-            n = chunk_until(self.t, self.dt, next_autosave_t, n_total - done, fire_in=min((k for k, _, _ in due), default=None))
-            self.run_steps(n)
-            done += n
-            for k, t_days, run in due:
-                if n == k:                                     # the chunk ended with the firing step
-                    run(t_days)
-            if after_chunk is not None:
-                next_autosave_t = after_chunk(done, next_autosave_t)
+            self._in_chunk = True                              # a stop asked for in here (request_stop) waits for the chunk's end
+            try:
+                due = self.outputs_due(self._index_base + done, min(200, n_total - done))
+                n = chunk_until(self.t, self.dt, next_autosave_t, n_total - done, fire_in=min((k for k, _, _ in due), default=None))
+                self.run_steps(n)
+                done += n
+                for k, t_days, run in due:
+                    if n == k:                                 # the chunk ended with the firing step
+                        run(t_days)
+                if after_chunk is not None:
+                    next_autosave_t = after_chunk(done, next_autosave_t)
+            finally:
+                self._in_chunk = False
+            if self._stop_request is not None:                 # every clock, delivery, window file and output of the chunk is done
+                stop, self._stop_request = self._stop_request, None
+                stop()
+
+    def request_stop(self, stop):
+        """Called from a signal handler that wants a consistent state: inside a chunk of run_loop -> True, and stop() is called
+        behind that chunk (at most 200 steps), when the device and every host clock stand at the same step; else -> False and
+        the caller acts at once."""
+        if not self._in_chunk:
+            return False
+        self._stop_request = stop
+        return True
 
     # -- speciation (adapter.py:437-466 inside run_simulation.py:1786-1864)
     def speciation_due(self, n_max):
@@ -786,12 +846,16 @@ class Simulation:
         lanes = {k: p for k, p in (("phyto_daily", self.phyto_daily), ("routing", self.routing), ("budget", self.budget),
                                    ("eco_daily", eco_daily), ("history", self.history)) if p is not None}
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
+        # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
+        # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
+        self._in_span = True
         try:
             self.dev.step_n(stars, float(self.dt), with_ocean=self.ocean is not None, with_physics=True, pass_albedo=False,
                             with_hydrology=True, energy_diag=energy_diag, ecology=self.eco is not None, phyto=self.phyto_transport,
                             t0=times, **lanes)
         except Exception:
             self._t_origin = origin                            # nothing ran: the clock stays where it was, like the lanes' clocks
+            self._in_span = False                              # (where the device did run a part of it, the span mark no longer fits)
             raise
         self._t = t_next
         self._step_index += n
@@ -799,6 +863,8 @@ class Simulation:
             recs = p.span_deliver(float(self.dt))              # the span's lines, oldest first
             if p is eco_daily and self.speciation is not None and len(recs):
                 self._firings_passed(len(recs), times, *eco_clock)
+        self._span_mark = (self._step_index, self._span_mark[1] + n)      # qd_step_n moves the device's atm counter by one per step
+        self._in_span = False
 
     def _firings_passed(self, n_fired, times, accum0, struck0):
         """Behind a span's eco-daily firings under QD_ECO_SPECIATION=1: none of them was a hit, and the weights and genes are the
@@ -948,9 +1014,11 @@ def speciation_enabled(env, *, eco_daily, daily_hook):
 
 def eco_persist_level(env):
     """QD_ECO_PERSIST (default 0): 1 writes and reads data/ecology.nc and data/genes.json with the reference's variable set, 2 adds the
-    qd_* extension variables with which the ecology lanes resume bit for bit (qingdai_amd/ecology.py persist_level)."""
+    qd_* extension variables with which the ecology lanes resume bit for bit (qingdai_amd/ecology.py persist_level).  Under
+    QD_CHECKPOINT=1 the level is 2 whatever the variable says: ecology.nc and genes.json then fit the checkpoint beside them."""
     from .ecology import persist_level
-    return persist_level(env)
+    from .checkpoint import read_env
+    return 2 if read_env(env)["enabled"] else persist_level(env)
 
 
 def indiv_daily_enabled(env, *, eco_daily, ecology, population, individuals, daily_hook):
@@ -1032,42 +1100,81 @@ def main(argv=None):
     data_dir = env.get("QD_DATA_DIR", "data")
     restart_in = env.get("QD_RESTART_IN")
     autosave_nc = os.path.join(data_dir, "atmosphere.nc")
-    loaded = None
-    if restart_in and os.path.exists(restart_in):
-        loaded = restart_in
-    elif not restart_in and int(env.get("QD_AUTOSAVE_LOAD", "1")) == 1 and os.path.exists(autosave_nc):
-        loaded = autosave_nc
-    if loaded:
-        try:
-            sim.load(loaded)
-            print(f"[{'Restart' if loaded == restart_in else 'Autosave'}] loaded '{loaded}' at t={sim.t:.1f} s")
-            if int(env.get("QD_LOAD_OCEAN", "1")) == 1:
-                try:
-                    if sim.load_ocean_override(os.path.join(data_dir, "ocean.nc")):
-                        print("[Restart] Ocean state overridden from 'data/ocean.nc'.")
-                except Exception as e:     # noqa: BLE001
-                    print(f"[Restart] ocean.nc load skipped: {e}")
-        except Exception as e:             # noqa: BLE001
-            print(f"[Restart] Failed to load '{loaded}': {e}\nContinuing with fresh init.")
-            loaded = None
-    # run_simulation.py:1464-1488 / 1566-1590: genes.json, then the ecology autosave, behind either checkpoint or none
-    # (QD_ECO_PERSIST >= 1; gated by QD_AUTOSAVE_LOAD alone, like the reference)
-    sim.load_ecology(data_dir, env)
-    # run_simulation.py:1377-1399: data/plankton.nc restores the tracer distributions at startup (QD_LOAD_PLANKTON=1, default)
-    if sim.phyto is not None and int(env.get("QD_LOAD_PLANKTON", "1")) == 1:
-        pnc = os.path.join(data_dir, "plankton.nc")
-        if os.path.exists(pnc):
-            loader = sim.phyto_daily if sim.phyto_daily is not None else sim.phyto
-            print(f"[Phyto] plankton.nc load {'OK' if loader.load_distribution_nc(pnc) else 'skipped/failed'}.")
-    if not loaded and sim.t == 0.0:
-        if env.get("QD_ORBIT_EPOCH_SECONDS"):
-            sim.t = float(env["QD_ORBIT_EPOCH_SECONDS"])
-        elif env.get("QD_ORBIT_EPOCH_DAYS"):
-            sim.t = float(env["QD_ORBIT_EPOCH_DAYS"]) * day
+    # QD_CHECKPOINT=1 (qingdai_amd/checkpoint.py): with QD_AUTOSAVE_LOAD=1 and no QD_RESTART_IN an existing checkpoint file wins over
+    # atmosphere.nc, ocean.nc, ecology.nc and plankton.nc -- the run then continues the saved one bit for bit.  A file that does not
+    # fit is refused with one line and start-up fails, unless QD_CHECKPOINT_STRICT=0 takes the load order above instead
+    from . import checkpoint
+    ck = checkpoint.read_env(env, data_dir)
+    ck_file = None
+    if ck["enabled"]:
+        why = checkpoint.startup_refusal(sim, env)
+        if why:
+            print(f"[Checkpoint] {why}")
+            return 2
+        if sim.eco is not None and sim.eco.pop is not None:
+            from .ecology import persist_level
+            if persist_level(env) < 2:
+                print("[Checkpoint] ecology.nc and genes.json are written and read as under QD_ECO_PERSIST=2.")
+        if not restart_in and int(env.get("QD_AUTOSAVE_LOAD", "1")) == 1 and os.path.exists(ck["path"]):
+            try:
+                ck_file = checkpoint.read(ck["path"])
+                checkpoint.check_grid_and_abi(ck_file, sim.dev.shape, sim.dev)
+                checkpoint.verify_file(ck_file)
+            except checkpoint.CheckpointRefused as e:
+                print(f"[Checkpoint] refused '{ck['path']}': {e}")
+                if ck["strict"]:
+                    return 2
+                ck_file = None
+
+    def _legacy_load():
+        loaded = None
+        if restart_in and os.path.exists(restart_in):
+            loaded = restart_in
+        elif not restart_in and int(env.get("QD_AUTOSAVE_LOAD", "1")) == 1 and os.path.exists(autosave_nc):
+            loaded = autosave_nc
+        if loaded:
+            try:
+                sim.load(loaded)
+                print(f"[{'Restart' if loaded == restart_in else 'Autosave'}] loaded '{loaded}' at t={sim.t:.1f} s")
+                if int(env.get("QD_LOAD_OCEAN", "1")) == 1:
+                    try:
+                        if sim.load_ocean_override(os.path.join(data_dir, "ocean.nc")):
+                            print("[Restart] Ocean state overridden from 'data/ocean.nc'.")
+                    except Exception as e:     # noqa: BLE001
+                        print(f"[Restart] ocean.nc load skipped: {e}")
+            except Exception as e:             # noqa: BLE001
+                print(f"[Restart] Failed to load '{loaded}': {e}\nContinuing with fresh init.")
+                loaded = None
+        # run_simulation.py:1464-1488 / 1566-1590: genes.json, then the ecology autosave, behind either checkpoint or none
+        # (QD_ECO_PERSIST >= 1; gated by QD_AUTOSAVE_LOAD alone, like the reference)
+        sim.load_ecology(data_dir, env)
+        # run_simulation.py:1377-1399: data/plankton.nc restores the tracer distributions at startup (QD_LOAD_PLANKTON=1, default)
+        if sim.phyto is not None and int(env.get("QD_LOAD_PLANKTON", "1")) == 1:
+            pnc = os.path.join(data_dir, "plankton.nc")
+            if os.path.exists(pnc):
+                loader = sim.phyto_daily if sim.phyto_daily is not None else sim.phyto
+                print(f"[Phyto] plankton.nc load {'OK' if loader.load_distribution_nc(pnc) else 'skipped/failed'}.")
+        if not loaded and sim.t == 0.0:
+            if env.get("QD_ORBIT_EPOCH_SECONDS"):
+                sim.t = float(env["QD_ORBIT_EPOCH_SECONDS"])
+            elif env.get("QD_ORBIT_EPOCH_DAYS"):
+                sim.t = float(env["QD_ORBIT_EPOCH_DAYS"]) * day
+    if ck_file is None:
+        _legacy_load()
     sim.enable_routing(env)
     sim.enable_budget_diag(env)
     sim.enable_history(env)
-    sim.bootstrap_ecology()
+    if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
+        try:
+            sim.load_checkpoint(ck_file, env)
+        except checkpoint.CheckpointRefused as e:
+            print(f"[Checkpoint] refused '{ck['path']}': {e}")
+            if ck["strict"]:
+                return 2
+            ck_file = None
+            _legacy_load()
+    if ck_file is None:                                        # (a resumed run had its bootstrap before its first step)
+        sim.bootstrap_ecology()
     t0 = sim.t
     n_total = len(np.arange(t0, t0 + duration, sim.dt))
     print(f"Grid resolution: {sim.grid.n_lat} lat x {sim.grid.n_lon} lon | dt = {sim.dt} s | "
@@ -1098,11 +1205,24 @@ def main(argv=None):
             print(f"[Autosave] ({reason}) core state saved to 'data/atmosphere.nc' at t={sim.t:.1f} s")
         except Exception as e:     # noqa: BLE001  (the reference never lets I/O kill the run)
             print(f"[Autosave] skipped: {e}")
+        if ck["enabled"]:                                      # behind the reference's files, which are written exactly as before
+            try:
+                sim.save_checkpoint(ck["path"], reason=reason)
+            except Exception as e:     # noqa: BLE001  (not at a span boundary, or I/O: the last good file stays)
+                print(f"[Checkpoint] ({reason}) skipped: {e}")
         state["saved"] = True
 
-    def _on_signal(signum, _frame):
+    def _stop(signum):
         _autosave("signal")
         sys.exit(130 if signum == signal.SIGINT else 143)
+
+    def _on_signal(signum, _frame):
+        # Python runs a handler right behind the device call it interrupted, before the span's bookkeeping: the device is then up to
+        # a chunk ahead of the host clocks.  The f4 files promise no continuation and are written at once, as always; a run that
+        # writes checkpoints waits for the end of the chunk in flight, where both stand at the same step
+        if ck["enabled"] and getattr(sim, "request_stop", None) is not None and sim.request_stop(lambda: _stop(signum)):
+            return
+        _stop(signum)
     signal.signal(signal.SIGINT, _on_signal)
     signal.signal(signal.SIGTERM, _on_signal)
     atexit.register(lambda: _autosave("atexit"))
@@ -1123,7 +1243,9 @@ def main(argv=None):
                 next_autosave_t += autosave_dt
         return next_autosave_t
     sim.run_loop(n_total, next_autosave_t if autosave_on else None, _after_chunk)
-    if sim.history is not None:                                # the open window, marked incomplete (the signal path does not get here)
+    if sim.history is not None and not (ck["enabled"] and autosave_on):
+        # the open window, marked incomplete (the signal path does not get here); under QD_CHECKPOINT=1 the final checkpoint carries
+        # it instead, and the run that resumes writes it when it is complete
         sim.flush_history(complete=0)
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
