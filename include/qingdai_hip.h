@@ -158,9 +158,23 @@ int qd_driver_physics(qd_handle h, double dt);
 /* run_simulation.py:2290-2339: commit the provisional snowpack, update the land bucket (hydrology.py:219-260) */
 int qd_hydrology_commit(qd_handle h, double dt);
 /* benchmark_jax.py:124-158 as one resident loop of n steps: forcing -> albedo -> time_step [-> ocean
- * coupling] [-> hydrology commit].  flags bit0 = with_ocean, bit1 = with_driver_physics (else the simple
- * ocean/land albedo of benchmark_jax.py:129), bit2 = pass albedo to time_step, bit3 = hydrology commit, bit4 = energy diagnostics on the first step (qd_energy_diagnostics_last), bit5 = ecology sub-step (qd_eco_substep, and qd_indiv_substep when a pool is configured; needs bit1), bit6 = tracer transport after the ocean step (qd_phyto_advect_diffuse; needs bit0 and qd_phyto_configure), bit7 = river routing after the hydrology commit (qd_route_accumulate, and qd_route_event on the steps a qd_route_schedule of n entries names; needs bit3 and qd_route_configure), bit8 = daily phytoplankton step at the top of the steps a qd_phyto_daily_schedule of n entries names (SST with bit0, else TS; needs bit1 and qd_phyto_daily_configure), bit9 = daily vegetation step at the top of the steps a qd_eco_daily_schedule of n entries names (needs bit5 and qd_eco_daily_configure).  `stars` holds n rows of 7 host scalars
+ * coupling] [-> hydrology commit].  `flags` is a mask of enum qd_step_flag.  `stars` holds n rows of 7 host scalars
  * (flux_A, decl_A, ra_A, flux_B, decl_B, ra_B, theta), evaluated by the caller as forcing.py:85-125 does. */
+enum qd_step_flag {
+    QD_STEP_WITH_OCEAN = 1,        /* bit0: the ocean coupling */
+    QD_STEP_WITH_PHYSICS = 2,      /* bit1: the driver physics (else the simple ocean/land albedo of benchmark_jax.py:129) */
+    QD_STEP_PASS_ALBEDO = 4,       /* bit2: pass albedo to time_step */
+    QD_STEP_WITH_HYDROLOGY = 8,    /* bit3: hydrology commit */
+    QD_STEP_ENERGY_DIAG = 16,      /* bit4: energy diagnostics on the first step (qd_energy_diagnostics_last) */
+    QD_STEP_ECOLOGY = 32,          /* bit5: ecology sub-step (qd_eco_substep, and qd_indiv_substep when a pool is configured; needs bit1) */
+    QD_STEP_PHYTO = 64,            /* bit6: tracer transport after the ocean step (qd_phyto_advect_diffuse; needs bit0 and qd_phyto_configure) */
+    QD_STEP_ROUTING = 128,         /* bit7: river routing after the hydrology commit (qd_route_accumulate, and qd_route_event on the steps a
+                                      qd_route_schedule of n entries names; needs bit3 and qd_route_configure) */
+    QD_STEP_PHYTO_DAILY = 256,     /* bit8: daily phytoplankton step at the top of the steps a qd_phyto_daily_schedule of n entries names
+                                      (SST with bit0, else TS; needs bit1 and qd_phyto_daily_configure) */
+    QD_STEP_ECO_DAILY = 512        /* bit9: daily vegetation step at the top of the steps a qd_eco_daily_schedule of n entries names (needs
+                                      bit5 and qd_eco_daily_configure) */
+};
 int qd_step_n(qd_handle h, int n, double dt, int flags, const double* stars);
 int qd_last_ocean_nsub(qd_handle h, int* n_sub);
 int qd_sync(qd_handle h);
@@ -267,6 +281,8 @@ int qd_phyto_advect_diffuse(qd_handle h, double dt_seconds);             /* all 
  * With `couple` set, the albedo launches override the ocean base albedo with clip(WATER_ALPHA, 0, 1) from the first daily step on
  * (run_simulation.py:2121-2128). */
 #define QD_PHYTO_DAILY_LOG_W 4
+#define QD_SPAN_LOG_CAP 4096          /* records the device log of a span lane (this one, the daily vegetation and individuals' steps, routing,
+                                         the budget diagnostics) holds between two drains */
 typedef struct qd_phyto_daily_params {
     int32_t n_species, n_bands;
     int32_t idx_490;             /* band nearest 490 nm */
@@ -586,6 +602,7 @@ int qd_tiles_download(qd_handle h, int which, void* host, size_t n);
  * segments ordered by junction level.  The buffer accumulates RUNOFF every step; an event routes it with at most seven launches,
  * fills the flow map and appends one record of QD_ROUTE_LOG_W = 8 doubles to a device event log:
  * {step, event_dt, ocean_inflow_kgps, mass_closure_error_kg, mass_input_kg, ocean_kg, residual_kg, lake_delta_kg}. */
+#define QD_ROUTE_LOG_W 8
 typedef struct qd_route_plan {
     int32_t n_cells;                    /* n_lat * n_lon */
     int32_t n_seg, n_seg_cells, n_levels, n_jp, n_lakes;
@@ -725,20 +742,32 @@ int qd_history_restore(qd_handle h, const double* sums, int64_t count);
  * addition is associative: the value does not depend on the launch shape or on the order in which the workgroups finish.
  * A ref is a qd_field id (every f64 field, QD_F_LAND_MASK, QD_F_ICE_MASK) or one of the resident planes that have no field id: */
 enum qd_state_ref {
-    QD_SR_PHYTO_TRACER = 200,      /* + s: the tracer of species s (< 64), [n_lat][n_lon] */
+    QD_SR_PHYTO_TRACER = 200,      /* + s: the tracer of species s (< QD_STATE_REF_TRACERS), [n_lat][n_lon] */
     QD_SR_ROUTE_BUFFER = 300, QD_SR_ROUTE_FLOW = 301,   /* what qd_route keeps: the buffer and the flow map [n_lat][n_lon] ... */
     QD_SR_ROUTE_LAKES = 302,       /* ... and the lake volumes [n_lakes] */
     QD_SR_ECO_LAI_STACK = 310,     /* the LAI stack of the daily vegetation step, [n_species * n_layers][n_lat][n_lon] as ONE plane */
     QD_SR_INDIV_E_DAY = 320, QD_SR_INDIV_STRESS = 321,   /* the individuals' buffers [n_indiv] */
-    QD_SR_HISTORY_SUM = 400        /* + k: the sum plane of history entry k (< 32) */
+    QD_SR_HISTORY_SUM = 400        /* + k: the sum plane of history entry k (< QD_STATE_REF_HISTORY_SUMS) */
 };
+#define QD_STATE_REF_TRACERS 64                         /* index range of QD_SR_PHYTO_TRACER */
+#define QD_STATE_REF_HISTORY_SUMS QD_HISTORY_MAX_ENTRIES   /* index range of QD_SR_HISTORY_SUM */
 #define QD_STATE_DIGEST_MAX 64
 /* n <= 64 refs -> out[n].  Refused: latitude bands, an unknown ref, a ref whose subsystem is not configured (the line names it). */
 int qd_state_digest(qd_handle h, int n, const int32_t* refs, uint64_t* out);
-/* The host-side scalars a step reads besides the planes and the two step counters -- cloud_eff_valid, the ecology sub-step's clock,
- * cache flags and versions, the accumulator of the individuals' sub-step, the firing counts of the daily lanes, the last span's
- * energy-budget means -- as n = QD_STATE_SCALARS_N doubles (csrc/qd_digest.hip names the slots); set puts them back on a fresh
- * handle that was configured like the one they were read from. */
+/* The host-side scalars a step reads besides the planes and the two step counters, as n = QD_STATE_SCALARS_N doubles in the slots
+ * of enum qd_state_scalar; set puts them back on a fresh handle that was configured like the one they were read from. */
+enum qd_state_scalar {
+    QD_SS_CLOUD_EFF_VALID = 0,
+    QD_SS_HAS_ELEVATION = 1,          /* read only: the elevation map is the run's own */
+    QD_SS_ECO_HOURS = 2, QD_SS_ECO_NEXT_H = 3, QD_SS_ECO_COUNT = 4,   /* the ecology sub-step's clock */
+    QD_SS_HAVE_LAI = 5, QD_SS_F_VALID = 6, QD_SS_ALPHA_VALID = 7, QD_SS_ALPHA_DIRTY = 8, QD_SS_BANDED_VALID = 9, QD_SS_WATER_VALID = 10,
+    QD_SS_LAI_VERSION = 11, QD_SS_SNAP_VERSION = 12, QD_SS_N_RECOMPUTE = 13,
+    QD_SS_INDIV_PERIOD = 14,          /* the individuals' sub-step period (-1: not begun) */
+    QD_SS_INDIV_ACCUM = 15, QD_SS_INDIV_FIRED = 16,   /* its accumulator, its firings */
+    QD_SS_PHYTO_DAILY_STEPS = 17, QD_SS_ECO_DAILY_FIRED = 18, QD_SS_INDIV_DAILY_FIRED = 19,   /* the counts of the daily lanes */
+    QD_SS_LAST_NSUB = 20,
+    QD_SS_LAST_DIAG = 21              /* .. 30: the energy-budget means of the last span that took them; 31 reserved (0) */
+};
 #define QD_STATE_SCALARS_N 32
 int qd_state_scalars_get(qd_handle h, double* out, int n);
 int qd_state_scalars_set(qd_handle h, const double* in, int n);

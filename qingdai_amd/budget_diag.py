@@ -14,8 +14,11 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._lib import BUDGET_LOG_W as LOG_W, C
+
 EVERY = 200                      # run_simulation.py:2150, 2264, 2275, 2350: `i % 200 == 0`
-LINE_ENERGY, LINE_OCEAN, LINE_OCEAN_ENERGY, LINE_HUMIDITY, LINE_WATER = 1, 2, 4, 8, 16      # QD_BD_LINE_*
+LINE_ENERGY, LINE_OCEAN, LINE_OCEAN_ENERGY, LINE_HUMIDITY, LINE_WATER = (
+    C["QD_BD_LINE_" + n] for n in ("ENERGY", "OCEAN", "OCEAN_ENERGY", "HUMIDITY", "WATER"))
 FIRE_MAIN, FIRE_OCEAN_E = 1, 2
 
 # record slots (include/qingdai_hip.h, QD_BUDGET_LOG_W doubles)
@@ -27,7 +30,6 @@ REC = {k: i for i, k in enumerate(
      "W_E", "W_P", "W_R", "W_CWV", "W_ICE", "W_WLAND", "W_SSNOW",
      "R_FLOW", "R_INFLOW", "R_ERR"))}
 REC.update({"RAN_ENERGY": 32, "RAN_OCEAN_ENERGY": 33, "RAN_OCEAN": 34, "RAN_HUMIDITY": 35, "RAN_WATER": 36, "FIRE": 37})
-LOG_W = 40
 
 
 def read_env(env):

@@ -678,13 +678,14 @@ int qd_side_join(qd_ctx* c) {
 extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double* stars) {
     if (!c || !stars) return -1;
     hipSetDevice(c->desc.device);
-    const int with_ocean = flags & 1, with_phys = flags & 2, pass_alb = flags & 4, with_hydro = flags & 8, want_diag = flags & 16;
-    const int with_eco = flags & 32, with_phyto = flags & 64;
+    const int with_ocean = flags & QD_STEP_WITH_OCEAN, with_phys = flags & QD_STEP_WITH_PHYSICS, pass_alb = flags & QD_STEP_PASS_ALBEDO;
+    const int with_hydro = flags & QD_STEP_WITH_HYDROLOGY, want_diag = flags & QD_STEP_ENERGY_DIAG;
+    const int with_eco = flags & QD_STEP_ECOLOGY, with_phyto = flags & QD_STEP_PHYTO;
     if (with_phyto && !with_ocean) return qd_fail(c, "qd_step_n: the tracer transport (bit6) needs the ocean step (bit0)");
     if (with_phyto && c->phyto.S == 0) return qd_fail(c, "qd_step_n: bit6 set but qd_phyto_configure has not been called");
     if (with_eco && !with_phys) return qd_fail(c, "qd_step_n: the ecology sub-step (bit5) needs the driver physics (bit1)");
     if (with_eco && !c->eco.configured) return qd_fail(c, "qd_step_n: bit5 set but qd_eco_configure has not been called");
-    const int with_route = flags & 128;
+    const int with_route = flags & QD_STEP_ROUTING;
     if (with_route && !with_hydro) return qd_fail(c, "qd_step_n: river routing (bit7) needs the hydrology commit (bit3)");
     // whatever way this call ends: a lane's schedule was for this span only, and once the loop has begun the per-span switches are
     // back to what a stand-alone qd_* call expects
@@ -694,9 +695,9 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (begun) { c->diag_write = 1; c->want_pcond_ahead = 0; c->pcond_ahead = 0; c->defer_final = 0; c->final_pending.on = 0; qd_saf_drop(c); }
     } } span{c};
     if (with_route && !(span.lane[QD_LANE_ROUTE] = qd_route_span_begin(c, n))) return -1;
-    const int with_pdaily = flags & 256;
+    const int with_pdaily = flags & QD_STEP_PHYTO_DAILY;
     if (with_pdaily && !(span.lane[QD_LANE_PHYTO_DAILY] = qd_phyto_daily_span_begin(c, n, with_phys))) return -1;
-    const int with_edaily = flags & 512;
+    const int with_edaily = flags & QD_STEP_ECO_DAILY;
     if (with_edaily && !(span.lane[QD_LANE_ECO_DAILY] = qd_eco_daily_span_begin(c, n, with_eco))) return -1;
     // the individuals' daily step (qd_indiv_daily_configure) fires with the daily lane and logs into a lane of its own
     const bool with_idaily = with_edaily && c->idaily;

@@ -153,24 +153,31 @@ extern "C" int qd_state_digest(qd_handle c, int n, const int32_t* refs, uint64_t
 
 // ------------------------------------------------------------------ the host-side scalars of an exact resume
 // What a step reads from the context besides the planes and the two step counters (qd_internal.h: qd_ctx, QdEco), as doubles (the
-// counts stay far below 2^53).  Slots, QD_STATE_SCALARS_N = 32 of them:
+// counts stay far below 2^53).  The QD_STATE_SCALARS_N = 32 slots are enum qd_state_scalar of the public header, which the code
+// below uses by name; what they hold:
 //   0 cloud_eff_valid   1 has_elevation (read only: the elevation map is the run's own)   2 eco.hours   3 eco.next_h   4 eco.count
 //   5 have_lai   6 f_valid   7 alpha_valid   8 alpha_dirty   9 banded_valid   10 water_valid   11 lai_version   12 snap_version
 //   13 n_recompute   14 the individuals' sub-step period (-1: not begun)   15 its accumulator   16 its firings
 //   17 daily phytoplankton steps   18 daily vegetation firings   19 firings of the individuals' daily step   20 last_nsub
 //   21 .. 30 the energy-budget means of the last span that took them   31 reserved (0)
+static_assert(QD_STATE_REF_TRACERS == QD_MAX_SPECIES, "the public index range of QD_SR_PHYTO_TRACER is the species cap");
+static_assert(QD_SS_LAST_DIAG + 10 < QD_STATE_SCALARS_N, "the ten energy-budget means and the reserved slot end the table");
 extern "C" int qd_state_scalars_get(qd_handle c, double* out, int n) {
     if (!c || !out) return -1;
     if (n != QD_STATE_SCALARS_N) return qd_fail(c, "qd_state_scalars_get: n is not QD_STATE_SCALARS_N (ABI drift)");
     const QdEco& E = c->eco;
-    const double v[QD_STATE_SCALARS_N] = {
-        (double)c->cloud_eff_valid, (double)c->has_elevation, E.hours, E.next_h, (double)E.count,
-        (double)E.have_lai, (double)E.f_valid, (double)E.alpha_valid, (double)E.alpha_dirty, (double)E.banded_valid, (double)E.water_valid,
-        (double)E.lai_version, (double)E.snap_version, (double)E.n_recompute, E.period, E.accum, (double)E.n_fired,
-        (double)qd_phyto_daily_steps(c, -1), (double)qd_eco_daily_fired(c, -1), (double)qd_indiv_daily_fired(c, -1), (double)c->last_nsub,
-        c->last_diag[0], c->last_diag[1], c->last_diag[2], c->last_diag[3], c->last_diag[4], c->last_diag[5], c->last_diag[6],
-        c->last_diag[7], c->last_diag[8], c->last_diag[9], 0.0};
-    std::copy(v, v + QD_STATE_SCALARS_N, out);
+    std::fill(out, out + QD_STATE_SCALARS_N, 0.0);
+    out[QD_SS_CLOUD_EFF_VALID] = (double)c->cloud_eff_valid; out[QD_SS_HAS_ELEVATION] = (double)c->has_elevation;
+    out[QD_SS_ECO_HOURS] = E.hours; out[QD_SS_ECO_NEXT_H] = E.next_h; out[QD_SS_ECO_COUNT] = (double)E.count;
+    out[QD_SS_HAVE_LAI] = (double)E.have_lai; out[QD_SS_F_VALID] = (double)E.f_valid; out[QD_SS_ALPHA_VALID] = (double)E.alpha_valid;
+    out[QD_SS_ALPHA_DIRTY] = (double)E.alpha_dirty; out[QD_SS_BANDED_VALID] = (double)E.banded_valid;
+    out[QD_SS_WATER_VALID] = (double)E.water_valid;
+    out[QD_SS_LAI_VERSION] = (double)E.lai_version; out[QD_SS_SNAP_VERSION] = (double)E.snap_version;
+    out[QD_SS_N_RECOMPUTE] = (double)E.n_recompute;
+    out[QD_SS_INDIV_PERIOD] = E.period; out[QD_SS_INDIV_ACCUM] = E.accum; out[QD_SS_INDIV_FIRED] = (double)E.n_fired;
+    out[QD_SS_PHYTO_DAILY_STEPS] = (double)qd_phyto_daily_steps(c, -1); out[QD_SS_ECO_DAILY_FIRED] = (double)qd_eco_daily_fired(c, -1);
+    out[QD_SS_INDIV_DAILY_FIRED] = (double)qd_indiv_daily_fired(c, -1); out[QD_SS_LAST_NSUB] = (double)c->last_nsub;
+    std::copy(c->last_diag, c->last_diag + 10, out + QD_SS_LAST_DIAG);
     return 0;
 }
 
@@ -179,14 +186,17 @@ extern "C" int qd_state_scalars_set(qd_handle c, const double* in, int n) {
     if (n != QD_STATE_SCALARS_N) return qd_fail(c, "qd_state_scalars_set: n is not QD_STATE_SCALARS_N (ABI drift)");
     if (!qd_whole_globe(c)) return qd_fail(c, "qd_state_scalars_set: an exact resume needs a whole-globe handle; latitude bands are not supported");
     QdEco& E = c->eco;
-    c->cloud_eff_valid = in[0] != 0.0;
-    E.hours = in[2]; E.next_h = in[3]; E.count = (int64_t)in[4];
-    E.have_lai = in[5] != 0.0; E.f_valid = in[6] != 0.0; E.alpha_valid = in[7] != 0.0; E.alpha_dirty = in[8] != 0.0;
-    E.banded_valid = in[9] != 0.0; E.water_valid = in[10] != 0.0;
-    E.lai_version = (int)in[11]; E.snap_version = (int)in[12]; E.n_recompute = (int)in[13];
-    E.period = in[14]; E.accum = in[15]; E.n_fired = (int64_t)in[16];
-    qd_phyto_daily_steps(c, (int64_t)in[17]); qd_eco_daily_fired(c, (int64_t)in[18]); qd_indiv_daily_fired(c, (int64_t)in[19]);
-    c->last_nsub = (int)in[20];
-    for (int k = 0; k < 10; ++k) c->last_diag[k] = in[21 + k];
+    c->cloud_eff_valid = in[QD_SS_CLOUD_EFF_VALID] != 0.0;      // QD_SS_HAS_ELEVATION is read only
+    E.hours = in[QD_SS_ECO_HOURS]; E.next_h = in[QD_SS_ECO_NEXT_H]; E.count = (int64_t)in[QD_SS_ECO_COUNT];
+    E.have_lai = in[QD_SS_HAVE_LAI] != 0.0; E.f_valid = in[QD_SS_F_VALID] != 0.0; E.alpha_valid = in[QD_SS_ALPHA_VALID] != 0.0;
+    E.alpha_dirty = in[QD_SS_ALPHA_DIRTY] != 0.0; E.banded_valid = in[QD_SS_BANDED_VALID] != 0.0;
+    E.water_valid = in[QD_SS_WATER_VALID] != 0.0;
+    E.lai_version = (int)in[QD_SS_LAI_VERSION]; E.snap_version = (int)in[QD_SS_SNAP_VERSION];
+    E.n_recompute = (int)in[QD_SS_N_RECOMPUTE];
+    E.period = in[QD_SS_INDIV_PERIOD]; E.accum = in[QD_SS_INDIV_ACCUM]; E.n_fired = (int64_t)in[QD_SS_INDIV_FIRED];
+    qd_phyto_daily_steps(c, (int64_t)in[QD_SS_PHYTO_DAILY_STEPS]); qd_eco_daily_fired(c, (int64_t)in[QD_SS_ECO_DAILY_FIRED]);
+    qd_indiv_daily_fired(c, (int64_t)in[QD_SS_INDIV_DAILY_FIRED]);
+    c->last_nsub = (int)in[QD_SS_LAST_NSUB];
+    std::copy(in + QD_SS_LAST_DIAG, in + QD_SS_LAST_DIAG + 10, c->last_diag);
     return 0;
 }

@@ -22,7 +22,7 @@
 #define QD_ROUTE_RED_BLOCKS 1024
 #define QD_ROUTE_WIDE_LEVELS 4    // at most this many levels go out as wide launches ...
 #define QD_ROUTE_WIDE_MIN 2048    // ... and beyond level 0 only while a level holds this many segments
-#define QD_ROUTE_LOG_W 8          // step, event_dt, ocean_kgps, closure, input, ocean_kg, residual, lake_delta
+// QD_ROUTE_LOG_W (include/qingdai_hip.h): step, event_dt, ocean_kgps, closure, input, ocean_kg, residual, lake_delta
 
 enum { QR_OCEAN = -1, QR_VOID = -2, QR_DEAD = -3, QR_NOTPROC = -4, QR_LAKE0 = -5 };
 

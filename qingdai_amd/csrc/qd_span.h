@@ -13,7 +13,7 @@
 #pragma once
 #include "qd_internal.h"
 
-#define QD_SPAN_LOG_CAP 4096        // records a lane holds between two drains (qingdai_amd/_lib.py: SPAN_LOG_CAP is the same number)
+// QD_SPAN_LOG_CAP, the records a lane holds between two drains, is the public header's (the host sizes its drain buffers by it)
 enum { QD_LANE_ROUTE = 0, QD_LANE_PHYTO_DAILY, QD_LANE_ECO_DAILY, QD_LANE_INDIV_DAILY, QD_LANE_BUDGET, QD_LANE_HISTORY, QD_N_LANES };
 
 struct QdSpanLane {

@@ -12,7 +12,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from dataclasses import dataclass, fields
+
+from ._lib import QdError, qd_params
 
 NAN = float("nan")
 PLANET_RADIUS = 6.371e6                 # constants.py:32
@@ -88,9 +89,16 @@ _INTS = [
 ]
 
 
-class qd_params(ctypes.Structure):
-    """ctypes mirror of `struct qd_params` (include/qingdai_hip.h) -- same order."""
-    _fields_ = [(n, ctypes.c_double) for n, _, _ in _DOUBLES] + [(n, ctypes.c_int32) for n, _, _ in _INTS]
+def _check_tables():
+    """The two tables name exactly the fields of `struct qd_params`, doubles and int32 switches as the header types them (the
+    struct's order is the header's, not the tables')."""
+    table = {**{n: ctypes.c_double for n, _, _ in _DOUBLES}, **{n: ctypes.c_int32 for n, _, _ in _INTS}}
+    if table != dict(qd_params._fields_) or len(table) != len(_DOUBLES) + len(_INTS):
+        odd = sorted(f"{n}: {t.__name__}" for n, t in set(table.items()) ^ set(qd_params._fields_))
+        raise QdError(f"params._DOUBLES / _INTS and struct qd_params (include/qingdai_hip.h) differ: {odd or 'a name is listed twice'}")
+
+
+_check_tables()
 
 
 def _env_float(name, default):

@@ -16,12 +16,13 @@ import ctypes
 
 import numpy as np
 
+from ._lib import C
 from .params import PLANET_OMEGA, PLANET_RADIUS
 from .topography import _kernel
 
 PLANET_AXIAL_TILT = 27.0                      # constants.py:35
-MAX_OCTAVES = 16                              # QD_TOPOGEN_MAX_OCTAVES
-MAX_CONTINENTS = 64                           # QD_TOPOGEN_MAX_CONTINENTS
+MAX_OCTAVES = C["QD_TOPOGEN_MAX_OCTAVES"]
+MAX_CONTINENTS = C["QD_TOPOGEN_MAX_CONTINENTS"]
 
 # generate_elevation_map's params (topography.py:101-109, 160-167, 183-186, 235-241); None: derived from the grid
 DEFAULTS = {"N_CONTINENTS": 3, "CONTINENT_SIGMA_DEG": 30.0, "CONTINENT_SHAPE_P": 2.0, "CONTINENT_AMP_RANGE": (0.8, 1.2),

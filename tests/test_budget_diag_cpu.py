@@ -156,9 +156,7 @@ def test_simulation_without_the_switch_creates_no_lane():
 
 def test_abi_surface():
     from qingdai_amd import _lib
-    h = open(os.path.join(HERE, "..", "include", "qingdai_hip.h")).read()
-    for n in ("qd_budget_diag_configure", "qd_budget_diag_schedule", "qd_budget_diag_log", "qd_budget_diag_reset"):
-        assert n in _lib.SYMBOLS and re.search(rf"\bint {n}\(", h), n
-    assert _lib.BUDGET_LOG_W == bd.LOG_W == int(re.search(r"#define QD_BUDGET_LOG_W (\d+)", h).group(1))
+    assert _lib.BUDGET_LOG_W == bd.LOG_W == _lib.C["QD_BUDGET_LOG_W"]           # the header's own value: tests/test_abi_cpu.py
+    assert (bd.LINE_ENERGY, bd.LINE_OCEAN, bd.LINE_OCEAN_ENERGY, bd.LINE_HUMIDITY, bd.LINE_WATER) == (1, 2, 4, 8, 16)
     assert max(bd.REC.values()) < bd.LOG_W and len(set(bd.REC.values())) == len(bd.REC)
     assert "budget" not in " ".join(_lib.STEP_BITS)          # no flag bit: a schedule turns the lane on

@@ -3,7 +3,6 @@ golden of the reference; two wrong neighbourhoods that the goldens must notice; 
 literal replay of the reference's loop; the writer's files; the environment switches; the ABI names."""
 import glob
 import os
-import re
 
 import numpy as np
 import pytest
@@ -212,12 +211,9 @@ def test_env_parsing():
 
 
 def test_abi_names():
-    h = open(os.path.join(HERE, "..", "include", "qingdai_hip.h")).read()
-    for n in ("qd_eco_diversity", "qd_eco_diversity_on", "qd_eco_diversity_download"):
-        assert n in _lib.SYMBOLS and re.search(rf"\bint {n}\(", h), n
-    ids = dict(re.findall(r"QD_F_(ECO_DIV_[A-Z]+) = (\d+)", h))
-    assert ids == {"ECO_DIV_LS": "110", "ECO_DIV_ALPHA": "111", "ECO_DIV_BC": "112", "ECO_DIV_SUMMARY": "113"}
-    assert all(_lib.F[k] == int(v) for k, v in ids.items())
+    # that the header declares the symbols and the ids are the compiler's: tests/test_abi_cpu.py
+    assert {k: v for k, v in _lib.F.items() if k.startswith("ECO_DIV_")} == {"ECO_DIV_LS": 110, "ECO_DIV_ALPHA": 111, "ECO_DIV_BC": 112,
+                                                                            "ECO_DIV_SUMMARY": 113}
     assert _lib.FIELDS[-1] == "KD490" and _lib.F["LAND_MASK"] == 100 and _lib.F["ICE_MASK"] == 101      # nothing renumbered
     from qingdai_amd.device import Device
     from qingdai_amd.ecology import PopulationCanopy

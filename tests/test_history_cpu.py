@@ -213,13 +213,9 @@ def test_six_entries_in_the_line(tmp_path):
 def test_abi_surface():
     from qingdai_amd import _lib
     from qingdai_amd.device import Device
-    h = open(os.path.join(HERE, "..", "include", "qingdai_hip.h")).read()
-    lib = _lib.load()
     for n in ("qd_history_configure", "qd_history_schedule", "qd_history_sample", "qd_history_read", "qd_history_reset"):
-        assert n in _lib.SYMBOLS and re.search(rf"\bint {n}\(", h), n
-        assert hasattr(lib, n) and getattr(lib, n).argtypes is not None, n
-        assert hasattr(Device, n[3:]), n
-    assert _lib.HISTORY_MAX_ENTRIES == int(re.search(r"#define QD_HISTORY_MAX_ENTRIES (\d+)", h).group(1)) == 32
+        assert hasattr(Device, n[3:]), n            # that the header declares and the library exports them: tests/test_abi_cpu.py
+    assert _lib.HISTORY_MAX_ENTRIES == 32
     assert "history" not in " ".join(_lib.STEP_BITS)        # no flag bit: a schedule turns the lane on
     src = open(os.path.join(HERE, "..", "qingdai_amd", "csrc", "qd_span.h")).read()
     assert "QD_LANE_HISTORY" in src

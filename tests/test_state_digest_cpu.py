@@ -91,19 +91,22 @@ def test_sensitive_to_every_bit_change_cpu():
 
 def test_names_and_header_ids_cpu():
     from qingdai_amd import _lib
-    h = open(os.path.join(ROOT, "include", "qingdai_hip.h")).read()
-    body = h[h.index("enum qd_state_ref {"):]
-    body = re.sub(r"/\*.*?\*/", "", body[:body.index("};")], flags=re.S)
-    ids = {n: int(v) for n, v in re.findall(r"QD_SR_([A-Z_]+)\s*=\s*(\d+)", body)}
-    assert ids == _lib.STATE_REFS
-    assert int(re.search(r"#define QD_STATE_DIGEST_MAX (\d+)", h).group(1)) == _lib.STATE_DIGEST_MAX
+    # the ids and constants themselves against the header as a compiler reads it: tests/test_abi_cpu.py
+    assert _lib.STATE_REFS == {"PHYTO_TRACER": 200, "ROUTE_BUFFER": 300, "ROUTE_FLOW": 301, "ROUTE_LAKES": 302, "ECO_LAI_STACK": 310,
+                               "INDIV_E_DAY": 320, "INDIV_STRESS": 321, "HISTORY_SUM": 400}
+    assert _lib.STATE_REF_COUNT == {"PHYTO_TRACER": 64, "HISTORY_SUM": _lib.HISTORY_MAX_ENTRIES}
     from qingdai_amd import checkpoint
-    assert int(re.search(r"#define QD_ABI_VERSION (\d+)", h).group(1)) == checkpoint.ABI_VERSION == _lib.load().qd_abi_version()
+    assert _lib.C["QD_ABI_VERSION"] == checkpoint.ABI_VERSION == _lib.load().qd_abi_version()
     assert checkpoint.abi_version(type("D", (), {"lib": _lib.load()})()) == checkpoint.ABI_VERSION
+    # the slots are enum qd_state_scalar of the header, and qd_digest.hip reads and writes them by those names only
+    assert (_lib.C["QD_SS_PHYTO_DAILY_STEPS"], _lib.C["QD_SS_ECO_DAILY_FIRED"], _lib.C["QD_SS_INDIV_DAILY_FIRED"], _lib.C["QD_SS_LAST_NSUB"]) == (17, 18, 19, 20)
     slots = open(os.path.join(ROOT, "qingdai_amd", "csrc", "qd_digest.hip")).read()
     assert "17 daily phytoplankton steps   18 daily vegetation firings   19 firings of the individuals' daily step   20 last_nsub" in slots
+    slots = slots[slots.index('extern "C" int qd_state_scalars_get'):]
+    assert not re.search(r"\b(in|out)\[\d+\]", slots) and slots.count("QD_SS_PHYTO_DAILY_STEPS") == 2
     assert (_lib.STATE_SCALAR_SLOT["phyto_daily_steps"], _lib.STATE_SCALAR_SLOT["eco_daily_fired"], _lib.STATE_SCALAR_SLOT["indiv_daily_fired"]) == (17, 18, 19)
-    assert int(re.search(r"#define QD_STATE_SCALARS_N (\d+)", h).group(1)) == _lib.STATE_SCALARS_N
+    assert (_lib.STATE_SCALAR_SLOT["cloud_eff_valid"], _lib.STATE_SCALAR_SLOT["has_elevation"], _lib.STATE_SCALAR_SLOT["last_nsub"]) == (0, 1, 20)
+    assert len(_lib.STATE_SCALAR_SLOT) == 22 and max(_lib.STATE_SCALAR_SLOT.values()) + 10 < _lib.STATE_SCALARS_N
     assert _lib.state_ref("U") == 0 and _lib.state_ref("ICE_MASK") == 101 and _lib.state_ref("ROUTE_LAKES") == 302
     assert _lib.state_ref("PHYTO_TRACER:3") == 203 and _lib.state_ref("HISTORY_SUM:31") == 431
     for bad in ("PHYTO_TRACER", "PHYTO_TRACER:64", "HISTORY_SUM:32", "ROUTE_FLOW:1", "NOPE", "ECO_DIV_LS"):
