@@ -2,7 +2,8 @@
 qingdai_amd/_lib.py -- ctypes binding of libqingdai_hip.so, read from include/qingdai_hip.h.
 
 The header is the one statement of the C ABI: its integer constants and enumerators (C), its structs (qd_X) and its
-prototypes (SYMBOLS, PROTOTYPES) are parsed from it here and written nowhere else.
+prototypes (SYMBOLS, PROTOTYPES, SIGNATURES) are parsed from it here and written nowhere else.  `call` is the one way into the
+library: it marshals every argument by the parameter the header declares and checks the return code.
 
 There is no CPU fallback: if the HIP library is missing or no GPU is visible the
 product raises.  (The oracle under oracle/ is test infrastructure and is never
@@ -14,6 +15,8 @@ import ctypes
 import os
 import re
 import types
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QD_LIB_PATH") or os.path.join(_HERE, "libqingdai_hip.so")     # QD_LIB_PATH: developer A/B builds
@@ -27,6 +30,10 @@ class QdError(RuntimeError):
 # ---- the header reader -------------------------------------------------------------------------------------------------------
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "long long": ctypes.c_longlong,
             "size_t": ctypes.c_size_t, "double": ctypes.c_double}
+NP_OF = {"int": np.intc, "int32_t": np.int32, "int64_t": np.int64, "long long": np.longlong, "size_t": np.uintp, "double": np.float64,
+         "uint8_t": np.uint8, "uint64_t": np.uint64}                                    # the NumPy twin of what an array parameter may be of
+_C_OF = {**_SCALARS, "uint8_t": ctypes.c_uint8, "uint64_t": ctypes.c_uint64}         # ... and the ctypes twin, and the pointer to it
+_PTR_OF = {k: ctypes.POINTER(t) for k, t in _C_OF.items()}
 _POINTEES = set(_SCALARS) | {"void", "char", "uint8_t", "uint64_t", "qd_handle"}      # what a pointer or array may be of
 _ITEM = re.compile(r"""\s*(?:
       \#[ \t]*define[ \t]+(?P<define>QD_\w+)[ \t]+(?P<value>\w+)[ \t]*$
@@ -67,28 +74,30 @@ def _value_type(base, by_value, where):
     return by_value[base]
 
 
-def _param_type(text, structs, where):
-    """The one rule of the binding: scalars by their ctypes twin, qd_handle a void pointer, qd_handle* / void** a pointer to
-    one, const char* a C string, const qd_X* a pointer to that struct; every other pointer and every array parameter a void
-    pointer, which takes data_as(...) pointers, byref, ctypes arrays, None and raw addresses alike."""
-    const, base, ptr, [(_, dims)] = _decl(text, structs, where)
-    if dims or ptr:
-        if (base, ptr) in (("qd_handle", "*"), ("void", "**")) and not dims:
-            return ctypes.POINTER(ctypes.c_void_p)
-        if const and ptr == "*" and not dims and (base == "char" or base in structs):
-            return ctypes.c_char_p if base == "char" else ctypes.POINTER(structs[base])
-        return ctypes.c_void_p
-    return _value_type(base, {**_SCALARS, "qd_handle": ctypes.c_void_p}, where)
+def _param(text, structs, where):
+    """One parameter (or return type) -> (its ctypes type, (name, kind, base type, is_const)).  The one rule of the binding:
+    scalars by their ctypes twin, qd_handle a void pointer, qd_handle* / void** a pointer to one, const char* a C string,
+    const qd_X* a pointer to that struct; every other pointer and every array parameter a void pointer.  The kinds, which
+    `call` marshals by: scalar, handle, handle_out, cstring, struct_ptr, array (of a type of NP_OF), void_ptr."""
+    const, base, ptr, [(name, dims)] = _decl(text, structs, where)
+    if not (dims or ptr):
+        return _value_type(base, {**_SCALARS, "qd_handle": ctypes.c_void_p}, where), (name, "handle" if base == "qd_handle" else "scalar", base, const)
+    if (base, ptr) in (("qd_handle", "*"), ("void", "**")) and not dims:
+        return ctypes.POINTER(ctypes.c_void_p), (name, "handle_out", base, const)
+    if const and ptr == "*" and not dims and (base == "char" or base in structs):
+        return (ctypes.c_char_p, (name, "cstring", base, const)) if base == "char" else (ctypes.POINTER(structs[base]), (name, "struct_ptr", base, const))
+    return ctypes.c_void_p, (name, "array" if base in NP_OF else "void_ptr", base, const)
 
 
 def parse_header(text):
     """The text of a C header in the style of include/qingdai_hip.h -> a namespace of
          constants   {name: int}: every `#define QD_* <integer or earlier constant>` and every enumerator, in header order
          structs     {name: ctypes.Structure subclass}: every `typedef struct qd_X { ... } qd_X;`
-         prototypes  {name: (restype, [argtypes])}: every function declared, by the rule of _param_type
+         prototypes  {name: (restype, [argtypes])}: every function declared, by the rule of _param
+         signatures  {name: [(parameter name, kind, base type, is_const)]}: what the header says of each parameter
     Anything else at the top level, an unknown type word or an unreadable declaration raises a QdError that names it."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    consts, structs, protos = {}, {}, {}
+    consts, structs, protos, sigs = {}, {}, {}, {}
     pos = 0
     while text[pos:].strip():
         m = _ITEM.match(text, pos)
@@ -122,15 +131,19 @@ def parse_header(text):
             ret = re.fullmatch(r"(.*?)(\w+)\s*", head, flags=re.S)
             if not ret or not ret.group(1).strip():
                 raise QdError(f"include/qingdai_hip.h: cannot parse the declaration '{where}'")
-            args = [] if params.strip() in ("", "void") else [_param_type(p, structs, where) for p in params.split(",")]
-            protos[ret.group(2)] = (_param_type(ret.group(1), structs, where), args)
-    return types.SimpleNamespace(constants=consts, structs=structs, prototypes=protos)
+            args = [] if params.strip() in ("", "void") else [_param(p, structs, where) for p in params.split(",")]
+            if not all(sig[0] for _, sig in args):
+                raise QdError(f"include/qingdai_hip.h: a parameter without a name in: {where}")
+            protos[ret.group(2)] = (_param(ret.group(1), structs, where)[0], [t for t, _ in args])
+            sigs[ret.group(2)] = [sig for _, sig in args]
+    return types.SimpleNamespace(constants=consts, structs=structs, prototypes=protos, signatures=sigs)
 
 
 with open(HEADER_PATH, encoding="utf-8") as _f:
     HEADER = parse_header(_f.read())
 C = HEADER.constants                  # every integer constant and enumerator of the header, by its C name
 PROTOTYPES = HEADER.prototypes
+SIGNATURES = HEADER.signatures        # {symbol: [(parameter name, kind, base type, is_const)]}: what `call` marshals by
 SYMBOLS = list(PROTOTYPES)            # every symbol include/qingdai_hip.h declares
 globals().update(HEADER.structs)      # qd_grid_desc, qd_params, qd_eco_params, ...: the header's structs, by their C names
 
@@ -191,6 +204,74 @@ STEP_BITS = tuple(sorted(_STEP, key=_STEP.get))
 
 def step_flags(**on):
     return sum(_STEP[k] for k, v in on.items() if v)
+
+
+# ---- the one call seam -----------------------------------------------------------------------------------------------------------
+class OUT:
+    """In the place of an output pointer: `call` allocates it and returns what the library stored.  OUT = one element, handed
+    back as a Python number; OUT(n) = n elements, handed back as an ndarray."""
+
+    def __init__(self, n):
+        self.n = int(n)
+
+
+def _refuse(symbol, name, why):
+    raise TypeError(f"{symbol}: {name}: {why}")
+
+
+def call(lib, symbol, args, *, last_error, error=QdError, what=None):
+    """Call `symbol` of `lib` with `args` marshalled by its declaration in the header, and check its return code.
+         scalar          a number or bool -> int / float
+         const char*     str or bytes -> bytes
+         const qd_X*     an instance of that struct -> a pointer to it (a ctypes array of them passes as it is)
+         const T*, T[N]  anything np.ascontiguousarray(x, dtype=NP_OF[T]) takes; the temporary lives until the call returns
+         T*, T[N]        OUT / OUT(n), a ctypes instance or array of T, or a C-contiguous writeable ndarray of exactly NP_OF[T];
+                         anything else is a TypeError before the library is entered
+         void*           an address, or a C-contiguous ndarray (writeable unless the parameter is const)
+         handles         as they are
+    None is NULL for every pointer.  A non-zero return raises error(f"{what or symbol} failed: " + last_error()).  -> the values
+    of the OUT arguments in parameter order: None, the one value, or a tuple."""
+    sig = SIGNATURES[symbol]
+    if len(args) != len(sig):
+        raise TypeError(f"{symbol} takes {len(sig)} arguments, {len(args)} were given")
+    passed, outs, keep = [], [], []                              # keep: the arrays passed by a bare address, alive until the return
+    for (name, kind, base, const), x in zip(sig, args):
+        if kind == "scalar":
+            x = float(x) if base == "double" else int(x)
+        elif x is None or kind in ("handle", "handle_out"):
+            pass
+        elif kind == "cstring":
+            x = x.encode() if isinstance(x, str) else x
+        elif kind == "struct_ptr":
+            if isinstance(x, ctypes.Structure):                  # a ctypes array of them passes as it is
+                if type(x).__name__ != base:
+                    _refuse(symbol, name, f"a {type(x).__name__} where a {base} is declared")
+                x = ctypes.pointer(x)
+        elif kind == "void_ptr":
+            if isinstance(x, np.ndarray):
+                if not x.flags.c_contiguous or not (const or x.flags.writeable):
+                    _refuse(symbol, name, "the array must be C-contiguous" + ("" if const else " and writeable"))
+                keep.append(x)
+                x = x.ctypes.data
+        elif const:
+            x = np.ascontiguousarray(x, dtype=NP_OF[base]).ctypes.data_as(_PTR_OF[base])      # the pointer holds the temporary
+        elif x is OUT or isinstance(x, OUT):
+            outs.append(((_C_OF[base] * (1 if x is OUT else x.n))(), x is OUT, base))
+            x = outs[-1][0]
+        elif isinstance(x, np.ndarray):
+            if x.dtype != NP_OF[base] or not x.flags.c_contiguous or not x.flags.writeable:
+                _refuse(symbol, name, f"an output must be a C-contiguous writeable {np.dtype(NP_OF[base]).name} array, not "
+                                      f"{x.dtype.name}{'' if x.flags.c_contiguous else ', strided'}{'' if x.flags.writeable else ', read-only'}")
+            x = x.ctypes.data_as(_PTR_OF[base])
+        elif isinstance(x, _C_OF[base]):
+            x = ctypes.pointer(x)
+        elif not (isinstance(x, ctypes.Array) and x._type_ is _C_OF[base]):
+            _refuse(symbol, name, f"an output must be OUT, an ndarray or a ctypes {base}, not a {type(x).__name__}")
+        passed.append(x)
+    if getattr(lib, symbol)(*passed) != 0:
+        raise error(f"{what or symbol} failed: " + (last_error() or b"?").decode())
+    got = [c[0] if one else np.frombuffer(c, dtype=NP_OF[base]) for c, one, base in outs]
+    return None if not got else got[0] if len(got) == 1 else tuple(got)
 
 
 _lib = None

@@ -18,6 +18,7 @@ import time
 import numpy as np
 
 from . import _lib
+from ._lib import OUT
 from .device import Device
 from .params import QdParams
 
@@ -113,20 +114,10 @@ class BandGroup:
                 raise e
 
     def exchanges(self):
-        out = []
-        for d in self.devs:
-            n = ctypes.c_int(0)
-            d.lib.qd_comm_stats(d.h, ctypes.byref(n))
-            out.append(n.value)
-        return out
+        return [d.call("qd_comm_stats", OUT) for d in self.devs]
 
     def allreduces(self):
-        out = []
-        for d in self.devs:
-            n = ctypes.c_int(0)
-            d.lib.qd_comm_allreduce_count(d.h, ctypes.byref(n))
-            out.append(n.value)
-        return out
+        return [d.call("qd_comm_allreduce_count", OUT) for d in self.devs]
 
     def close(self):
         for d in self.devs:
@@ -270,7 +261,7 @@ def init_peer(dev: Device, rank, world, tag="peer", timeout_s=180.0):
         if not good:
             lib.qd_peer_disable(dev.h)
     if good:
-        dev._chk(lib.qd_comm_barrier(dev.h), "qd_comm_barrier")
+        dev.call("qd_comm_barrier")
     _write_atomic(f"{base}.done.{rank}", b"\1")
     if rank == 0:
         gather("done", 1)
@@ -315,8 +306,7 @@ def init_rccl(dev: Device, rank, world, tag="id", timeout_s=180.0):
         return bytes(buf)
 
     def open_ring():
-        if lib.qd_comm_init_shm(dev.h, ring_name) != 0:
-            raise _lib.QdError("qd_comm_init_shm failed: " + (lib.qd_last_error(dev.h) or b"?").decode())
+        dev.call("qd_comm_init_shm", ring_name)
 
     # rank 0 creates the ring segment (unlinking a stale one) BEFORE the id is published; the others open it after reading the id
     uid = exchange_unique_id(rank, world, make_id, key, before_publish=open_ring if ring else None, timeout_s=timeout_s)
@@ -324,7 +314,6 @@ def init_rccl(dev: Device, rank, world, tag="id", timeout_s=180.0):
     ctypes.memmove(buf, uid, min(128, len(uid)))
     if ring and rank != 0:
         open_ring()
-    if lib.qd_comm_init(dev.h, buf, 128) != 0:
-        raise _lib.QdError("qd_comm_init failed: " + (lib.qd_last_error(dev.h) or b"?").decode())
-    dev._chk(lib.qd_comm_barrier(dev.h), "qd_comm_barrier")
+    dev.call("qd_comm_init", ctypes.addressof(buf), 128)
+    dev.call("qd_comm_barrier")
     finish_rendezvous(rank, key)

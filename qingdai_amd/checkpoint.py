@@ -472,7 +472,6 @@ def load(sim, path, env=None, out=print):
         raise CheckpointRefused("the ecology variables of the file do not fit this run (species, layers or individuals differ)")
     # 2. the planes.  LAND_MASK is the run's own (checked above); an elevation map only where the run has one (an upload marks it present)
     dev._host.clear()
-    dev._dirty.clear()
     for name in FIELDS:
         if name == "ELEVATION" and sim.elevation is None:
             continue

@@ -40,10 +40,8 @@ import numpy as np
 
 from . import ncio
 from . import spectral as sp
-from ._lib import QdError, qd_eco_params, qd_eco_daily_params, qd_indiv_daily_params
-
-_dp = ctypes.POINTER(ctypes.c_double)
-_ip = ctypes.POINTER(ctypes.c_int32)
+from ._lib import OUT, QdError, qd_eco_params, qd_eco_daily_params, qd_indiv_daily_params
+from .device import Device     # Device.call(dev, symbol, ...): the classes here take whatever has a handle `h` on a library `lib` for a device
 
 
 def _envf(name, default):
@@ -147,8 +145,7 @@ class PopulationCanopy:
         a = np.ascontiguousarray(self.LAI_layers_SK, dtype=np.float64)
         if a.shape[-2:] != self.shape:
             raise ValueError(f"LAI layers: expected [..., {self.shape[0]}, {self.shape[1]}], got {a.shape}")
-        n = int(np.prod(a.shape[:-2]))
-        self._dev._chk(self._dev.lib.qd_eco_set_lai_layers(self._dev.h, a.ctypes.data, n, 1 if init else 0), "qd_eco_set_lai_layers")
+        Device.call(self._dev, "qd_eco_set_lai_layers", a, np.prod(a.shape[:-2]), bool(init))
         if self.daily is not None:
             self._dev.eco_daily_set_layers(a.reshape((-1,) + self.shape))
 
@@ -255,8 +252,7 @@ class PopulationCanopy:
         return d.eco_diversity_get("ECO_DIV_ALPHA"), d.eco_diversity_get("ECO_DIV_BC"), d.eco_diversity_get("ECO_DIV_LS"), summary
 
     def state(self):
-        out = (ctypes.c_double * 5)()
-        self._dev._chk(self._dev.lib.qd_eco_get_state(self._dev.h, out), "qd_eco_get_state")
+        out = Device.call(self._dev, "qd_eco_get_state", OUT(5)).tolist()
         return {"hours": out[0], "next_recompute_hours": out[1], "step_count": int(out[2]), "n_recompute": int(out[3]),
                 "alpha_cached": bool(out[4])}
 
@@ -1170,14 +1166,13 @@ class EcologyAdapter:
             d.eco_daily_set_layers(stack.reshape((-1,) + pop.shape))
             pop.LAI_layers_SK = stack
             pop.daily.accum_day = float(v["qd_accum_day"])
-            d._chk(d.lib.qd_eco_set_lai_layers(d.h, stack.ctypes.data, int(stack.shape[0] * stack.shape[1]), 0), "qd_eco_set_lai_layers")
+            Device.call(d, "qd_eco_set_lai_layers", stack, stack.shape[0] * stack.shape[1], 0)
             d._host.pop("ECO_LAI", None)
         else:
             pop.push_layers(stack)
         for name, fid in EXT_PLANES:
             d.upload_now(fid, np.asarray(v[name], dtype=np.float64))
-        clock = (ctypes.c_double * 3)(*[float(x) for x in np.ravel(v["qd_eco_clock"])])
-        d._chk(d.lib.qd_eco_set_state(d.h, clock), "qd_eco_set_state")
+        Device.call(d, "qd_eco_set_state", np.ravel(v["qd_eco_clock"]))
         if with_indiv:
             indiv.reset(np.asarray(v["qd_indiv_E_day"], dtype=np.float64), np.asarray(v["qd_indiv_stress_days"], dtype=np.float64))
         return True
@@ -1263,8 +1258,7 @@ class EcologyAdapter:
             return False
 
     def configure(self):
-        self._dev._chk(self._dev.lib.qd_eco_configure(self._dev.h, ctypes.byref(self.params), ctypes.sizeof(self.params)),
-                       "qd_eco_configure")
+        Device.call(self._dev, "qd_eco_configure", self.params, ctypes.sizeof(self.params))
 
     def step_subdaily(self, I_total=None, cloud_eff=None, dt_seconds=300.0):
         """adapter.py:140-186.  With I_total=None the resident ISR is used (the usual case); returns the land-only alpha map
@@ -1273,9 +1267,8 @@ class EcologyAdapter:
         if I_total is not None:
             d.set("ISR", I_total)
         d.flush()
-        d._chk(d.lib.qd_eco_substep(d.h, float(dt_seconds)), "qd_eco_substep")
-        out = (ctypes.c_double * 5)()
-        d._chk(d.lib.qd_eco_get_state(d.h, out), "qd_eco_get_state")
+        Device.call(d, "qd_eco_substep", dt_seconds)
+        out = Device.call(d, "qd_eco_get_state", OUT(5))
         if int(out[2]) % max(1, self.cfg.substep_every_nphys) != 0:
             return None
         d._host.pop("ECO_ALPHA", None)
@@ -1286,10 +1279,9 @@ class EcologyAdapter:
         ECO_ALPHA_BANDED: clip(nansum_b A_b w_b, 0, 1).  Returns the host copy."""
         d = self._dev
         nb = int(self.bands.nbands)
-        r = np.ascontiguousarray(self.pop.effective_leaf_reflectance_bands(nb), dtype=np.float64)
-        w = np.ascontiguousarray(self.w_b, dtype=np.float64)
+        r = self.pop.effective_leaf_reflectance_bands(nb)
         d.flush()
-        d._chk(d.lib.qd_eco_banded_alpha(d.h, nb, r.ctypes.data_as(_dp), w.ctypes.data_as(_dp)), "qd_eco_banded_alpha")
+        Device.call(d, "qd_eco_banded_alpha", nb, r, self.w_b)
         d._host.pop("ECO_ALPHA_BANDED", None)
         return d.get("ECO_ALPHA_BANDED").copy()
 
@@ -1386,14 +1378,9 @@ class IndividualPool:
 
     def configure(self, **star_kw):
         d = self._dev
-        specA, specB, tray = (np.ascontiguousarray(a, dtype=np.float64) for a in sp.star_band_weights(self.bands, **star_kw))
-        sj, si, ci = (np.ascontiguousarray(a, dtype=np.int32) for a in (self.sample_j, self.sample_i, self.indiv_cell_index))
-        Ab = np.ascontiguousarray(self.indiv_Ab, dtype=np.float64)
-        tol = np.ascontiguousarray(self.indiv_tol, dtype=np.float64)
-        d._chk(d.lib.qd_indiv_configure(d.h, self.n_cells, sj.ctypes.data_as(_ip), si.ctypes.data_as(_ip), self.n_indiv,
-                                        ci.ctypes.data_as(_ip), Ab.ctypes.data, tol.ctypes.data, self.nb, specA.ctypes.data_as(_dp),
-                                        specB.ctypes.data_as(_dp), tray.ctypes.data_as(_dp), self.substeps_per_day,
-                                        self.day_seconds, self.soil_cap, 1 if self.f32_storage else 0), "qd_indiv_configure")
+        specA, specB, tray = sp.star_band_weights(self.bands, **star_kw)
+        Device.call(d, "qd_indiv_configure", self.n_cells, self.sample_j, self.sample_i, self.n_indiv, self.indiv_cell_index, self.indiv_Ab,
+                    self.indiv_tol, self.nb, specA, specB, tray, self.substeps_per_day, self.day_seconds, self.soil_cap, self.f32_storage)
         if self.daily is not None:                                                      # the device dropped it with the old pool
             self.daily.configure()
 
@@ -1429,13 +1416,11 @@ class IndividualPool:
         if soil_W_land is not None:
             d.set("W_LAND", np.asarray(soil_W_land, dtype=np.float64) * max(1e-6, self.soil_cap))
         d.flush()
-        fired = ctypes.c_int32(0)
-        d._chk(d.lib.qd_indiv_substep(d.h, float(dt_seconds), ctypes.byref(fired)), "qd_indiv_substep")
-        return bool(fired.value)
+        return bool(Device.call(d, "qd_indiv_substep", dt_seconds, OUT))
 
     def _pull(self):
         E, S = np.empty(self.n_indiv), np.empty(self.n_indiv)
-        self._dev._chk(self._dev.lib.qd_indiv_download(self._dev.h, E.ctypes.data, S.ctypes.data), "qd_indiv_download")
+        Device.call(self._dev, "qd_indiv_download", E, S)
         return E, S
 
     @property
@@ -1448,6 +1433,6 @@ class IndividualPool:
 
     def reset(self, E_day=None, stress_days=None):
         """What the daily step does to the buffers (individuals.py:207-208 and the end of step_daily)."""
-        E = np.zeros(self.n_indiv) if E_day is None else np.ascontiguousarray(E_day, dtype=np.float64)
-        S = np.zeros(self.n_indiv) if stress_days is None else np.ascontiguousarray(stress_days, dtype=np.float64)
-        self._dev._chk(self._dev.lib.qd_indiv_upload(self._dev.h, E.ctypes.data, S.ctypes.data), "qd_indiv_upload")
+        E = np.zeros(self.n_indiv) if E_day is None else E_day
+        S = np.zeros(self.n_indiv) if stress_days is None else stress_days
+        Device.call(self._dev, "qd_indiv_upload", E, S)

@@ -11,10 +11,9 @@ are computed here (`host_tables`), exactly as the reference writes them; the res
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
+from ._lib import OUT
 from .params import PLANET_RADIUS
 
 NETWORK_KEYS = ("land_mask", "elevation_filled", "flow_to_index", "flow_order", "lake_mask", "lake_id", "lake_outlet_index")
@@ -70,21 +69,11 @@ def generate_network(grid, land_mask, elevation=None, eps=1e-3, max_iters=200, d
     lmask = np.zeros((n_lat, n_lon), dtype=np.uint8)
     lid = np.zeros((n_lat, n_lon), dtype=np.int32)
     outlet = np.zeros(cells, dtype=np.int32)
-    n_land = ctypes.c_int32(0)
-    n_lakes = ctypes.c_int32(0)
-    P = lambda a, t: a.ctypes.data_as(ctypes.POINTER(t))
-    d, u8, i32 = ctypes.c_double, ctypes.c_uint8, ctypes.c_int32
-    rc = dev.lib.qd_hydronet_build(dev.h, n_lat, n_lon, P(land, u8), P(elev, d), float(eps), int(max_iters), P(lat, d), P(lon, d),
-                                   P(cos_pair, d), float(PLANET_RADIUS), P(ef, d), P(ft, i32), P(order, i32), P(lmask, u8), P(lid, i32),
-                                   P(outlet, i32), cells, ctypes.byref(n_land), ctypes.byref(n_lakes))
-    if rc != 0:
-        raise HydroNetError("qd_hydronet_build failed: " + (dev.lib.qd_last_error(dev.h) or b"?").decode())
-    sweeps = ctypes.c_int32(0)
-    dev._chk(dev.lib.qd_hydronet_sweeps(dev.h, ctypes.byref(sweeps)), "qd_hydronet_sweeps")
-    nl = int(n_lakes.value)
+    n_land, nl = dev.call("qd_hydronet_build", n_lat, n_lon, land, elev, eps, max_iters, lat, lon, cos_pair, PLANET_RADIUS, ef, ft, order,
+                          lmask, lid, outlet, cells, OUT, OUT, error=HydroNetError)
     return {"land_mask": land, "elevation_filled": ef, "flow_to_index": ft.astype(np.int64),
-            "flow_order": order[:int(n_land.value)].astype(np.int64), "lake_mask": lmask, "lake_id": lid,
-            "lake_outlet_index": outlet[:nl].copy(), "n_lakes": nl, "sweeps": int(sweeps.value)}
+            "flow_order": order[:n_land].astype(np.int64), "lake_mask": lmask, "lake_id": lid,
+            "lake_outlet_index": outlet[:nl].copy(), "n_lakes": nl, "sweeps": dev.call("qd_hydronet_sweeps", OUT)}
 
 
 def write_network(path, grid, net, auto=False):

@@ -10,7 +10,6 @@ The rest of the ecology (canopy, populations, individuals) is not on the device 
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from dataclasses import dataclass
 
@@ -85,12 +84,10 @@ def star_band_weights(bands, T_eff_A=None, T_eff_B=None, j_A=None, j_B=None):
 def dual_star_insolation_to_bands(dev, bands, download=True, **star_kw):
     """Band intensities [NB, n_lat, n_lon] from the device's resident ISR_A / ISR_B (set them with ThermalForcing.update_device
     or by assigning gcm.isr_A / gcm.isr_B).  Returns the host array, or None with download=False (result stays resident)."""
-    specA, specB, tray = (np.ascontiguousarray(a, dtype=np.float64) for a in star_band_weights(bands, **star_kw))
+    specA, specB, tray = star_band_weights(bands, **star_kw)
     dev.flush()
     out = np.empty((bands.nbands,) + dev.shape, dtype=np.float64) if download else None
-    dp = ctypes.POINTER(ctypes.c_double)
-    dev._chk(dev.lib.qd_band_insolation(dev.h, int(bands.nbands), specA.ctypes.data_as(dp), specB.ctypes.data_as(dp),
-                                        tray.ctypes.data_as(dp), out.ctypes.data if download else None), "qd_band_insolation")
+    dev.call("qd_band_insolation", bands.nbands, specA, specB, tray, out)
     return out
 
 

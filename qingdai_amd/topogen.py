@@ -12,11 +12,9 @@ QD_TOPO_NC loads; scripts/generate_topography.py is the CLI.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
-from ._lib import C
+from ._lib import C, OUT
 from .params import PLANET_OMEGA, PLANET_RADIUS
 from .topography import _kernel
 
@@ -129,10 +127,6 @@ def _half_kernel(sigma):
     return np.ascontiguousarray(w[:r + 1], dtype=np.float64), r
 
 
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
 class _Handle:
     """dev, the grid's own device, or a fresh one that is closed (and taken off the grid again) on exit"""
 
@@ -169,9 +163,7 @@ def smooth(field, sig_lat, sig_lon, dev=None, grid=None, lds_bytes=0):
         wa, ra = _half_kernel(sig_lat)
         wo, ro = _half_kernel(sig_lon)
         out = np.empty_like(f)
-        rc = d.lib.qd_topogen_smooth(d.h, f.shape[0], f.shape[1], _dp(f), _dp(wa), ra, _dp(wo), ro, int(lds_bytes), _dp(out))
-        if rc != 0:
-            raise TopoGenError("qd_topogen_smooth failed: " + (d.lib.qd_last_error(d.h) or b"?").decode())
+        d.call("qd_topogen_smooth", f.shape[0], f.shape[1], f, wa, ra, wo, ro, lds_bytes, out, error=TopoGenError)
     return out
 
 
@@ -243,19 +235,12 @@ def generate(grid, seed=42, params=None, target_land_frac=0.29, dev=None, draws=
     n_lat, n_lon = int(grid.n_lat), int(grid.n_lon)
     elev = np.empty((n_lat, n_lon), dtype=np.float64)
     mask = np.empty((n_lat, n_lon), dtype=np.uint8)
-    sea = ctypes.c_double(0.0)
     with _Handle(grid, dev, device) as h:
-        rc = h.lib.qd_topogen_build(h.h, n_lat, n_lon, _dp(a["par"]), len(a["oct_amp"]), _dp(a["oct_amp"]), _dp(a["noise"]),
-                                    len(a["cont"]), _dp(a["cont"]), _dp(a["cont_coslon"]), _dp(a["sin_lat"]), _dp(a["cos_lat"]),
-                                    _dp(a["area_w"]), a["radii"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(a["weights"]),
-                                    _dp(elev), mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(sea))
-        if rc != 0:
-            raise TopoGenError("qd_topogen_build failed: " + (h.lib.qd_last_error(h.h) or b"?").decode())
+        sea = h.call("qd_topogen_build", n_lat, n_lon, a["par"], len(a["oct_amp"]), a["oct_amp"], a["noise"], len(a["cont"]), a["cont"],
+                     a["cont_coslon"], a["sin_lat"], a["cos_lat"], a["area_w"], a["radii"], a["weights"], elev, mask, OUT, error=TopoGenError)
         if timing is not None:
-            ms = ctypes.c_double(0.0)
-            h._chk(h.lib.qd_topogen_last_ms(h.h, ctypes.byref(ms)), "qd_topogen_last_ms")
-            timing["kernels_ms"] = float(ms.value)
-    return {"elevation": elev, "land_mask": mask, "sea_level_m": float(sea.value), "land_frac": land_fraction(mask, grid),
+            timing["kernels_ms"] = h.call("qd_topogen_last_ms", OUT)
+    return {"elevation": elev, "land_mask": mask, "sea_level_m": sea, "land_frac": land_fraction(mask, grid),
             "cont_lats": a["cont_lats"], "cont_lons": a["cont_lons"], "cont_amps": a["cont_amps"]}
 
 

@@ -167,6 +167,19 @@ int qd_make(const qd_in* desc, qd_out* result, qd_handle* out, void** ring, qd_h
     p = ctypes.POINTER
     assert h.prototypes["qd_make"][1][1:] == [vp, p(vp), p(vp), p(vp), ctypes.c_char_p, vp]
     assert h.prototypes["qd_make"][1][0] is p(h.structs["qd_in"])             # const qd_X*: a pointer to the derived struct
+    # what the header says of each parameter: (name, kind, base type, is_const)
+    assert h.signatures["qd_version"] == [] and list(h.signatures) == list(h.prototypes)
+    assert h.signatures["qd_arrays"] == [("h", "handle", "qd_handle", False), ("star", "array", "double", True), ("out", "array", "double", False),
+                                         ("fire", "array", "int32_t", True), ("mask", "array", "uint8_t", True), ("digest", "array", "uint64_t", False)]
+    assert [s[1] for s in h.signatures["qd_make"]] == ["struct_ptr", "void_ptr", "handle_out", "handle_out", "handle_out", "cstring", "void_ptr"]
+    from qingdai_amd._lib import NP_OF, _C_OF, SIGNATURES as S                # one pinned entry per kind, from the real header
+    assert S["qd_step_n"] == [("h", "handle", "qd_handle", False), ("n", "scalar", "int", False), ("dt", "scalar", "double", False),
+                              ("flags", "scalar", "int", False), ("stars", "array", "double", True)]
+    assert S["qd_tiles_scan"][1] == ("refs", "struct_ptr", "qd_tile_ref", True) and S["qd_tiles_scan"][4] == ("argmax_cell", "array", "int64_t", False)
+    assert S["qd_eco_state_restore"][1] == ("lai", "void_ptr", "void", True)
+    assert S["qd_timing_select"][1] == ("name", "cstring", "char", True)
+    assert S["qd_create"][3] == ("out", "handle_out", "qd_handle", False) and S["qd_create"][2] == ("q_init_rh", "scalar", "double", False)
+    assert set(NP_OF) == set(_C_OF) and all(np.dtype(NP_OF[b]) == np.dtype(t) for b, t in _C_OF.items())
 
 
 @pytest.mark.parametrize("text, names", [
@@ -185,6 +198,7 @@ int qd_make(const qd_in* desc, qd_out* result, qd_handle* out, void** ring, qd_h
     ("#define QD_W (4)", ("QD_W",)),
     ("enum { QD_X = 1 << 3 };", ("QD_X",)),
     ("enum { QD_X = QD_LATER };\n#define QD_LATER 1", ("QD_LATER", "QD_X")),
+    ("int qd_f(qd_handle h, int);", ("name", "qd_f")),                          # a parameter without a name: the seam's errors name it
 ])
 def test_reader_is_strict(text, names):
     from qingdai_amd._lib import QdError, parse_header

@@ -30,7 +30,7 @@ class FakeDev:
     def __init__(self, seed=0, f32=False):
         rng = np.random.default_rng(seed)
         self.shape, self.params, self.f32 = SHAPE, QdParams(), f32
-        self._host, self._dirty = {}, set()
+        self._host = {}
         bits = lambda *s: rng.integers(0, 2**64, s, dtype=np.uint64).view(np.float64)
         self.planes = {n: bits(*SHAPE) for n in _lib.FIELDS}
         for n in ck.F32_MAPS:                                  # what a download of an f32 slab hands out: f8 images of f32 values

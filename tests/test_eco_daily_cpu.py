@@ -240,7 +240,7 @@ class StubLib:
 
 def _stub_device(fail=None):
     dev = object.__new__(Device)
-    dev.lib, dev.h, dev._host, dev._dirty = StubLib(fail), ctypes.c_void_p(1), {}, set()
+    dev.lib, dev.h, dev._host = StubLib(fail), ctypes.c_void_p(1), {}
     return dev
 
 

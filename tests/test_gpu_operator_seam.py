@@ -112,6 +112,28 @@ def test_point_stencils_vs_oracle(gpu, monkeypatch, shape):
     assert storm < STORM_TOL, storm
 
 
+# ---------------------------------------------------------------- what the call seam does to an input
+@pytest.mark.parametrize("shape", ((19, 36), (5, 130)))
+def test_inputs_of_any_layout_equal_their_contiguous_f64_copy(gpu, monkeypatch, shape):
+    """float32, Fortran-ordered and strided inputs: each operator's result is, bit for bit, the one for
+    np.ascontiguousarray(x, dtype=np.float64) -- the conversion every caller of the seam used to write out by hand."""
+    dev = handle(monkeypatch, shape)
+    fields = (oc.field(shape), *oc.winds(shape))
+    forms = {"float32": lambda x: x.astype(np.float32), "fortran": np.asfortranarray, "strided": lambda x: np.repeat(x, 2, axis=1)[:, ::2]}
+    for name, form in forms.items():
+        f, u, v = (form(x) for x in fields)
+        assert f.dtype != np.float64 or not f.flags.c_contiguous, name
+        cf, cu, cv = (np.ascontiguousarray(x, dtype=np.float64) for x in (f, u, v))
+        got = (dev.op_laplacian(f), dev.op_laplacian(f, ocean=True), dev.op_advect(f, u, v, DT), dev.op_advect(f, u, v, DT, ocean=True),
+               dev.op_divvort(u, v), dev.op_divvort(u, v, vort=True))
+        want = (dev.op_laplacian(cf), dev.op_laplacian(cf, ocean=True), dev.op_advect(cf, cu, cv, DT), dev.op_advect(cf, cu, cv, DT, ocean=True),
+                dev.op_divvort(cu, cv), dev.op_divvort(cu, cv, vort=True))
+        for k, (g, w) in enumerate(zip(got, want)):
+            assert np.all(np.isfinite(w)) and float(np.max(np.abs(w))) > 0.0, (name, k)
+            assert np.array_equal(g, w), (name, k)
+        assert f.dtype == form(fields[0]).dtype and np.array_equal(f, form(fields[0])), name      # the caller's array is left alone
+
+
 # ---------------------------------------------------------------- Shapiro
 @pytest.mark.parametrize("shape", oc.SHAPIRO_SHAPES)
 def test_shapiro_vs_oracle_and_pass_form(gpu, monkeypatch, shape):

@@ -140,7 +140,7 @@ def test_device_caps_are_checked_on_the_device_side_too(gpu):
     dev = Device(grid)
     a = topogen.build_inputs(grid, None, topogen.draw(grid, 42), 0.29)
     elev, mask, sea = np.empty((13, 24)), np.empty((13, 24), np.uint8), ctypes.c_double(0.0)
-    dp = topogen._dp
+    dp = lambda x: x.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
     def call(n_oct, n_cont):
         return dev.lib.qd_topogen_build(dev.h, 13, 24, dp(a["par"]), n_oct, dp(a["oct_amp"]), dp(a["noise"]), n_cont, dp(a["cont"]),

@@ -66,7 +66,7 @@ class StubForcing:
 
 def make_sim(t0, dt, day_phyto, day_eco, dt_hydro):
     dev = object.__new__(Device)
-    dev.lib, dev.h, dev._host, dev._dirty = StubLib(), ctypes.c_void_p(1), {}, set()
+    dev.lib, dev.h, dev._host = StubLib(), ctypes.c_void_p(1), {}
     sim = object.__new__(Simulation)
     sim.dev, sim.dt, sim._step_index, sim.forcing = dev, dt, 0, StubForcing()
     sim.t = t0

@@ -42,7 +42,7 @@ class StubLib:
 
 def make_device(fail=None):
     dev = object.__new__(Device)
-    dev.lib, dev.h, dev._host, dev._dirty = StubLib(fail), ctypes.c_void_p(1), {}, set()
+    dev.lib, dev.h, dev._host = StubLib(fail), ctypes.c_void_p(1), {}
     return dev
 
 
