@@ -732,6 +732,29 @@ int qd_history_reset(qd_handle h);                                       /* sums
 /* the inverse of qd_history_read, for an exact resume (QD_CHECKPOINT): an open window's sums and sample count put back */
 int qd_history_restore(qd_handle h, const double* sums, int64_t count);
 
+/* ---- per-step time series and zonal means (QD_SERIES), whole-globe handles ------------------------------------------------
+ * Nothing the reference has.  A span lane without a flag bit, like the history accumulators, and with a device log, like the budget
+ * diagnostics: a schedule given before a qd_step_n span turns it on for that span, and on every sampled step each entry (an entry
+ * is a history entry: op 0 = an f64 plane, 1 = sqrt(a*a + b*b)) is reduced on the device to
+ *     mean, min, max, nan_count [, zonal[n_lat]]
+ * with w_j = w_row[j] (the host's max(cos lat_j, 0)), S_j the sum of row j, zonal[j] = S_j / n_lon, mean = (sum_j w_j S_j) /
+ * (n_lon sum_j w_j), min / max over the non-NaN cells (NaN when there is none), nan_count exact; a NaN cell makes its row's zonal
+ * and the mean NaN.  The n entries' results in configure order are ONE record of n * (QD_SERIES_STATS + (zonal ? n_lat : 0))
+ * doubles; the log holds QD_SERIES_LOG_CAP records between two drains.  The summation order is fixed (csrc/qd_series.hip,
+ * qingdai_amd/series.py: reduce_reference): a record depends on the planes' values and the grid shape alone.  Entries that read
+ * PRECIP are reduced in front of the ocean step, the others behind the step's last launch, as in the history lane: at most two
+ * launches per sampled step, none on the others; a sampled step stores the lazily stored diagnostics when an entry reads one. */
+#define QD_SERIES_MAX_ENTRIES 32                         /* entries of one configuration */
+#define QD_SERIES_LOG_CAP 256                            /* records the series log holds between two drains */
+#define QD_SERIES_STATS 4                                /* mean, min, max, nan_count in front of an entry's zonal means */
+/* n entries as qd_history_configure takes them, zonal != 0: the records carry the zonal means, w_row[n_lat]: the row weights.
+ * Allocates the log; forgets an earlier configuration; n == 0 only releases.  Refused as in qd_history_configure. */
+int qd_series_configure(qd_handle h, int n, const int32_t* op, const int32_t* a, const int32_t* b, int zonal, const double* w_row); /* n == 0 releases */
+int qd_series_schedule(qd_handle h, int steps, const int32_t* sample);  /* the next qd_step_n span: non-zero = the step is sampled */
+int qd_series_sample(qd_handle h);                                   /* class seam: one record now, outside a span */
+int qd_series_log(qd_handle h, double* out, int max, int* n);        /* drain: *n records of width doubles, oldest first */
+int qd_series_reset(qd_handle h);                                    /* log and schedule forgotten */
+
 /* ---- state digest and exact resume (QD_CHECKPOINT), whole-globe handles ---------------------------------------------------
  * Nothing the reference has: its restart file holds 14 planes as f4 and a resumed run does not continue the run that was stopped.
  * qd_state_digest: a 64-bit digest of resident planes, all of them in ONE launch.  The digest of a plane of n elements is

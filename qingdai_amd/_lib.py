@@ -175,6 +175,9 @@ INDIV_DAILY_LOG_W = C["QD_INDIV_DAILY_LOG_W"]        # doubles per record of the
 BUDGET_LOG_W = C["QD_BUDGET_LOG_W"]                  # doubles per budget diagnostics record (budget_diag.REC names the slots)
 ROUTE_LOG_W = C["QD_ROUTE_LOG_W"]                    # doubles per routing event record (routing.LOG_KEYS)
 HISTORY_MAX_ENTRIES = C["QD_HISTORY_MAX_ENTRIES"]
+SERIES_MAX_ENTRIES = C["QD_SERIES_MAX_ENTRIES"]
+SERIES_LOG_CAP = C["QD_SERIES_LOG_CAP"]              # records the series lane's device log holds between two drains
+SERIES_STATS = C["QD_SERIES_STATS"]                  # mean, min, max, nan_count in front of an entry's zonal means
 STATE_DIGEST_MAX = C["QD_STATE_DIGEST_MAX"]          # refs per qd_state_digest call
 STATE_SCALARS_N = C["QD_STATE_SCALARS_N"]
 # enum qd_state_scalar: the slots of qd_state_scalars_get / set, by their lower-case names

@@ -10,6 +10,8 @@ The file (one NetCDF file through ncio.write_nc, f8 / u1 / i8 only; written to a
   phyto_C             the tracers [species, lat, lon]; PHYTO_N, KD490 and WATER_ALPHA are fields
   route_buffer, route_flow, route_lakes, route_clock {t_accum, steps, an event has happened}
   hist_sums, hist_clock {i, t_first, t_last, n_open, count}       an open history window continues
+  series_records, series_times, series_steps, series_clock {i, records}   an open series window continues (QD_SERIES=1 only; host
+                      data: the records were reduced on the device and enter no digest)
   qd_*                the ecology's own exact-resume variables (ecology.py: EcologyAdapter._extension_variables), not restated here
   atm_counter, ocn_counter, step_index, span_mark {step index, atm counter at the last span's end}, t_seconds, t_origin {t0, steps
   since, their dt}, diversity_next_day,
@@ -142,15 +144,18 @@ def _eco_f32(sim):
 
 
 def subsystems(sim):
-    """The subsystem set a file must share with the run that loads it, as one string per item."""
+    """The subsystem set a file must share with the run that loads it, as one string per item.  The series lane's key is there only
+    when the lane is on: a file without it says "off", as every file written before the lane existed does."""
     pop = sim.eco.pop if sim.eco is not None else None
-    return {"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
+    ser = getattr(sim, "series", None)
+    extra = {"series": f"{','.join(ser.names)}|zonal={int(ser.zonal)}|every={int(ser.every)}"} if ser is not None else {}
+    return {**{"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
             "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
             "phyto_daily": str(int(sim.phyto_daily is not None)),
             "ecology": str(int(sim.eco is not None)), "population": str(int(pop is not None)), "eco_f32": str(int(_eco_f32(sim))),
             "eco_daily": str(int(sim.eco_daily is not None)), "individuals": str(int(sim.indiv is not None)),
             "indiv_daily": str(int(sim.indiv_daily is not None)),
-            "history": ",".join(sim.history.names) if sim.history is not None else "-"}
+            "history": ",".join(sim.history.names) if sim.history is not None else "-"}, **extra}
 
 
 def plane_names(sim):
@@ -253,6 +258,16 @@ def collect(sim):
         dims["hist"] = int(sums.shape[0])
         v["hist_sums"] = ("f8", ("hist", "lat", "lon"), sums)
         v["hist_clock"] = ("f8", ("five",), np.array([float(h.i), _nan(h.t_first), _nan(h.t_last), float(h.n_open), float(count)]))
+    ser = getattr(sim, "series", None)
+    if ser is not None:
+        recs, times, steps = ser.window()                      # (a span boundary: every record of the log has been delivered)
+        n = int(len(recs))
+        pad = max(n, 1)                                        # classic NetCDF reads a dimension of size 0 as the unlimited one
+        dims["series_time"], dims["series_width"] = pad, int(ser.width)
+        v["series_records"] = ("f8", ("series_time", "series_width"), np.concatenate([recs, np.zeros((pad - n, ser.width))]))
+        v["series_times"] = ("f8", ("series_time",), np.concatenate([times, np.zeros(pad - n)]))
+        v["series_steps"] = ("f8", ("series_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
+        v["series_clock"] = ("f8", ("two",), np.array([float(ser.i), float(n)]))
     if sim.eco is not None and sim.eco.pop is not None:
         xd, xv = sim.eco._extension_variables(sim.indiv)
         dims["species"] = int(sim.eco.pop.Ns)
@@ -370,6 +385,9 @@ def check_grid_and_abi(f, shape, dev=None):
 def check_subsystems(f, sim):
     want, got = subsystems(sim), f.subsystems()
     onoff = lambda s: {"0": "off", "1": "on"}.get(s, f"'{s}'")
+    if got.get("series", "-") != want.get("series", "-"):
+        raise CheckpointRefused(f"the subsystem set differs: the series lane is '{got.get('series', '-')}' in the file and "
+                                f"'{want.get('series', '-')}' in this run")
     for k in want:
         if got.get(k) != want[k]:
             if k == "history":
@@ -489,6 +507,12 @@ def load(sim, path, env=None, out=print):
         h, clock = sim.history, np.asarray(v["hist_clock"], dtype=np.float64)
         dev.history_restore(np.asarray(v["hist_sums"], dtype=np.float64), int(clock[4]))
         h.i, h.t_first, h.t_last, h.n_open = int(clock[0]), _none(clock[1]), _none(clock[2]), int(clock[3])
+    if getattr(sim, "series", None) is not None:
+        clock = np.asarray(v["series_clock"], dtype=np.float64)
+        n = int(clock[1])
+        sim.series.restore_window(np.asarray(v["series_records"], dtype=np.float64)[:n], np.asarray(v["series_times"])[:n],
+                                  np.asarray(v["series_steps"])[:n], int(clock[0]))
+        dev.series_reset()
     # 3. counters, parameters, the host-side scalars (last: the uploads above set some of the flags they carry)
     dev.set_counters(int(f.scalar("atm_counter")), int(f.scalar("ocn_counter")))
     if autotune:

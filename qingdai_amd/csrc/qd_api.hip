@@ -482,6 +482,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_tiles_release(c);
     qd_budget_release(c);
     qd_history_release(c);
+    qd_series_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -710,6 +711,10 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     const bool with_hist = qd_history_scheduled(c);
     if (with_hist && !(span.lane[QD_LANE_HISTORY] = qd_history_span_begin(c, n))) return -1;
     const bool hist_lazy = with_hist && qd_history_reads_lazy(c);
+    // nor has the per-step series (qd_series.hip): a sampled step reduces its fields into one record, at most two launches
+    const bool with_series = qd_series_scheduled(c);
+    if (with_series && !(span.lane[QD_LANE_SERIES] = qd_series_span_begin(c, n))) return -1;
+    const bool series_lazy = with_series && qd_series_reads_lazy(c);
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -720,6 +725,8 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         const bool bd_water = bd_main && with_hydro && (bd_lines & QD_BD_LINE_WATER);
         if (bd_fire != 0.0 && (rc = qd_budget_begin_step(c))) return rc;
         const bool hist_fire = with_hist && span.lane[QD_LANE_HISTORY]->at(s) != 0.0;
+        const bool series_fire = with_series && span.lane[QD_LANE_SERIES]->at(s) != 0.0;
+        if (series_fire && (rc = qd_series_begin_step(c))) return rc;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
         if (with_pdaily && span.lane[QD_LANE_PHYTO_DAILY]->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
@@ -739,7 +746,8 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         const bool merged = with_phys && c->merge_pointwise;
         const QdForcingCall fc{st, st + 3, st[6]};
         // lazy diagnostics: inside a span only the last step stores what nothing inside a span reads -- unless a reader comes with the flags
-        c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag || bd_main || (hist_fire && hist_lazy)) ? 1 : 0;
+        c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag || bd_main || (hist_fire && hist_lazy) ||
+                         (series_fire && series_lazy)) ? 1 : 0;
         if (with_phys) {
             const int part = c->precip_done ? 2 : 0;         // the precipitation block may have run inside the previous ocean step
             c->precip_done = 0;
@@ -770,6 +778,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (with_ocean && want_diag && s == 0 && (rc = qd_energy_diag_impl(c, c->last_diag))) return rc;
         // history: PRECIP is this step's until the block below overwrites it with the next step's -- its entries are sampled here
         if (hist_fire && (rc = qd_history_accumulate(c, 0))) return rc;
+        if (series_fire && (rc = qd_series_reduce(c, 0))) return rc;
         // The precipitation block of step s + 1 (run_simulation.py:1740-1790) reads u, v and P_cond as time_step left them and
         // nothing the ocean step, the tracers, the individuals or the bucket touch, and writes only what the rest of step s + 1's
         // driver physics reads: it is queued inside the ocean step, between the stress kernel and the host's wait for the CFL maxima.
@@ -791,6 +800,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (bd_water && (rc = qd_budget_water(c, bd_fire, with_route ? 1 : 0))) return rc;      // run_simulation.py:2350-2394
         // history: every other entry as the step leaves it -- what a span that ended here would hand to qd_download
         if (hist_fire && (rc = qd_history_accumulate(c, 1))) return rc;
+        if (series_fire && (rc = qd_series_reduce(c, 1))) return rc;
     }
     c->diag_write = 1;
     return qd_launch_check(c, "qd_step_n");

@@ -18,15 +18,14 @@
 // is unrolled by four: the loads of four entries are in flight before the first add.  The grid is sized from the CU count.  No LDS,
 // no atomics.  Whole-globe handles only.
 #include "qd_span.h"
+#include "qd_entry.h"
 #include <algorithm>
 
-#define QD_HISTORY_MAX 32          // entries (include/qingdai_hip.h: QD_HISTORY_MAX_ENTRIES)
+#define QD_HISTORY_MAX QD_ENTRY_MAX    // entries (include/qingdai_hip.h: QD_HISTORY_MAX_ENTRIES)
 #define QD_HIST_UNROLL 4
 
 struct QdHistEntry { const double* a; const double* b; double* sum; };        // b == nullptr: op 0
 struct QdHistTab { QdHistEntry e[QD_HISTORY_MAX]; int n; };
-
-__device__ __forceinline__ double hist_value(double a, double b, bool pair) { return pair ? sqrt(a * a + b * b) : a; }
 
 __global__ void __launch_bounds__(QD_BLOCK)
 k_hist_accum(QdHistTab T, size_t npairs, size_t cells) {
@@ -64,11 +63,7 @@ k_hist_accum(QdHistTab T, size_t npairs, size_t cells) {
     }
 }
 
-struct QdHistory {
-    int n = 0;
-    int op[QD_HISTORY_MAX], a[QD_HISTORY_MAX], b[QD_HISTORY_MAX];
-    bool early[QD_HISTORY_MAX];       // the entry reads PRECIP: sampled in front of the ocean step
-    bool lazy = false;                // an entry reads one of the lazily stored diagnostics (QD_LAZY_DIAG)
+struct QdHistory : QdEntrySel {       // the entry table (qd_entry.h)
     double* sums = nullptr;           // [n][stride]
     size_t stride = 0;                // cells rounded up to even: every sum plane starts 16-byte aligned
     int64_t count = 0;                // samples in the sums
@@ -86,36 +81,17 @@ void qd_history_release(qd_ctx* c) {
     c->history = nullptr;
 }
 
-// the fields nothing inside a span reads and only a span's last step stores (qd_internal.h: lazy_diag)
-static bool hist_lazy_field(int f) {
-    static const int L[] = {QD_F_P_RAIN, QD_F_S_SNOW_NEXT, QD_F_MELT, QD_F_C_SNOW, QD_F_GLACIER, QD_F_ISR_A, QD_F_ISR_B, QD_F_EFLUX, QD_F_LHREL, QD_F_OLR};
-    return std::find(std::begin(L), std::end(L), f) != std::end(L);
-}
-static bool hist_plane(const qd_ctx* c, int f) { return f >= 0 && f < QD_F_COUNT_F64 && !qd_eco_is_f32(c, f); }
-
 extern "C" int qd_history_configure(qd_handle c, int n, const int32_t* op, const int32_t* a, const int32_t* b) {
     if (!c || n < 0 || (n && (!op || !a))) return -1;
     if (!qd_whole_globe(c))
         return qd_fail(c, "qd_history_configure: the history accumulators need a whole-globe handle (world == 1, n_rows == n_lat); "
                           "latitude bands are not supported");
-    if (n > QD_HISTORY_MAX) return qd_fail(c, "qd_history_configure: at most 32 entries");
     QdHistory t;
-    for (int k = 0; k < n; ++k) {
-        if (op[k] != 0 && op[k] != 1) return qd_fail(c, "qd_history_configure: unknown op (0 = field a, 1 = sqrt(a*a + b*b))");
-        if (!hist_plane(c, a[k])) return qd_fail(c, "qd_history_configure: field a is not an f64 plane");
-        if (op[k] == 1 && !b) return qd_fail(c, "qd_history_configure: op 1 needs a second field b");
-        if (op[k] == 1 && !hist_plane(c, b[k])) return qd_fail(c, "qd_history_configure: field b is not an f64 plane");
-        t.op[k] = op[k]; t.a[k] = a[k]; t.b[k] = op[k] == 1 ? b[k] : -1;
-        t.early[k] = a[k] == QD_F_PRECIP || t.b[k] == QD_F_PRECIP;
-        if (t.early[k] && op[k] == 1 && a[k] != b[k])
-            return qd_fail(c, "qd_history_configure: op 1 cannot pair PRECIP with another field (they are sampled at different places of a step)");
-        t.lazy = t.lazy || hist_lazy_field(a[k]) || (op[k] == 1 && hist_lazy_field(b[k]));
-    }
+    if (qd_entries_parse(c, "qd_history_configure", n, op, a, b, t)) return -1;
     hipSetDevice(c->desc.device);
     qd_history_release(c);
     if (n == 0) return 0;
     QdHistory* h = new QdHistory(t);
-    h->n = n;
     h->stride = (c->geo.cells() + 1) & ~(size_t)1;
     const size_t bytes = (size_t)n * h->stride * sizeof(double);
     const bool ok = hipMalloc(&h->sums, bytes) == hipSuccess && hipMemsetAsync(h->sums, 0, bytes, c->stream) == hipSuccess &&
@@ -132,13 +108,7 @@ extern "C" int qd_history_schedule(qd_handle c, int steps, const int32_t* sample
 bool qd_history_scheduled(const qd_ctx* c) { return c->history && !c->history->lane.sched.empty(); }
 bool qd_history_reads_lazy(const qd_ctx* c) { return c->history && c->history->lazy; }
 
-// the ecology may have turned a selected map into an f32 slab since the configure (qd_eco_params.map_f32)
-static bool hist_stale(const qd_ctx* c) {
-    const QdHistory* h = c->history;
-    for (int k = 0; h && k < h->n; ++k)
-        if (!hist_plane(c, h->a[k]) || (h->op[k] == 1 && !hist_plane(c, h->b[k]))) return true;
-    return false;
-}
+static bool hist_stale(const qd_ctx* c) { return c->history && c->history->stale(c); }
 
 QdSpanLane* qd_history_span_begin(qd_ctx* c, int n) {
     static const QdSpanTexts T = {

@@ -3,7 +3,8 @@
 // qd_phyto_daily.hip), the daily vegetation step (bit9, qd_eco_daily.hip); the individuals' daily step
 // (qd_indiv_daily.hip) fires with bit9 and keeps a log of its own; the budget diagnostics (qd_budget_diag.hip) have no flag bit:
 // a schedule given before the span turns them on; so it is with the history accumulators (qd_history.hip), which keep sum planes
-// instead of a log (width 0).
+// instead of a log (width 0), and with the per-step series (qd_series.hip), whose records are large and come every sampled step: its
+// lane holds QD_SERIES_LOG_CAP of them (cap), every other lane QD_SPAN_LOG_CAP.
 //   qd_X_schedule           qd_lane_schedule: one value per step of the NEXT span, 0 = the step does not fire
 //   qd_step_n, before work  qd_lane_span_begin: exactly n steps scheduled, and their firings fit into the log behind the cursor
 //   qd_step_n, step s       at(s) != 0: X runs (not when full()) and writes its record at next()
@@ -14,21 +15,22 @@
 #include "qd_internal.h"
 
 // QD_SPAN_LOG_CAP, the records a lane holds between two drains, is the public header's (the host sizes its drain buffers by it)
-enum { QD_LANE_ROUTE = 0, QD_LANE_PHYTO_DAILY, QD_LANE_ECO_DAILY, QD_LANE_INDIV_DAILY, QD_LANE_BUDGET, QD_LANE_HISTORY, QD_N_LANES };
+enum { QD_LANE_ROUTE = 0, QD_LANE_PHYTO_DAILY, QD_LANE_ECO_DAILY, QD_LANE_INDIV_DAILY, QD_LANE_BUDGET, QD_LANE_HISTORY, QD_LANE_SERIES, QD_N_LANES };
 
 struct QdSpanLane {
-    double* log = nullptr;          // device, [QD_SPAN_LOG_CAP][width]; the subsystem sets width, allocates and frees it
+    double* log = nullptr;          // device, [cap][width]; the subsystem sets width (and cap), allocates and frees it
     int width = 0, n = 0;           // doubles per record; records queued since the last drain (the cursor)
+    int cap = QD_SPAN_LOG_CAP;      // records the log holds between two drains
     bool counts = false;            // a schedule value is the step's number of firings (>= 0); else any non-zero value is one firing
     std::vector<double> sched;      // the next span's value per step
 
-    size_t log_doubles() const { return (size_t)QD_SPAN_LOG_CAP * width; }     // what the subsystem allocates
+    size_t log_doubles() const { return (size_t)cap * width; }     // what the subsystem allocates
     double at(int s) const { return s >= 0 && s < (int)sched.size() ? sched[s] : 0.0; }
     void clear_schedule() { sched.clear(); }
     void reset() { n = 0; sched.clear(); }
     bool scheduled(int steps) const { return (int)sched.size() == steps; }
-    bool fits() const { double ev = 0.0; for (double x : sched) ev += counts ? x : (x != 0.0 ? 1.0 : 0.0); return n + ev <= QD_SPAN_LOG_CAP; }
-    bool full() const { return n >= QD_SPAN_LOG_CAP; }
+    bool fits() const { double ev = 0.0; for (double x : sched) ev += counts ? x : (x != 0.0 ? 1.0 : 0.0); return n + ev <= cap; }
+    bool full() const { return n >= cap; }
     double* next() { return log + (size_t)(n++) * width; }                     // where the next record goes; the cursor moves on
 };
 

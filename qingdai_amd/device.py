@@ -24,6 +24,7 @@ def _c(a, dtype=np.float64):
 
 class Device:
     _history_n = 0            # entries of the last history_configure
+    _series_width = 0         # doubles per record of the last series_configure
     _tiles_n = 1              # tiles of the last tile configuration
     _div_shape = None         # [S, lat, lon] of the last eco_diversity call
 
@@ -130,7 +131,8 @@ class Device:
         self.call("qd_hydrology_commit", dt)
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
-               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None):
+               ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None,
+               series=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  The span lanes, each a participant on this handle whose records stay in its
         device log until the caller has it deliver them: `routing`, a RiverRouting -- bit7, after the hydrology commit (which it
@@ -139,7 +141,8 @@ class Device:
         ecology.PopulationDaily -- bit9 (needs `ecology`); its day accumulator names the firing steps.  `budget`, a
         budget_diag.BudgetDiag -- no flag bit: its schedule (run-local step index, the ocean's step count) turns the lane on for
         the span.  `history`, a history.History -- no flag bit either: its window clock names the sampled steps, whose fields are
-        added to the resident sums (history_read)."""
+        added to the resident sums (history_read).  `series`, a series.Series -- no flag bit: its window clock names the sampled
+        steps, each of which leaves one record of reduced fields in the lane's log (series_log)."""
         self.flush()
         st = _c(stars)
         assert st.ndim == 2 and st.shape[1] == 7
@@ -151,7 +154,7 @@ class Device:
         #   span_restore(clock)       nothing ran (an upload or qd_step_n raised): the clock back to what span_clock gave
         #   _fired(k)                 the span ran: k is what span_schedule returned
         #   span_deliver(dt)          drain the lane's device log and deliver it (print, keep); the caller's move, once per span
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history) if p is not None]
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series) if p is not None]
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -270,6 +273,35 @@ class Device:
 
     def history_reset(self):
         self.call("qd_history_reset")
+
+    # ---- per-step series (qd_series.hip)
+    def series_configure(self, entries, zonal, w_row):
+        """entries: [(op, a, b)] as history_configure takes them; zonal: the records carry every row's zonal mean; w_row [n_lat]:
+        the row weights of the mean, max(cos lat, 0).  An empty list releases the lane."""
+        if len(entries) and (w_row is None or np.size(w_row) != self.shape[0]):
+            raise ValueError("series_configure: w_row holds one weight per latitude row")
+        self.call("qd_series_configure", len(entries), [e[0] for e in entries], [F[e[1]] for e in entries],
+                  [F[e[2]] if e[2] is not None else -1 for e in entries], int(bool(zonal)), None if w_row is None else _c(w_row).reshape(-1))
+        self._series_width = len(entries) * (_lib.SERIES_STATS + (self.shape[0] if zonal else 0))
+
+    def series_schedule(self, sample):
+        self.call("qd_series_schedule", np.size(sample), sample)
+
+    def series_sample(self):
+        """One record of every entry from the fields as they stand (the class seam)."""
+        self.flush()
+        self.call("qd_series_sample")
+
+    def series_log(self, max_records=None):
+        """Drain the records -> [n][width], oldest first; width = entries * (SERIES_STATS + (n_lat if zonal else 0)), per entry
+        mean, min, max, nan_count and then the zonal means.  max_records: what the caller knows to be queued at most."""
+        room = _lib.SERIES_LOG_CAP if max_records is None else max(0, min(int(max_records), _lib.SERIES_LOG_CAP))
+        w = max(1, self._series_width)
+        buf = np.empty(max(1, room) * w, dtype=np.float64)      # a record is large: no zero-filled ctypes buffer here
+        return self._records((buf, self.call("qd_series_log", buf, room, OUT)), w)
+
+    def series_reset(self):
+        self.call("qd_series_reset")
 
     # ---- daily phytoplankton step (qd_phyto_daily.hip)
     def phyto_daily_configure(self, params, band_tab, species_tab, shape):

@@ -91,6 +91,15 @@ fifth span lane (qingdai_amd/history.py, qd_history_*).  A chunk ends with a win
 complete) is written and one [History] line printed; a and b are the start times over `day` of the first and last sampled step,
 `05.1f` like the frames (more decimals for windows shorter than 0.1 day).  The normal end of main writes the open window with
 complete = 0; the signal path does not.
+Per-step series (QD_SERIES=1, default 0; nothing the reference has): on every QD_SERIES_EVERY-th (default 1; the phase restarts with
+each window) step of a window of QD_SERIES_EVERY_DAYS (default 10) planet-days -- history's window clock -- every field of
+QD_SERIES_FIELDS (history's parser, defaults, ocean-only rule and refusals) is reduced on the device to a cos-latitude-weighted
+global mean, a minimum, a maximum, a NaN count and, under QD_SERIES_ZONAL=1 (default), the zonal mean of every latitude row, in a
+fixed summation order, by a sixth span lane (qingdai_amd/series.py, qd_series_*) whose records stay in a device log until the chunk
+ends.  A chunk ends with a window's last step, behind which <QD_OUTPUT_DIR>/series/series_day_{a}_{b}.nc (time_seconds, step, lat,
+per field {name}_mean / _min / _max / _nan [time] and {name}_zonal [time][lat], dt_seconds, sample_every, zonal, complete) is
+written and one [Series] line printed, labelled like the history files.  The normal end of main writes the open window with
+complete = 0; the signal path does not; under QD_CHECKPOINT=1 the checkpoint carries the open window instead.
 Exact resume (QD_CHECKPOINT=1, default 0; nothing the reference has: its restart holds 14 planes as f4 and t_seconds, and the step
 counters, routing buffers, tracers, carry-over planes, autotuned parameters and history window start again): every autosave --
 periodic, signal, atexit, final -- also writes <QD_DATA_DIR>/checkpoint.nc (QD_CHECKPOINT_PATH names another file) behind the
@@ -232,6 +241,7 @@ class Simulation:
     diversity_on, diversity_every, diversity_next_day = False, 10.0, 0.0
     phyto = phyto_daily = None
     routing = budget = history = None      # enable_routing, enable_budget_diag (QD_BUDGET_DIAG=1), enable_history (QD_HISTORY=1)
+    series = None                          # enable_series (QD_SERIES=1)
     truecolor = stateframe = figures = None
     plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
     _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
@@ -820,19 +830,28 @@ class Simulation:
 
     def _run_cut(self, n, energy_diag=False):
         """n steps through _run_lanes; under QD_HISTORY=1 cut so that a chunk ends with a window's last step, behind which the
-        window's file is written (the sums then start the next window from zero)."""
-        hist = self.history
+        window's file is written (the sums then start the next window from zero); under QD_SERIES=1 likewise with its windows."""
+        hist, ser = self.history, self.series
         while n > 0:
             k = n if hist is None else min(n, hist.steps_to_window_end())
+            if ser is not None:
+                k = min(k, ser.steps_to_window_end())
             self._run_lanes(k, energy_diag)
             n -= k
             if hist is not None and hist.window_closed():
                 self.flush_history()
+            if ser is not None and ser.window_closed():
+                self.flush_series()
 
     def flush_history(self, complete=1):
         """Write the history window that stands in the accumulators -> the path or None.  A failure is reported and the window is
         dropped (the next one starts from zero): output never stops the run."""
         return self._nonfatal(lambda: self.history.flush(complete=complete), "[History] window skipped: {}", cleanup=self.history.drop)
+
+    def flush_series(self, complete=1):
+        """Write the series window that stands on the host -> the path or None.  A failure is reported and the window is dropped:
+        output never stops the run."""
+        return self._nonfatal(lambda: self.series.flush(complete=complete), "[Series] window skipped: {}", cleanup=self.series.drop)
 
     def _run_lanes(self, n, energy_diag=False):
         """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
@@ -844,7 +863,7 @@ class Simulation:
         if self.budget is not None:
             self.budget.routed = self.routing is not None
         lanes = {k: p for k, p in (("phyto_daily", self.phyto_daily), ("routing", self.routing), ("budget", self.budget),
-                                   ("eco_daily", eco_daily), ("history", self.history)) if p is not None}
+                                   ("eco_daily", eco_daily), ("history", self.history), ("series", self.series)) if p is not None}
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
         # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
@@ -900,6 +919,15 @@ class Simulation:
         self.history = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
                                 dt=float(self.dt), day=self.day_seconds)
         return self.history
+
+    def enable_series(self, env=None):
+        """QD_SERIES=1: per-step global means, extrema, NaN counts and zonal means of the selected fields, reduced by a device lane
+        and written per window to <QD_OUTPUT_DIR>/series/ (qingdai_amd/series.py) -> the Series or None.  The run-local step index
+        the windows count on starts where this is called.  An unknown field name raises here, before the loop."""
+        from .series import from_env
+        self.series = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
+                               dt=float(self.dt), day=self.day_seconds)
+        return self.series
 
     def enable_routing(self, env=None):
         """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
@@ -1164,6 +1192,8 @@ def main(argv=None):
     sim.enable_routing(env)
     sim.enable_budget_diag(env)
     sim.enable_history(env)
+    if getattr(sim, "enable_series", None) is not None:        # (a stand-in Simulation from before the series lane has none)
+        sim.enable_series(env)
     if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
         try:
             sim.load_checkpoint(ck_file, env)
@@ -1247,6 +1277,8 @@ def main(argv=None):
         # the open window, marked incomplete (the signal path does not get here); under QD_CHECKPOINT=1 the final checkpoint carries
         # it instead, and the run that resumes writes it when it is complete
         sim.flush_history(complete=0)
+    if getattr(sim, "series", None) is not None and not (ck["enabled"] and autosave_on):
+        sim.flush_series(complete=0)                           # likewise the open series window
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")

@@ -30,14 +30,15 @@ OCEAN_ONLY = frozenset(DEFAULT_OCEAN_FIELDS)
 EVERY_DAYS, SAMPLE_EVERY = 10.0, 1
 
 
-def parse_fields(text):
-    """QD_HISTORY_FIELDS -> upper-cased names, in order; an unknown name, or more than 32, raises a ValueError that names it."""
+def parse_fields(text, var="QD_HISTORY_FIELDS"):
+    """QD_HISTORY_FIELDS (or the variable `var` names: the series lane reads its own list with this parser) -> upper-cased names,
+    in order; an unknown name, or more than 32, raises a ValueError that names it."""
     names = [s.strip().upper() for s in str(text).split(",") if s.strip()]
     for n in names:
         if n not in FIELDS and n not in DERIVED:
-            raise ValueError(f"QD_HISTORY_FIELDS: unknown field '{n}' (an f64 plane as Device.get takes it, WIND_SPEED or CURRENT_SPEED)")
+            raise ValueError(f"{var}: unknown field '{n}' (an f64 plane as Device.get takes it, WIND_SPEED or CURRENT_SPEED)")
     if len(names) > HISTORY_MAX_ENTRIES:
-        raise ValueError(f"QD_HISTORY_FIELDS: {len(names)} entries, at most {HISTORY_MAX_ENTRIES}")
+        raise ValueError(f"{var}: {len(names)} entries, at most {HISTORY_MAX_ENTRIES}")
     return names
 
 
@@ -65,14 +66,14 @@ def read_env(env):
     return {"enabled": enabled, "every_days": days, "sample_every": k, "fields": fields}
 
 
-def resolve_fields(fields, with_ocean):
+def resolve_fields(fields, with_ocean, var="QD_HISTORY_FIELDS"):
     """The run's entry names: the default list (ocean fields only with the ocean) or the named ones, among which a field of a
     subsystem that is off is refused."""
     if fields is None:
         return list(DEFAULT_FIELDS) + (list(DEFAULT_OCEAN_FIELDS) if with_ocean else [])
     for n in fields:
         if n in OCEAN_ONLY and not with_ocean:
-            raise ValueError(f"QD_HISTORY_FIELDS: field '{n}' needs the ocean, which is off in this run (QD_USE_OCEAN)")
+            raise ValueError(f"{var}: field '{n}' needs the ocean, which is off in this run (QD_USE_OCEAN)")
     return list(fields)
 
 
