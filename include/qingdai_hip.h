@@ -204,6 +204,50 @@ int qd_median_state(qd_handle h, double* out64);
 int qd_step_scalars(qd_handle h, double* out8);
 /* (new, diagnostics) ocean sub-steps since create whose eta mean was left to the next momentum launch (QD_MEAN_IN_MOMENTUM) */
 int qd_ocean_mean_next_count(qd_handle h, int64_t* out);
+/* (new, diagnostics) which form of the step kernels this handle takes: out[QD_SF_N].  The timing groups k_dyn_hyper / k_ocn_hyper are
+ * shared by the row-streaming and the LDS-tile launchers and ocean_tail by three kernels; this says which.  Read-only, no launch, no
+ * wait.  The geometry entries are what the launchers' own shape functions return for the handle's rows (margin 0); the QD_SF_LAST_*
+ * entries are what the last atmosphere / ocean step noted where it decided (0 before the first step). */
+enum qd_step_form {
+    QD_SF_DYN_STREAM,       /* momentum + del^4 of the atmosphere: 1 = k_dyn_stream, 0 = k_dyn_hyper<TR> (LDS tiles) */
+    QD_SF_OCN_STREAM,       /* the same of the ocean sub-step: 1 = k_ocn_stream, 0 = k_ocn_hyper<TR> */
+    QD_SF_DYN_NTC,          /* streaming form, atmosphere: column strips (58 owned columns each), */
+    QD_SF_DYN_NRS,          /*   row strips, */
+    QD_SF_DYN_R,            /*   rows of a strip, */
+    QD_SF_DYN_VB,           /*   virtual rows that trim the north-pole strip */
+    QD_SF_OCN_NTC,          /* streaming form, ocean: the same four */
+    QD_SF_OCN_NRS,
+    QD_SF_OCN_R,
+    QD_SF_OCN_VB,
+    QD_SF_TILE_TR,          /* tile form: owned rows of a tile, */
+    QD_SF_TILE_NTR,         /*   row tiles, */
+    QD_SF_TILE_NTC,         /*   column tiles (58 owned columns each), */
+    QD_SF_TILE_DYN_FAST,    /*   row tiles of k_dyn_hyper whose workgroups take the FAST path (0: every tile EXACT), */
+    QD_SF_TILE_OCN_FAST,    /*   the same of k_ocn_hyper */
+    QD_SF_TAIL_KERNEL,      /* one-launch ocean tail this handle's launcher picks: 0 refuses (two launches), 1 k_ocn_tail_fast, 2 k_ocn_tail_stream */
+    QD_SF_TAIL_NTC,         /*   column groups (60 owned columns each; k_ocn_tail_stream: 62), */
+    QD_SF_TAIL_POLE,        /*   pole strips (k_ocn_tail_fast), */
+    QD_SF_TAIL_MID,         /*   strips between them (k_ocn_tail_stream: all strips), */
+    QD_SF_TAIL_R,           /*   rows of such a strip, */
+    QD_SF_TAIL_RP,          /*   rows of a pole strip, */
+    QD_SF_TAIL_GENERAL,     /*   1: every wave takes the general form (QD_TAIL_GENERAL) */
+    QD_SF_FUSED_OK,         /* k_ocn_fused (QD_OCN_FUSED=1) accepts the grid; its column groups, middle strips, their rows, QD_FUSED_SEQ */
+    QD_SF_FUSED_NTC,
+    QD_SF_FUSED_NMID,
+    QD_SF_FUSED_R,
+    QD_SF_FUSED_SEQ,
+    QD_SF_LAST_NSUB,        /* the last ocean step: sub-steps, */
+    QD_SF_LAST_USE_TAIL,    /*   the rest of a sub-step was one launch, */
+    QD_SF_LAST_TAIL_ACC,    /*   that launch reduced its own strip sums, */
+    QD_SF_LAST_USE_FUSED1,  /*   the whole sub-step was one launch (k_ocn_fused), */
+    QD_SF_LAST_MEAN_FORM,   /*   the eta mean of a sub-step was left to the next momentum launch (mean_form_ok), */
+    QD_SF_LAST_FIX_NOW,     /*   the currents were patched in place through the fix list (fix_now), */
+    QD_SF_LAST_TAIL_KERNEL, /*   last tail launch: 0 none, 1 k_ocn_tail_fast<false>, 2 k_ocn_tail_fast<true>, 3 k_ocn_tail_stream, 4 k_ocn_fused */
+    QD_SF_LAST_DYN_FORM,    /* the last momentum launch of the atmosphere: 0 none (QD_FUSED=0), 1 streaming, 2 tiles */
+    QD_SF_LAST_OCN_FORM,    /* the last momentum launch of the ocean: the same */
+    QD_SF_N
+};
+int qd_step_forms(qd_handle h, int32_t* out);
 
 /* ---- ecology spectral sub-step, first stage (pygcm/ecology/spectral.py:304-426) --------------------
  * dual_star_insolation_to_bands on the resident ISR_A / ISR_B: specA/specB/tray are the NB host-computed band weights of the

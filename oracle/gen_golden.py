@@ -840,6 +840,10 @@ def case_param_sweep(scenario):
          cells=cells, vals=vals, sums=sums, maxs=maxs)
 
 
+# (n_lat, n_lon, seed, ocean_cfl) of the *_forms fixtures
+FORM_SHAPES = ((11, 63, 111, 0.05), (47, 61, 112, 0.05), (12, 64, 113, 0.05), (13, 65, 114, 0.05), (25, 117, 115, 0.1), (29, 121, 116, 0.1))
+
+
 def main():
     only = sys.argv[1:]
 
@@ -860,6 +864,10 @@ def main():
         ("ts_19x36_spectral_diffq", 19, 36, 6, {"spec_every": 2, "diff_q": 1, "diff_cloud": 1, "k4_nsub": 2, "shapiro_every": 3}, True, 8, False, True, False),
         ("ts_19x36_pcondref_scalar_k4", 19, 36, 4, {"energy_w": 1.0, "pcond_ref": 2e-6, "k4_u": 1.0e14, "k4_q": 0.0, "tau_cond": 900.0}, True, 9, True, True, True),
     ]
+    # ragged grid shapes at which the step kernels change form (tests/step_form_cases.py has what each one reaches): energy_w = 1,
+    # albedo passed, a wet / cloudy / icy state so that every column branch is live.  Two steps: over three the condensation
+    # diagnostics of this state answer a 1e-15 perturbation of the wind with up to 2.3e-11 (tests/test_step_form_cases_cpu.py)
+    ts_cases += [(f"ts_{a}x{b}_forms", a, b, 2, {"energy_w": 1.0}, True, sd, True, True, True) for (a, b, sd, _) in FORM_SHAPES]
     for c in ts_cases:
         if want(c[0]):
             print(f"[{c[0]}]")
@@ -872,6 +880,8 @@ def main():
         ("ocean_37x72_nsub", 37, 72, 3, {"ocean_cfl": 0.02}, 24, True),
         ("ocean_19x36_nanpoison", 19, 36, 3, {}, 25, False, True),
     ]
+    # the same shapes, strong winds, an ocean_cfl that gives 2-6 sub-steps (one sub-step never reaches the deferred-mean forms)
+    oc_cases += [(f"ocean_{a}x{b}_forms", a, b, 3, {"ocean_cfl": cfl}, sd + 100, True) for (a, b, sd, cfl) in FORM_SHAPES]
     for c in oc_cases:
         if want(c[0]):
             print(f"[{c[0]}]")

@@ -1,5 +1,7 @@
 // qd_api.hip -- the C-ABI of include/qingdai_hip.h: context, memory, tables, operator seam.
 #include "qd_span.h"
+#include "qd_fused.h"
+#include "qd_ocntail.h"
 #include <chrono>
 #include <atomic>
 #include <cstring>
@@ -937,6 +939,16 @@ extern "C" int qd_step_scalars(qd_handle c, double* out8) {
 extern "C" int qd_ocean_mean_next_count(qd_handle c, int64_t* out) {
     if (!c || !out) return -1;
     *out = c->mean_next_count;
+    return 0;
+}
+
+extern "C" int qd_step_forms(qd_handle c, int32_t* out) {
+    if (!c || !out) return -1;
+    for (int k = 0; k < QD_SF_N; ++k) out[k] = 0;
+    qd_stream_report(c, out);
+    if (qd_tile_report(c, out)) return -1;
+    qd_tail_report(c, qd_segments(c, 0).g[0], out);
+    for (int k = QD_SF_LAST_NSUB; k < QD_SF_N; ++k) out[k] = c->form_last[k - QD_SF_LAST_NSUB];
     return 0;
 }
 

@@ -51,3 +51,7 @@ int qd_launch_dyn_stream(qd_ctx* c, const QdDynArgs& P, int margin);
 int qd_launch_ocn_stream(qd_ctx* c, const QdOcnArgs& P, int margin);
 bool qd_ocn_stream_ok_list(const qd_ctx* c, const QdSegList& S);              // explicit row segments (interior / boundary rows around a halo exchange)
 int qd_launch_ocn_stream_list(qd_ctx* c, const QdOcnArgs& P, const QdSegList& S);
+
+// qd_step_forms (include/qingdai_hip.h): the launchers' own shape functions asked for the handle's rows
+void qd_stream_report(qd_ctx* c, int32_t* out);          // QD_SF_DYN_STREAM .. QD_SF_OCN_VB
+int qd_tile_report(qd_ctx* c, int32_t* out);             // QD_SF_TILE_*

@@ -433,7 +433,7 @@ template <int TR> struct QdFast {
 
 struct QdFastTile { int p0, o0, o1; bool fits, interior; };
 template <int TR>
-__device__ __forceinline__ QdFastTile qd_fast_tile(const QdGeom& G, int i0) {
+__host__ __device__ __forceinline__ QdFastTile qd_fast_tile(const QdGeom& G, int i0) {      // (host: qd_tile_report)
     constexpr int RA = TR + 10;
     const int n = G.nlat, s0 = G.row0, s1 = G.row0 + G.nrows;
     const int lo = s0 == 0 ? 0 : s0 - 5, hi = s1 == n ? n : s1 + 5;
@@ -444,6 +444,10 @@ __device__ __forceinline__ QdFastTile qd_fast_tile(const QdGeom& G, int i0) {
     t.interior = t.p0 >= 2 && t.p0 + RA <= n - 2;
     return t;
 }
+
+// k_ocn_hyper: a pole tile also reads the other pole's eta row (np.roll): it must be on this slab (one text for the kernel and for
+// qd_tile_report, which asks it on the host)
+#define QD_OCN_WRAP_OK(G, t) ((t).interior || (qd_lrow((G), 0) < (G).lrows() && qd_lrow((G), (G).nlat - 1) < (G).lrows()))
 
 struct QdPoleC { int n; const double* poleA; };
 struct QdLapTabs { const double *A, *P, *Q; };      // lapA / lapP / lapQ of the cos-floor kind
@@ -756,8 +760,7 @@ k_ocn_hyper(QdGeom G, QdTabs T, QdOcnArgs P) {
     qd_tile_origin(P.ts.ntc, P.ts.ntr, TR, G.row0, i0, j0);
     if constexpr (QdFast<TR>::ok) {
         const QdFastTile t = qd_fast_tile<TR>(G, i0);
-        // a pole tile also reads the other pole's eta row (np.roll): it must be on this slab
-        const bool wrap_ok = t.interior || (qd_lrow(G, 0) < G.lrows() && qd_lrow(G, G.nlat - 1) < G.lrows());
+        const bool wrap_ok = QD_OCN_WRAP_OK(G, t);
         if (P.fast && t.fits && wrap_ok) {
             const bool bad = t.interior ? qd_ocn_fast<TR, false>(G, T, P, t, j0, lds) : qd_ocn_fast<TR, true>(G, T, P, t, j0, lds);
             if (!__syncthreads_or(bad)) return;
@@ -799,15 +802,19 @@ QdTileShape qd_pick_tile(const QdGeom& G) {
     return bs;
 }
 
-static void qd_tile_init(qd_ctx* c) {
-    if (c->tile.tr != 0) return;
-    c->tile = qd_pick_tile(c->geo);
+static QdTileShape qd_tile_of(const qd_ctx* c) {
+    QdTileShape ts = qd_pick_tile(c->geo);
     if (c->tune.tile_tr > 0) {                                // QD_TILE_TR: tuning override (read at create)
         const int tr = c->tune.tile_tr;
         for (int t = 0; t < kNTileRows; ++t)
             if (kTileRows[t] == tr)
-                c->tile = QdTileShape{tr, QD_TC, (c->geo.nrows + tr - 1) / tr, (c->geo.nlon + QD_TC - 1) / QD_TC};
+                ts = QdTileShape{tr, QD_TC, (c->geo.nrows + tr - 1) / tr, (c->geo.nlon + QD_TC - 1) / QD_TC};
     }
+    return ts;
+}
+static void qd_tile_init(qd_ctx* c) {
+    if (c->tile.tr != 0) return;
+    c->tile = qd_tile_of(c);
 }
 
 // one launch per row segment (a whole-globe handle has one; a polar band computing its wrap rows has two)
@@ -837,7 +844,9 @@ template <int TR> static void launch_ocn(qd_ctx* c, const QdOcnArgs& P, int marg
     }
 
 int qd_launch_dyn_hyper(qd_ctx* c, QdDynArgs& P, int margin) {
-    if (qd_stream_ok(c, margin)) return qd_launch_dyn_stream(c, P, margin);
+    const bool stream = qd_stream_ok(c, margin);
+    c->form_note(QD_SF_LAST_DYN_FORM, stream ? 1 : 2);
+    if (stream) return qd_launch_dyn_stream(c, P, margin);
     qd_tile_init(c);
     P.ts = c->tile;
     P.fast = c->fused_fast != 0;
@@ -848,7 +857,9 @@ int qd_launch_dyn_hyper(qd_ctx* c, QdDynArgs& P, int margin) {
 }
 
 int qd_launch_ocn_hyper(qd_ctx* c, QdOcnArgs& P, int margin) {
-    if (qd_ocn_stream_ok(c, margin)) return qd_launch_ocn_stream(c, P, margin);
+    const bool stream = qd_ocn_stream_ok(c, margin);
+    c->form_note(QD_SF_LAST_OCN_FORM, stream ? 1 : 2);
+    if (stream) return qd_launch_ocn_stream(c, P, margin);
     if (P.acc_read) return qd_fail(c, "k_ocn_hyper: an unfinished eta mean needs the streaming kernel");
     qd_tile_init(c);
     P.ts = c->tile;
@@ -856,5 +867,26 @@ int qd_launch_ocn_hyper(qd_ctx* c, QdOcnArgs& P, int margin) {
     QdScope sc(c, "k_ocn_hyper");
 #define QD_CALL_OCN(N) launch_ocn<N>(c, P, margin)
     QD_DISPATCH_TR(P.ts.tr, QD_CALL_OCN)
+    return 0;
+}
+
+// qd_step_forms: the tile the two launchers above take for the handle's rows, and how many of its row tiles pass the kernels' own
+// test for the FAST path (qd_fast_tile, asked on the host)
+template <int TR> static void tile_fast_rows(const qd_ctx* c, const QdGeom& G, int32_t* out) {
+    out[QD_SF_TILE_DYN_FAST] = 0; out[QD_SF_TILE_OCN_FAST] = 0;
+    if constexpr (QdFast<TR>::ok) {
+        for (int i0 = G.row0; i0 < G.row0 + G.nrows; i0 += TR) {
+            const QdFastTile t = qd_fast_tile<TR>(G, i0);
+            if (c->fused_fast != 0 && t.fits) { out[QD_SF_TILE_DYN_FAST] += 1; out[QD_SF_TILE_OCN_FAST] += QD_OCN_WRAP_OK(G, t) ? 1 : 0; }
+        }
+    }
+}
+int qd_tile_report(qd_ctx* c, int32_t* out) {
+    const QdTileShape ts = c->tile.tr != 0 ? c->tile : qd_tile_of(c);
+    const QdSegs S = qd_segments(c, 0);
+    const QdGeom& G = S.g[0];
+    out[QD_SF_TILE_TR] = ts.tr; out[QD_SF_TILE_NTR] = (G.nrows + ts.tr - 1) / ts.tr; out[QD_SF_TILE_NTC] = ts.ntc;
+#define QD_CALL_REP(N) tile_fast_rows<N>(c, G, out)
+    QD_DISPATCH_TR(ts.tr, QD_CALL_REP)
     return 0;
 }

@@ -88,7 +88,7 @@ __device__ __forceinline__ double qd_pow4(double x) { double x2 = x * x; return 
 
 // local row of global row g; in `full` mode rows outside [0,nlat) wrap with period nlat
 // (np.roll(axis=0) semantics); in band mode they address the halo.
-__device__ __forceinline__ int qd_lrow(const QdGeom& G, int g) {
+__host__ __device__ __forceinline__ int qd_lrow(const QdGeom& G, int g) {      // (host: the form report asks qd_fast_tile)
     int l = g - G.lbase;                       // full mode: lbase = 0
     if (l < 0) l += G.nlat; else if (l >= G.nlat) l -= G.nlat;
     return l;
@@ -310,6 +310,9 @@ struct qd_ctx {
     int qs_wgs_per_cu[3] = {0, 0, 0};   // resident workgroups per CU of k_dyn_stream<false>, <true>, k_ocn_stream (occupancy query, cached)
     int cloud_eff_valid = 0;
     int last_nsub = 0;
+    // what the launchers of the last step chose (qd_step_forms, QD_SF_LAST_* of include/qingdai_hip.h): host-side notes, never read by a launch
+    int form_last[QD_SF_N - QD_SF_LAST_NSUB] = {0};
+    void form_note(int slot, int v) { form_last[slot - QD_SF_LAST_NSUB] = v; }
     // host staging
     void* stage = nullptr; size_t stage_bytes = 0;
     // latitude bands: validity margin (rows beyond the owned band that hold current data) per slab

@@ -892,6 +892,7 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
         const double v = std::ceil(std::max(cg, uadv) * (dt / std::max(1e-12, dx_min)) / target);
         n_sub = (v != v) ? 1 : (v > 500.0 ? 500 : (v < 1.0 ? 1 : (int)v));
         c->last_nsub = n_sub;
+        c->form_note(QD_SF_LAST_NSUB, n_sub); c->form_note(QD_SF_LAST_TAIL_KERNEL, 0); c->form_note(QD_SF_LAST_OCN_FORM, 0);
     }
     // the ocean tail's fix list (QD_TAIL_FIX) pays while few cells change (a run from rest: ~40 per launch, -1.2 us per launch on the whole
     // globe, -2.5 on a 1/8 band) and costs once the polar currents sit at the cap (~700 per launch at step 240 of the benchmark: the
@@ -936,7 +937,7 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
     // its per-tile eta sums into the mean.  Measured alternatives, both slower: the tail kernel's last workgroup doing it behind
     // two-level tickets (+12 us per sub-step: ticket round trips, acquire fence and read-back form a serial chain at the very end
     // of the launch); every wave of the next momentum kernel adding the ~1100 sums itself (+3.7 us per launch).
-    const bool use_tail = c->use_fused && (!band || band_tail) && defer_eta && G0.nlon >= 64 && c->ocn_tail;
+    const bool use_tail = c->use_fused && (!band || band_tail) && defer_eta && qd_ocn_tail_ok(G0) && c->ocn_tail;
     // QD_TAIL_ACC (default): the streaming tail kernel reduces its own strip sums (fixed-point atomics + spread tickets, qd_wave.h)
     // and its last workgroup writes the mean -- no k_eta_mean_tail launch (4.5 us of launch floor per sub-step)
     const bool tail_acc = use_tail && c->tail_acc;
@@ -955,6 +956,8 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
                               p.ocean_k4_nsub == 1 && !do_shap && qd_ocn_tail_is_fast(c) && qd_ocn_stream_ok(c, 0);
     if (mean_form_ok) fix_now = false;
     const bool mean_next_ok = mean_form_ok;
+    c->form_note(QD_SF_LAST_USE_TAIL, use_tail); c->form_note(QD_SF_LAST_TAIL_ACC, tail_acc); c->form_note(QD_SF_LAST_USE_FUSED1, use_fused1);
+    c->form_note(QD_SF_LAST_MEAN_FORM, mean_form_ok); c->form_note(QD_SF_LAST_FIX_NOW, fix_now);
     unsigned long long* acc_pending = nullptr;               // the slot set the previous tail launch left for this sub-step's momentum launch
     for (int s = 0; s < n_sub; ++s) {
         if (use_fused1) {

@@ -32,6 +32,8 @@ struct QdTailArgs {
 int qd_ocn_tail_tiles(const qd_ctx* c, const QdGeom& G);
 int qd_launch_ocn_tail(qd_ctx* c, const QdGeom& G, QdTailArgs& P);
 bool qd_ocn_tail_is_fast(const qd_ctx* c);               // the launcher picks k_ocn_tail_fast
+bool qd_ocn_tail_ok(const QdGeom& G);                     // the launcher takes the grid (>= 64 columns)
+void qd_tail_report(qd_ctx* c, const QdGeom& G, int32_t* out);   // qd_step_forms: QD_SF_TAIL_*, QD_SF_FUSED_*
 
 // the whole sub-step in one launch, streaming form (QD_OCN_FUSED=1; qd_ocntail.hip, k_ocn_fused)
 struct QdOcnArgs;

@@ -693,6 +693,9 @@ k_ocn_tail_fast(QdGeom G, QdTabs T, QdTailArgs P) {
     if (wv >= 1) {
         __builtin_amdgcn_s_setprio(2);
         bool general = !(plain && W.o0 >= 3 && W.o1 <= W.n - 3 && P.use_q && P.K_h > 0.0);
+        // 60 k + 1 columns: the group before the last holds column n_lon - 1 on lane 62, whose T1 the Laplacian of lane 61 reads, and its
+        // folded gather wants columns 0 and 1 = lanes 63 and 64: not in the wave (29 x 121 showed it: SST of column 119 off by 2e-12)
+        if (W.jbase + 62 == W.m - 1) general = true;
         if (!general) {
             const bool edge_lane = W.lane >= 1 && W.lane <= 62 && (W.j == 0 || W.j == W.m - 1);
             general = __builtin_amdgcn_ballot_w64(edge_lane) != 0ull ? qt_sst_fast<true>(P, W) : qt_sst_fast<false>(P, W);
@@ -1032,6 +1035,7 @@ int qd_launch_ocn_fused(qd_ctx* c, const QdOcnArgs& O, QdTailArgs& P) {
     if (!stamps) { hipMalloc(&stamps, stamp_words * 8); hipMemcpyToSymbol(HIP_SYMBOL(qt_stamp_buf), &stamps, sizeof(stamps)); }
     hipMemsetAsync(stamps, 0, stamp_words * 8, c->stream);
 #endif
+    c->form_note(QD_SF_LAST_TAIL_KERNEL, 4);
     QD_LAUNCH_TIMED(sc, k_ocn_fused, dim3(F.ntc * (1 + F.nmid)), dim3(320), c->stream, A, c->tabs, P, F);
 #ifdef QT_STAMPS
     if (const char* f = std::getenv("QD_STAMPS_FILE")) {     // developer build (-DQT_STAMPS) only
@@ -1077,8 +1081,31 @@ int qd_ocn_tail_tiles(const qd_ctx* c, const QdGeom& G) {
     return ((G.nrows + R - 1) / R) * ((G.nlon + QS_TC2 - 1) / QS_TC2);
 }
 
+// the one-launch tail needs a full wavefront of columns
+bool qd_ocn_tail_ok(const QdGeom& G) { return G.nlon >= 64; }
+
+// qd_step_forms: what qd_launch_ocn_tail / qd_launch_ocn_fused below make of the handle's own rows
+void qd_tail_report(qd_ctx* c, const QdGeom& G, int32_t* out) {
+    const bool fast = qt_use_fast(c);
+    out[QD_SF_TAIL_KERNEL] = !(c->ocn_tail && qd_ocn_tail_ok(G)) ? 0 : (fast ? 1 : 2);
+    if (out[QD_SF_TAIL_KERNEL]) {
+        const int R = fast ? qt_fast_rows(c, G) : qt_rows(c), Rp = qt_fast_pole_rows(c);
+        const QtPart part = qt_partition(G.row0, G.row0 + G.nrows, G.nlat, R, Rp);
+        out[QD_SF_TAIL_NTC] = fast ? (G.nlon + QS_TCF - 1) / QS_TCF : (G.nlon + QS_TC2 - 1) / QS_TC2;
+        out[QD_SF_TAIL_POLE] = fast ? (part.ps > 0) + (part.pn > 0) : 0;
+        out[QD_SF_TAIL_MID] = fast ? part.nmid : (G.nrows + R - 1) / R;
+        out[QD_SF_TAIL_R] = R; out[QD_SF_TAIL_RP] = fast ? Rp : 0;
+        out[QD_SF_TAIL_GENERAL] = c->tune.tail_general ? 1 : 0;
+    }
+    QfuArgs F;
+    if (qfu_shape(c, F)) {
+        out[QD_SF_FUSED_OK] = 1; out[QD_SF_FUSED_NTC] = F.ntc; out[QD_SF_FUSED_NMID] = F.nmid; out[QD_SF_FUSED_R] = F.R;
+        out[QD_SF_FUSED_SEQ] = F.mode & 1;
+    }
+}
+
 int qd_launch_ocn_tail(qd_ctx* c, const QdGeom& G, QdTailArgs& P) {
-    if (G.nlon < 64) return qd_fail(c, "k_ocn_tail: >= 64 columns");
+    if (!qd_ocn_tail_ok(G)) return qd_fail(c, "k_ocn_tail: >= 64 columns");
     if (G.full) { P.own0 = 0; P.own1 = G.nlat; }
     QdScope sc(c, "ocean_tail", true);
     const bool fast = qt_use_fast(c);
@@ -1108,6 +1135,7 @@ int qd_launch_ocn_tail(qd_ctx* c, const QdGeom& G, QdTailArgs& P) {
     if ((P.acc_next || P.acc_clear) && (!fast || P.fix_count || !G.full))        // only k_ocn_tail_fast<false> knows them (the caller decides the form)
         return qd_fail(c, "k_ocn_tail: the mean of a sub-step can only be left to the next launch by the storing fast form");
     if (!fast || !P.acc) { P.fix_count = nullptr; P.fix_list = nullptr; }          // the fix list is applied by k_ocn_tail_fast's finishing wave
+    c->form_note(QD_SF_LAST_TAIL_KERNEL, fast ? (P.fix_count ? 2 : 1) : 3);
     if (fast && P.fix_count) QD_LAUNCH_TIMED(sc, k_ocn_tail_fast<true>, dim3(nrs * P.ntc), dim3(128), c->stream, G, c->tabs, P);
     else if (fast) QD_LAUNCH_TIMED(sc, k_ocn_tail_fast<false>, dim3(nrs * P.ntc), dim3(128), c->stream, G, c->tabs, P);
     else QD_LAUNCH_TIMED(sc, k_ocn_tail_stream<1>, dim3(nrs * P.ntc), dim3(128), c->stream, G, c->tabs, P);

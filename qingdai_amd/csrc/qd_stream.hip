@@ -156,6 +156,20 @@ bool qd_stream_ok(const qd_ctx* c, int margin) {
            qs_segments_ok(c, margin);
 }
 
+// qd_step_forms: what the two launchers below make of the handle's rows (margin 0, one segment)
+void qd_stream_report(qd_ctx* c, int32_t* out) {
+    out[QD_SF_DYN_STREAM] = qd_stream_ok(c, 0) ? 1 : 0;
+    out[QD_SF_OCN_STREAM] = qd_ocn_stream_ok(c, 0) ? 1 : 0;
+    const QdSegs S = qd_segments(c, 0);
+    const QdGeom& G = S.g[0];
+    for (int k = 0; k < 2; ++k) {
+        if (!out[k == 0 ? QD_SF_DYN_STREAM : QD_SF_OCN_STREAM]) continue;
+        const QsShape sh = qs_shape(c, G.nrows, G.nlon, k == 0 ? 0 : 2, G.row0 + G.nrows == G.nlat);
+        int32_t* o = out + (k == 0 ? QD_SF_DYN_NTC : QD_SF_OCN_NTC);
+        o[0] = (G.nlon + QS_TC - 1) / QS_TC; o[1] = sh.nrs; o[2] = sh.R; o[3] = sh.vb;
+    }
+}
+
 // packed row tables {lapA[r+1], lapP[r], lapQ[r], k4[r]} per field; a scalar k4 override (QD_K4_U, ...) fills the column
 const double* qd_stream_tables(qd_ctx* c, int kind, int nf, const double* const* k4row, const double* k4s, const int* skip) {
     const int nlat = c->geo.nlat;

@@ -30,7 +30,7 @@ __device__ __forceinline__ double qd_west(double x) {
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x138, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ int qd_clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
+__host__ __device__ __forceinline__ int qd_clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // buffer access: the range check of the resource drops a store (returns 0 for a load) whose lane offset is QD_BUF_OOB, so a
 // masked store needs no exec branch (a branch around a store costs the row loops a full s_waitcnt vmcnt(0))

@@ -614,6 +614,12 @@ class Device:
         """Ocean sub-steps since create whose eta mean the next momentum launch finished (QD_MEAN_IN_MOMENTUM)."""
         return self.call("qd_ocean_mean_next_count", OUT)
 
+    def step_forms(self):
+        """Which form of the step kernels this handle takes and what the last step chose (include/qingdai_hip.h: qd_step_forms,
+        enum qd_step_form), by the enumerators' lower-case names: dyn_stream, ocn_ntc, tile_tr, tail_kernel, last_mean_form, ..."""
+        out = self.call("qd_step_forms", OUT(_lib.C["QD_SF_N"]))
+        return {k[len("QD_SF_"):].lower(): int(out[v]) for k, v in _lib.C.items() if k.startswith("QD_SF_") and k != "QD_SF_N"}
+
     def counters(self):
         return self.call("qd_get_step_counter", OUT, OUT)
 
