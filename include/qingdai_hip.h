@@ -799,6 +799,35 @@ int qd_series_sample(qd_handle h);                                   /* class se
 int qd_series_log(qd_handle h, double* out, int max, int* n);        /* drain: *n records of width doubles, oldest first */
 int qd_series_reset(qd_handle h);                                    /* log and schedule forgotten */
 
+/* ---- zonal wavenumber spectra (QD_SPECTRA), whole-globe handles ----------------------------------------------------------
+ * Nothing the reference has built (its plan for the dissipation filters asks for them).  A span lane without a flag bit and with a
+ * device log, like the series: a schedule given before a qd_step_n span turns it on for that span, and on every sampled step each
+ * entry (a history entry: op 0 = an f64 plane, 1 = sqrt(a*a + b*b)) is transformed row by row: with n = n_lon,
+ * X_j(k) = sum_i x[j][i] exp(-2 pi i ik / n) for k = 0 .. n / 2 (n_bins = n / 2 + 1),
+ *     P_j(k) = c_k |X_j(k)|^2 / n^2      c_k = 1 for k = 0 and for k = n / 2 of an even n, else 2      (sum_k P_j(k) = mean_i x^2)
+ *     P(k) = sum_j w_j P_j(k) / sum_j w_j                                with w_j = w_row[j] (the host's max(cos lat_j, 0)).
+ * A row that holds a non-finite value is NaN in every bin, makes every bin of P NaN, and is counted.  The n entries' results in
+ * configure order are ONE record of n * (n_bins + QD_SPECTRA_STATS) doubles -- per entry P(0 .. n / 2), then the count of non-finite
+ * rows; the log holds QD_SPECTRA_LOG_CAP records between two drains.  With lat_resolved the P_j(k) are also added into resident sum
+ * planes [n][n_lat][n_bins] (qd_spectra_sums_get / _set).  Rows of length 2^a 3^b 5^c take a mixed-radix FFT in LDS, every other
+ * length a direct DFT (QD_SPECTRA_FORM=direct in the environment of the configure call: the direct form everywhere); the order of
+ * every sum is fixed (csrc/qd_spectra.hip, qingdai_amd/spectra.py: combine_reference).  Entries that read PRECIP are sampled in
+ * front of the ocean step, the others behind the step's last launch: two launches per sampling position, none on unsampled steps;
+ * a sampled step stores the lazily stored diagnostics when an entry reads one. */
+#define QD_SPECTRA_MAX_ENTRIES 32                        /* entries of one configuration */
+#define QD_SPECTRA_LOG_CAP 256                           /* records the spectra log holds between two drains */
+#define QD_SPECTRA_STATS 1                               /* the count of non-finite rows behind an entry's n_bins powers */
+/* n entries as qd_history_configure takes them, lat_resolved != 0: the sum planes are kept, w_row[n_lat]: the row weights.
+ * Allocates the log, the twiddle table and the planes; forgets an earlier configuration; n == 0 only releases.  Refused as in
+ * qd_history_configure, and with one line when a row's working set does not fit the LDS a workgroup may take. */
+int qd_spectra_configure(qd_handle h, int n, const int32_t* op, const int32_t* a, const int32_t* b, int lat_resolved, const double* w_row); /* n == 0 releases */
+int qd_spectra_schedule(qd_handle h, int steps, const int32_t* sample); /* the next qd_step_n span: non-zero = the step is sampled */
+int qd_spectra_sample(qd_handle h);                                  /* class seam: one record now, outside a span */
+int qd_spectra_log(qd_handle h, double* out, int max, int* n);       /* drain: *n records of width doubles, oldest first */
+int qd_spectra_sums_get(qd_handle h, double* sums, int64_t* count);  /* lat_resolved: the sums [n][n_lat][n_bins] and the samples in them */
+int qd_spectra_sums_set(qd_handle h, const double* sums, int64_t count);   /* its inverse, for an exact resume (QD_CHECKPOINT) */
+int qd_spectra_reset(qd_handle h);                                   /* log and schedule forgotten, sums and count zeroed */
+
 /* ---- state digest and exact resume (QD_CHECKPOINT), whole-globe handles ---------------------------------------------------
  * Nothing the reference has: its restart file holds 14 planes as f4 and a resumed run does not continue the run that was stopped.
  * qd_state_digest: a 64-bit digest of resident planes, all of them in ONE launch.  The digest of a plane of n elements is
@@ -818,6 +847,7 @@ enum qd_state_ref {
 };
 #define QD_STATE_REF_TRACERS 64                         /* index range of QD_SR_PHYTO_TRACER */
 #define QD_STATE_REF_HISTORY_SUMS QD_HISTORY_MAX_ENTRIES   /* index range of QD_SR_HISTORY_SUM */
+#define QD_STATE_REF_SPECTRA_SUMS 500                   /* one more ref: the lat-resolved sums of the spectra lane, [n][n_lat][n_bins] as ONE plane */
 #define QD_STATE_DIGEST_MAX 64
 /* n <= 64 refs -> out[n].  Refused: latitude bands, an unknown ref, a ref whose subsystem is not configured (the line names it). */
 int qd_state_digest(qd_handle h, int n, const int32_t* refs, uint64_t* out);

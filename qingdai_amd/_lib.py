@@ -178,6 +178,9 @@ HISTORY_MAX_ENTRIES = C["QD_HISTORY_MAX_ENTRIES"]
 SERIES_MAX_ENTRIES = C["QD_SERIES_MAX_ENTRIES"]
 SERIES_LOG_CAP = C["QD_SERIES_LOG_CAP"]              # records the series lane's device log holds between two drains
 SERIES_STATS = C["QD_SERIES_STATS"]                  # mean, min, max, nan_count in front of an entry's zonal means
+SPECTRA_MAX_ENTRIES = C["QD_SPECTRA_MAX_ENTRIES"]
+SPECTRA_LOG_CAP = C["QD_SPECTRA_LOG_CAP"]            # records the spectra lane's device log holds between two drains
+SPECTRA_STATS = C["QD_SPECTRA_STATS"]                # the count of non-finite rows behind an entry's n_bins powers
 STATE_DIGEST_MAX = C["QD_STATE_DIGEST_MAX"]          # refs per qd_state_digest call
 STATE_SCALARS_N = C["QD_STATE_SCALARS_N"]
 # enum qd_state_scalar: the slots of qd_state_scalars_get / set, by their lower-case names
@@ -189,9 +192,11 @@ STATE_REF_COUNT = {"PHYTO_TRACER": C["QD_STATE_REF_TRACERS"], "HISTORY_SUM": C["
 
 def state_ref(name):
     """A plane's name -> the ref qd_state_digest takes: a field name of F (f64 fields and the two masks), a name of STATE_REFS, or
-    an indexed one, "PHYTO_TRACER:s" / "HISTORY_SUM:k"."""
+    an indexed one, "PHYTO_TRACER:s" / "HISTORY_SUM:k", or "SPECTRA_SUMS"."""
     if name in FIELDS or name in ("LAND_MASK", "ICE_MASK"):
         return F[name]
+    if name == "SPECTRA_SUMS":                        # a ref of its own beside the enum (QD_STATE_REF_SPECTRA_SUMS)
+        return C["QD_STATE_REF_SPECTRA_SUMS"]
     base, _, idx = str(name).partition(":")
     if base in STATE_REF_COUNT and idx.isdigit() and int(idx) < STATE_REF_COUNT[base]:
         return STATE_REFS[base] + int(idx)

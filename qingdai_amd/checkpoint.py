@@ -12,6 +12,8 @@ The file (one NetCDF file through ncio.write_nc, f8 / u1 / i8 only; written to a
   hist_sums, hist_clock {i, t_first, t_last, n_open, count}       an open history window continues
   series_records, series_times, series_steps, series_clock {i, records}   an open series window continues (QD_SERIES=1 only; host
                       data: the records were reduced on the device and enter no digest)
+  spectra_records, spectra_times, spectra_steps, spectra_clock {i, records, count}, spectra_sums   an open spectra window continues
+                      (QD_SPECTRA=1 only); the lat-resolved sum planes (QD_SPECTRA_LAT=1) are resident and digested as SPECTRA_SUMS
   qd_*                the ecology's own exact-resume variables (ecology.py: EcologyAdapter._extension_variables), not restated here
   atm_counter, ocn_counter, step_index, span_mark {step index, atm counter at the last span's end}, t_seconds, t_origin {t0, steps
   since, their dt}, diversity_next_day,
@@ -149,6 +151,9 @@ def subsystems(sim):
     pop = sim.eco.pop if sim.eco is not None else None
     ser = getattr(sim, "series", None)
     extra = {"series": f"{','.join(ser.names)}|zonal={int(ser.zonal)}|every={int(ser.every)}"} if ser is not None else {}
+    spc = getattr(sim, "spectra", None)
+    if spc is not None:                 # likewise the spectra lane's
+        extra["spectra"] = f"{','.join(spc.names)}|every={int(spc.every)}|lat={int(spc.lat_resolved)}"
     return {**{"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
             "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
             "phyto_daily": str(int(sim.phyto_daily is not None)),
@@ -171,6 +176,9 @@ def plane_names(sim):
         names += ["INDIV_E_DAY", "INDIV_STRESS"]
     if sim.history is not None:
         names += [f"HISTORY_SUM:{k}" for k in range(len(sim.history.names))]
+    spc = getattr(sim, "spectra", None)
+    if spc is not None and spc.lat_resolved:
+        names.append("SPECTRA_SUMS")
     return names
 
 
@@ -268,6 +276,20 @@ def collect(sim):
         v["series_times"] = ("f8", ("series_time",), np.concatenate([times, np.zeros(pad - n)]))
         v["series_steps"] = ("f8", ("series_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
         v["series_clock"] = ("f8", ("two",), np.array([float(ser.i), float(n)]))
+    spc = getattr(sim, "spectra", None)
+    if spc is not None:
+        recs, times, steps = spc.window()
+        n = int(len(recs))
+        pad = max(n, 1)
+        dims["spectra_time"], dims["spectra_width"] = pad, int(spc.width)
+        v["spectra_records"] = ("f8", ("spectra_time", "spectra_width"), np.concatenate([recs, np.zeros((pad - n, spc.width))]))
+        v["spectra_times"] = ("f8", ("spectra_time",), np.concatenate([times, np.zeros(pad - n)]))
+        v["spectra_steps"] = ("f8", ("spectra_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
+        sums, count = spc.sums()
+        v["spectra_clock"] = ("f8", ("three",), np.array([float(spc.i), float(n), float(count)]))
+        if sums is not None:
+            dims["spectra_entry"], dims["spectra_k"] = int(sums.shape[0]), int(sums.shape[2])
+            v["spectra_sums"] = ("f8", ("spectra_entry", "lat", "spectra_k"), sums)
     if sim.eco is not None and sim.eco.pop is not None:
         xd, xv = sim.eco._extension_variables(sim.indiv)
         dims["species"] = int(sim.eco.pop.Ns)
@@ -340,7 +362,7 @@ class CheckpointFile:
         if key is not None:
             return np.asarray(v[key], dtype=np.float64)[int(idx)]
         key = {"ROUTE_BUFFER": "route_buffer", "ROUTE_FLOW": "route_flow", "ROUTE_LAKES": "route_lakes", "ECO_LAI_STACK": "qd_LAI_layers_SK",
-               "INDIV_E_DAY": "qd_indiv_E_day", "INDIV_STRESS": "qd_indiv_stress_days"}[name]
+               "INDIV_E_DAY": "qd_indiv_E_day", "INDIV_STRESS": "qd_indiv_stress_days", "SPECTRA_SUMS": "spectra_sums"}[name]
         return np.asarray(v[key], dtype=np.float64)
 
     def subsystems(self):
@@ -388,6 +410,9 @@ def check_subsystems(f, sim):
     if got.get("series", "-") != want.get("series", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the series lane is '{got.get('series', '-')}' in the file and "
                                 f"'{want.get('series', '-')}' in this run")
+    if got.get("spectra", "-") != want.get("spectra", "-"):
+        raise CheckpointRefused(f"the subsystem set differs: the spectra lane is '{got.get('spectra', '-')}' in the file and "
+                                f"'{want.get('spectra', '-')}' in this run")
     for k in want:
         if got.get(k) != want[k]:
             if k == "history":
@@ -432,6 +457,8 @@ def _file_plane_names(f):
     names += [n for n, k in (("INDIV_E_DAY", "qd_indiv_E_day"), ("INDIV_STRESS", "qd_indiv_stress_days")) if k in v]
     if "hist_sums" in v:
         names += [f"HISTORY_SUM:{k}" for k in range(np.shape(v["hist_sums"])[0])]
+    if "spectra_sums" in v:
+        names.append("SPECTRA_SUMS")
     return names
 
 
@@ -513,6 +540,12 @@ def load(sim, path, env=None, out=print):
         sim.series.restore_window(np.asarray(v["series_records"], dtype=np.float64)[:n], np.asarray(v["series_times"])[:n],
                                   np.asarray(v["series_steps"])[:n], int(clock[0]))
         dev.series_reset()
+    if getattr(sim, "spectra", None) is not None:
+        clock = np.asarray(v["spectra_clock"], dtype=np.float64)
+        n = int(clock[1])
+        sim.spectra.restore_window(np.asarray(v["spectra_records"], dtype=np.float64)[:n], np.asarray(v["spectra_times"])[:n],
+                                   np.asarray(v["spectra_steps"])[:n], int(clock[0]),
+                                   sums=np.asarray(v["spectra_sums"], dtype=np.float64) if "spectra_sums" in v else None, count=int(clock[2]))
     # 3. counters, parameters, the host-side scalars (last: the uploads above set some of the flags they carry)
     dev.set_counters(int(f.scalar("atm_counter")), int(f.scalar("ocn_counter")))
     if autotune:

@@ -485,6 +485,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_budget_release(c);
     qd_history_release(c);
     qd_series_release(c);
+    qd_spectra_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -717,6 +718,10 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     const bool with_series = qd_series_scheduled(c);
     if (with_series && !(span.lane[QD_LANE_SERIES] = qd_series_span_begin(c, n))) return -1;
     const bool series_lazy = with_series && qd_series_reads_lazy(c);
+    // nor have the zonal spectra (qd_spectra.hip): a sampled step transforms its fields' rows into one record, two launches per position
+    const bool with_spectra = qd_spectra_scheduled(c);
+    if (with_spectra && !(span.lane[QD_LANE_SPECTRA] = qd_spectra_span_begin(c, n))) return -1;
+    const bool spectra_lazy = with_spectra && qd_spectra_reads_lazy(c);
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -729,6 +734,8 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         const bool hist_fire = with_hist && span.lane[QD_LANE_HISTORY]->at(s) != 0.0;
         const bool series_fire = with_series && span.lane[QD_LANE_SERIES]->at(s) != 0.0;
         if (series_fire && (rc = qd_series_begin_step(c))) return rc;
+        const bool spectra_fire = with_spectra && span.lane[QD_LANE_SPECTRA]->at(s) != 0.0;
+        if (spectra_fire && (rc = qd_spectra_begin_step(c))) return rc;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
         if (with_pdaily && span.lane[QD_LANE_PHYTO_DAILY]->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
@@ -749,7 +756,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         const QdForcingCall fc{st, st + 3, st[6]};
         // lazy diagnostics: inside a span only the last step stores what nothing inside a span reads -- unless a reader comes with the flags
         c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag || bd_main || (hist_fire && hist_lazy) ||
-                         (series_fire && series_lazy)) ? 1 : 0;
+                         (series_fire && series_lazy) || (spectra_fire && spectra_lazy)) ? 1 : 0;
         if (with_phys) {
             const int part = c->precip_done ? 2 : 0;         // the precipitation block may have run inside the previous ocean step
             c->precip_done = 0;
@@ -781,6 +788,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // history: PRECIP is this step's until the block below overwrites it with the next step's -- its entries are sampled here
         if (hist_fire && (rc = qd_history_accumulate(c, 0))) return rc;
         if (series_fire && (rc = qd_series_reduce(c, 0))) return rc;
+        if (spectra_fire && (rc = qd_spectra_transform(c, 0))) return rc;
         // The precipitation block of step s + 1 (run_simulation.py:1740-1790) reads u, v and P_cond as time_step left them and
         // nothing the ocean step, the tracers, the individuals or the bucket touch, and writes only what the rest of step s + 1's
         // driver physics reads: it is queued inside the ocean step, between the stress kernel and the host's wait for the CFL maxima.
@@ -803,6 +811,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // history: every other entry as the step leaves it -- what a span that ended here would hand to qd_download
         if (hist_fire && (rc = qd_history_accumulate(c, 1))) return rc;
         if (series_fire && (rc = qd_series_reduce(c, 1))) return rc;
+        if (spectra_fire && (rc = qd_spectra_transform(c, 1))) return rc;
     }
     c->diag_write = 1;
     return qd_launch_check(c, "qd_step_n");

@@ -214,6 +214,7 @@ struct qd_ctx {
     struct QdBudget* budget = nullptr;       // periodic budget diagnostics: schedule, SST snapshot, row partials, log (qd_budget_diag.hip)
     struct QdHistory* history = nullptr;     // time-mean history: entry table, sum planes, sample count, schedule (qd_history.hip)
     struct QdSeries* series = nullptr;       // per-step series: entry table, row weights, row results, record log, schedule (qd_series.hip)
+    struct QdSpectra* spectra = nullptr;     // zonal spectra: entry table, twiddles, row powers, sum planes, record log, schedule (qd_spectra.hip)
     unsigned long long* digest_out = nullptr; // [64] results of qd_state_digest, allocated at its first call (qd_digest.hip)
     double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
     int hydronet_sweeps = -1;        // pit-fill sweeps of the last qd_hydronet_build on this handle (qd_hydronet.hip)
@@ -537,6 +538,14 @@ bool qd_series_reads_lazy(const qd_ctx* c);
 struct QdSpanLane* qd_series_span_begin(qd_ctx* c, int n);
 int  qd_series_begin_step(qd_ctx* c);
 int  qd_series_reduce(qd_ctx* c, int group);
+// qd_spectra.hip: the same protocol again; transform is the two launches of a sampling position (row spectra, cross-row combination)
+void qd_spectra_release(qd_ctx* c);
+bool qd_spectra_scheduled(const qd_ctx* c);
+bool qd_spectra_reads_lazy(const qd_ctx* c);
+struct QdSpanLane* qd_spectra_span_begin(qd_ctx* c, int n);
+int  qd_spectra_begin_step(qd_ctx* c);
+int  qd_spectra_transform(qd_ctx* c, int group);
+bool qd_spectra_planes(const qd_ctx* c, const double** sums, size_t* n);      // the lat-resolved sums as one plane (qd_state_digest)
 // what qd_state_digest and the exact resume (qd_digest.hip) need from the feature modules: their resident planes, and their firing
 // counts (set >= 0 stores it; -> the count as it then stands, 0 when the module is not configured)
 bool qd_route_planes(const qd_ctx* c, const double** buf, const double** flow, const double** lakes, int* n_lakes);    // qd_route.hip

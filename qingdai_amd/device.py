@@ -25,6 +25,8 @@ def _c(a, dtype=np.float64):
 class Device:
     _history_n = 0            # entries of the last history_configure
     _series_width = 0         # doubles per record of the last series_configure
+    _spectra_n = 0            # entries of the last spectra_configure
+    _spectra_lat = False      # ... and whether it keeps the lat-resolved sum planes
     _tiles_n = 1              # tiles of the last tile configuration
     _div_shape = None         # [S, lat, lon] of the last eco_diversity call
 
@@ -132,7 +134,7 @@ class Device:
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
                ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None,
-               series=None):
+               series=None, spectra=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  The span lanes, each a participant on this handle whose records stay in its
         device log until the caller has it deliver them: `routing`, a RiverRouting -- bit7, after the hydrology commit (which it
@@ -142,7 +144,8 @@ class Device:
         budget_diag.BudgetDiag -- no flag bit: its schedule (run-local step index, the ocean's step count) turns the lane on for
         the span.  `history`, a history.History -- no flag bit either: its window clock names the sampled steps, whose fields are
         added to the resident sums (history_read).  `series`, a series.Series -- no flag bit: its window clock names the sampled
-        steps, each of which leaves one record of reduced fields in the lane's log (series_log)."""
+        steps, each of which leaves one record of reduced fields in the lane's log (series_log).  `spectra`, a spectra.Spectra -- no flag bit:
+        likewise, one record of zonal wavenumber spectra per sampled step (spectra_log)."""
         self.flush()
         st = _c(stars)
         assert st.ndim == 2 and st.shape[1] == 7
@@ -154,7 +157,7 @@ class Device:
         #   span_restore(clock)       nothing ran (an upload or qd_step_n raised): the clock back to what span_clock gave
         #   _fired(k)                 the span ran: k is what span_schedule returned
         #   span_deliver(dt)          drain the lane's device log and deliver it (print, keep); the caller's move, once per span
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series) if p is not None]
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra) if p is not None]
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -302,6 +305,52 @@ class Device:
 
     def series_reset(self):
         self.call("qd_series_reset")
+
+    # ---- zonal wavenumber spectra (qd_spectra.hip)
+    def spectra_configure(self, entries, lat_resolved, w_row):
+        """entries: [(op, a, b)] as history_configure takes them; lat_resolved: the per-row powers are also summed in resident
+        planes (spectra_sums); w_row [n_lat]: the row weights of the global spectrum, max(cos lat, 0).  An empty list releases the
+        lane.  QD_SPECTRA_FORM=direct in the environment of this call forces the direct DFT."""
+        if len(entries) and (w_row is None or np.size(w_row) != self.shape[0]):
+            raise ValueError("spectra_configure: w_row holds one weight per latitude row")
+        self.call("qd_spectra_configure", len(entries), [e[0] for e in entries], [F[e[1]] for e in entries],
+                  [F[e[2]] if e[2] is not None else -1 for e in entries], int(bool(lat_resolved)), None if w_row is None else _c(w_row).reshape(-1))
+        self._spectra_n, self._spectra_lat = len(entries), bool(lat_resolved) and len(entries) > 0
+
+    @property
+    def spectra_bins(self):
+        return self.shape[1] // 2 + 1
+
+    def spectra_schedule(self, sample):
+        self.call("qd_spectra_schedule", np.size(sample), sample)
+
+    def spectra_sample(self):
+        """One record of every entry from the fields as they stand (the class seam)."""
+        self.flush()
+        self.call("qd_spectra_sample")
+
+    def spectra_log(self, max_records=None):
+        """Drain the records -> [n][width], oldest first; width = entries * (n_bins + SPECTRA_STATS), per entry the global spectrum
+        P(0 .. n_lon // 2) and then the count of non-finite rows.  max_records: what the caller knows to be queued at most."""
+        room = _lib.SPECTRA_LOG_CAP if max_records is None else max(0, min(int(max_records), _lib.SPECTRA_LOG_CAP))
+        w = max(1, self._spectra_n * (self.spectra_bins + _lib.SPECTRA_STATS))
+        buf = np.empty(max(1, room) * w, dtype=np.float64)      # a record is large: no zero-filled ctypes buffer here
+        return self._records((buf, self.call("qd_spectra_log", buf, room, OUT)), w)
+
+    def spectra_sums(self):
+        """-> (sums [n][n_lat][n_bins] of the per-row powers, sample count); lat-resolved configurations only."""
+        out = np.empty((self._spectra_n, self.shape[0], self.spectra_bins), dtype=np.float64)
+        return out, self.call("qd_spectra_sums_get", out, OUT)
+
+    def spectra_sums_set(self, sums, count):
+        """The inverse of spectra_sums, for an exact resume."""
+        want = (self._spectra_n, self.shape[0], self.spectra_bins)
+        if np.shape(sums) != want:
+            raise ValueError(f"spectra_sums_set: expected sums of shape {want}, got {np.shape(sums)}")
+        self.call("qd_spectra_sums_set", _c(sums), count)
+
+    def spectra_reset(self):
+        self.call("qd_spectra_reset")
 
     # ---- daily phytoplankton step (qd_phyto_daily.hip)
     def phyto_daily_configure(self, params, band_tab, species_tab, shape):
@@ -630,7 +679,7 @@ class Device:
     def digest(self, names):
         """The 64-bit digests of resident planes (include/qingdai_hip.h: qd_state_digest), one launch per 64 of them -> np.uint64[n].
         names: what _lib.state_ref takes -- field names, LAND_MASK, ICE_MASK, ROUTE_BUFFER, ROUTE_FLOW, ROUTE_LAKES, ECO_LAI_STACK,
-        INDIV_E_DAY, INDIV_STRESS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
+        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
         self.flush()
         refs = [_lib.state_ref(n) for n in names]
         out = np.zeros(len(refs), dtype=np.uint64)

@@ -100,6 +100,17 @@ ends.  A chunk ends with a window's last step, behind which <QD_OUTPUT_DIR>/seri
 per field {name}_mean / _min / _max / _nan [time] and {name}_zonal [time][lat], dt_seconds, sample_every, zonal, complete) is
 written and one [Series] line printed, labelled like the history files.  The normal end of main writes the open window with
 complete = 0; the signal path does not; under QD_CHECKPOINT=1 the checkpoint carries the open window instead.
+Zonal wavenumber spectra (QD_SPECTRA=1, default 0; the reference's plan for its dissipation filters asks for them, its code has
+none): on every QD_SPECTRA_EVERY-th (default 24) step of a window of QD_SPECTRA_EVERY_DAYS (default 10) planet-days -- history's
+window clock -- every row of every field of QD_SPECTRA_FIELDS (default U,V,H,Q,CLOUD; history's parser, ocean-only rule and
+refusals) is transformed on the device to its one-sided variance spectrum P_j(k), k = 0 .. n_lon // 2 (an f64 FFT in LDS for row
+lengths 2^a 3^b 5^c, a direct DFT otherwise or under QD_SPECTRA_FORM=direct), and the rows are combined with cos-latitude weights in
+a fixed order, by a seventh span lane (qingdai_amd/spectra.py, qd_spectra_*) whose records stay in a device log until the chunk ends;
+under QD_SPECTRA_LAT=1 (default) the per-row powers are also summed in resident planes.  A chunk ends with a window's last step,
+behind which <QD_OUTPUT_DIR>/spectra/spectra_day_{a}_{b}.nc (time_seconds, step, wavenumber, lat, per field {name}_power [time][k],
+{name}_bad_rows, {name}_hi_frac [time], {name}_power_lat [lat][k], ke_power when U and V are selected, dt_seconds, sample_every,
+lat_resolved, n_samples, complete) is written and one [Spectra] line printed.  The normal end of main writes the open window with
+complete = 0; the signal path does not; under QD_CHECKPOINT=1 the checkpoint carries the open window and the sum planes instead.
 Exact resume (QD_CHECKPOINT=1, default 0; nothing the reference has: its restart holds 14 planes as f4 and t_seconds, and the step
 counters, routing buffers, tracers, carry-over planes, autotuned parameters and history window start again): every autosave --
 periodic, signal, atexit, final -- also writes <QD_DATA_DIR>/checkpoint.nc (QD_CHECKPOINT_PATH names another file) behind the
@@ -242,6 +253,7 @@ class Simulation:
     phyto = phyto_daily = None
     routing = budget = history = None      # enable_routing, enable_budget_diag (QD_BUDGET_DIAG=1), enable_history (QD_HISTORY=1)
     series = None                          # enable_series (QD_SERIES=1)
+    spectra = None                         # enable_spectra (QD_SPECTRA=1)
     truecolor = stateframe = figures = None
     plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
     _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
@@ -831,17 +843,21 @@ class Simulation:
     def _run_cut(self, n, energy_diag=False):
         """n steps through _run_lanes; under QD_HISTORY=1 cut so that a chunk ends with a window's last step, behind which the
         window's file is written (the sums then start the next window from zero); under QD_SERIES=1 likewise with its windows."""
-        hist, ser = self.history, self.series
+        hist, ser, spc = self.history, self.series, getattr(self, "spectra", None)
         while n > 0:
             k = n if hist is None else min(n, hist.steps_to_window_end())
             if ser is not None:
                 k = min(k, ser.steps_to_window_end())
+            if spc is not None:
+                k = min(k, spc.steps_to_window_end())
             self._run_lanes(k, energy_diag)
             n -= k
             if hist is not None and hist.window_closed():
                 self.flush_history()
             if ser is not None and ser.window_closed():
                 self.flush_series()
+            if spc is not None and spc.window_closed():
+                self.flush_spectra()
 
     def flush_history(self, complete=1):
         """Write the history window that stands in the accumulators -> the path or None.  A failure is reported and the window is
@@ -853,6 +869,11 @@ class Simulation:
         output never stops the run."""
         return self._nonfatal(lambda: self.series.flush(complete=complete), "[Series] window skipped: {}", cleanup=self.series.drop)
 
+    def flush_spectra(self, complete=1):
+        """Write the spectra window that stands on the host (and in the device's sum planes) -> the path or None.  A failure is
+        reported and the window is dropped: output never stops the run."""
+        return self._nonfatal(lambda: self.spectra.flush(complete=complete), "[Spectra] window skipped: {}", cleanup=self.spectra.drop)
+
     def _run_lanes(self, n, energy_diag=False):
         """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
         individuals')."""
@@ -863,7 +884,8 @@ class Simulation:
         if self.budget is not None:
             self.budget.routed = self.routing is not None
         lanes = {k: p for k, p in (("phyto_daily", self.phyto_daily), ("routing", self.routing), ("budget", self.budget),
-                                   ("eco_daily", eco_daily), ("history", self.history), ("series", self.series)) if p is not None}
+                                   ("eco_daily", eco_daily), ("history", self.history), ("series", self.series),
+                                   ("spectra", getattr(self, "spectra", None))) if p is not None}
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
         # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
@@ -928,6 +950,15 @@ class Simulation:
         self.series = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
                                dt=float(self.dt), day=self.day_seconds)
         return self.series
+
+    def enable_spectra(self, env=None):
+        """QD_SPECTRA=1: zonal wavenumber spectra of the selected fields, transformed by a device lane and written per window to
+        <QD_OUTPUT_DIR>/spectra/ (qingdai_amd/spectra.py) -> the Spectra or None.  The run-local step index the windows count on
+        starts where this is called.  An unknown field name raises here, before the loop."""
+        from .spectra import from_env
+        self.spectra = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
+                                dt=float(self.dt), day=self.day_seconds)
+        return self.spectra
 
     def enable_routing(self, env=None):
         """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
@@ -1194,6 +1225,8 @@ def main(argv=None):
     sim.enable_history(env)
     if getattr(sim, "enable_series", None) is not None:        # (a stand-in Simulation from before the series lane has none)
         sim.enable_series(env)
+    if getattr(sim, "enable_spectra", None) is not None:       # (likewise)
+        sim.enable_spectra(env)
     if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
         try:
             sim.load_checkpoint(ck_file, env)
@@ -1279,6 +1312,8 @@ def main(argv=None):
         sim.flush_history(complete=0)
     if getattr(sim, "series", None) is not None and not (ck["enabled"] and autosave_on):
         sim.flush_series(complete=0)                           # likewise the open series window
+    if getattr(sim, "spectra", None) is not None and not (ck["enabled"] and autosave_on):
+        sim.flush_spectra(complete=0)                          # and the open spectra window
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")
