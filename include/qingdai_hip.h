@@ -194,6 +194,14 @@ int qd_op_divergence(qd_handle h, const double* u, const double* v, double* out)
 int qd_op_vorticity(qd_handle h, const double* u, const double* v, double* out);    /* grid.py:70-88 */
 int qd_op_gaussian(qd_handle h, const double* F, double sigma, int mode_wrap, double* out); /* physics.py:44 */
 int qd_op_median_positive(qd_handle h, const double* x, double dflt, double* out);  /* dynamics.py:344-348 */
+/* (new, diagnostics) the same median by the arguments the step's own call sites pass: transform 0 = x, 1 = max(0, -(x - tparam))
+ * (physics.py:296); site 0..3 keeps a window on the device between calls, site -1 has none.  qd_op_median_positive is the call
+ * with (0, 0.0, 0). */
+int qd_op_median_at(qd_handle h, const double* x, double dflt, int transform, double tparam, int site, double* out);
+/* (new, diagnostics) two medians through the step's pair chain (one set of three launches, two buffer sets): out2 = {median 0,
+ * median 1}.  Whole-globe handles, two different sites that both have a window already; anything else is refused. */
+int qd_op_median_pair(qd_handle h, const double* x0, double dflt0, int tr0, double tp0, int site0,
+                      const double* x1, double dflt1, int tr1, double tp1, int site1, double* out2);
 /* (new, diagnostics) the per-call-site state of the three in-step medians (dynamics.py:344-348, run_simulation.py:1740-1747,
  * 1866-1874): 4 sites x 16 doubles {last median, -, -, valid, hits, misses, candidates of the last call, positives of the last
  * call, bracket lo, hi, -, ok, calls, last miss: call, centre, result}; site 1 = P_cond, 2 = convergence, 3 = precipitation */

@@ -916,14 +916,41 @@ extern "C" int qd_op_gaussian(qd_handle c, const double* F, double sigma, int mo
     return seam_out(c, c->scratch[11], out);
 }
 
-extern "C" int qd_op_median_positive(qd_handle c, const double* x, double dflt, double* out) {
+// the median seam: every form of qd_reduce.hip's exact median by its own arguments (the step's call sites pass the same three)
+extern "C" int qd_op_median_at(qd_handle c, const double* x, double dflt, int transform, double tparam, int site, double* out) {
     if (!c || !x || !out) return -1;
+    if (transform != 0 && transform != 1) return qd_fail(c, "qd_op_median_at: transform is 0 (x) or 1 (max(0, -(x - tparam)))");
+    if (site < -1 || site >= 4) return qd_fail(c, "qd_op_median_at: site is -1 (no window) or 0..3");
     hipSetDevice(c->desc.device);
     if (seam_in(c, c->scratch[10], x)) return -1;
-    qd_median_positive_dev(c, c->scratch[10], dflt, QD_S_MED_OUT, 0, 0.0, 0);
+    if (qd_median_positive_dev(c, c->scratch[10], dflt, QD_S_MED_OUT, transform, tparam, site)) return -1;
     QD_HIP(c, hipMemcpyAsync(c->hpin, c->dscal + QD_S_MED_OUT, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     QD_HIP(c, hipStreamSynchronize(c->stream));
     *out = c->hpin[0];
+    return 0;
+}
+
+extern "C" int qd_op_median_positive(qd_handle c, const double* x, double dflt, double* out) {
+    return qd_op_median_at(c, x, dflt, 0, 0.0, 0, out);
+}
+
+// two medians through the pair chain (k_med_hist2 / k_med_scan_bracket2 / k_med_final2); refused where qd_median_pair_dev would
+// run two single calls instead
+extern "C" int qd_op_median_pair(qd_handle c, const double* x0, double dflt0, int tr0, double tp0, int site0,
+                                 const double* x1, double dflt1, int tr1, double tp1, int site1, double* out2) {
+    if (!c || !x0 || !x1 || !out2) return -1;
+    if (!c->geo.full) return qd_fail(c, "qd_op_median_pair: the pair chain runs on whole-globe handles only");
+    if ((tr0 != 0 && tr0 != 1) || (tr1 != 0 && tr1 != 1)) return qd_fail(c, "qd_op_median_pair: transform is 0 or 1");
+    if (site0 < 0 || site0 >= 4 || site1 < 0 || site1 >= 4) return qd_fail(c, "qd_op_median_pair: sites are 0..3");
+    if (site0 == site1) return qd_fail(c, "qd_op_median_pair: the two jobs need different sites");
+    if (!qd_median_pair_ready(c, site0, site1))
+        return qd_fail(c, "qd_op_median_pair: the pair chain is not ready (QD_MEDIAN_PREDICT=0, no second buffer set, or a site without a window yet)");
+    hipSetDevice(c->desc.device);
+    if (seam_in(c, c->scratch[10], x0) || seam_in(c, c->scratch[11], x1)) return -1;
+    if (qd_median_pair_dev(c, c->scratch[10], dflt0, QD_S_TMP0, tr0, tp0, site0, c->scratch[11], dflt1, QD_S_TMP1, tr1, tp1, site1)) return -1;
+    QD_HIP(c, hipMemcpyAsync(c->hpin, c->dscal + QD_S_TMP0, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    QD_HIP(c, hipStreamSynchronize(c->stream));
+    out2[0] = c->hpin[0]; out2[1] = c->hpin[1];
     return 0;
 }
 

@@ -987,7 +987,7 @@ __device__ __forceinline__ void qd_med_final_body(unsigned long long* st, const 
         // rank k1 + 1: v1 again when it is repeated beyond rank k1, else the smallest value above it.  s_rank is now the rank
         // of the target inside its run of equal values (0-based), so the run must be longer than s_rank + 1.
         unsigned int c_eq = 0;
-        double mn = DBL_MAX;
+        double mn = (double)INFINITY;                                    // +inf can be the upper middle itself
         for (size_t k = t; k < N; k += NT) {
             const double v = qd_med_src(cand, field, src, k, transform, tparam, cap);
             if (!(v > 0.0)) continue;
@@ -999,7 +999,7 @@ __device__ __forceinline__ void qd_med_final_body(unsigned long long* st, const 
         if (lane == 0) { s_cnt[wv] = c_eq; s_min[wv] = mn; }
         __syncthreads();
         if (t == 0) {
-            unsigned int ce = 0; double mm = DBL_MAX;
+            unsigned int ce = 0; double mm = (double)INFINITY;
             for (int k = 0; k < NT / 64; ++k) { ce += s_cnt[k]; mm = s_min[k] < mm ? s_min[k] : mm; }
             v2 = ((unsigned long long)ce > s_rank + 1ull) ? v1 : mm;
         }

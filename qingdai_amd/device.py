@@ -790,3 +790,21 @@ class Device:
 
     def op_median_positive(self, x, default):
         return self.call("qd_op_median_positive", x, default, OUT)
+
+    def op_median_at(self, x, default, transform=0, tparam=0.0, site=0):
+        """The exact median of the positives of x (transform 0) or of max(0, -(x - tparam)) (transform 1) at call site `site`
+        (0..3: keeps a window on the device; -1: none)."""
+        return self.call("qd_op_median_at", x, default, transform, tparam, site, OUT)
+
+    def op_median_pair(self, x0, default0, transform0, tparam0, site0, x1, default1, transform1, tparam1, site1):
+        """Two medians through the step's pair chain -> (median 0, median 1); refused unless both sites have a window."""
+        out = self.call("qd_op_median_pair", x0, default0, transform0, tparam0, site0, x1, default1, transform1, tparam1, site1, OUT(2))
+        return float(out[0]), float(out[1])
+
+    def median_state(self):
+        """qd_median_state as one dict per call site: the form report of the last median there.  `lo_bits` / `hi_bits` are the bit
+        patterns of the published bracket."""
+        st = np.ascontiguousarray(self.call("qd_median_state", OUT(64))).reshape(4, 16)
+        bits = st.view(np.uint64)
+        return [dict(centre=float(s[0]), valid=bool(s[3]), hits=int(s[4]), misses=int(s[5]), list_len=int(s[6]), count=int(s[7]),
+                     lo_bits=int(b[8]), hi_bits=int(b[9]), calls=int(s[12])) for s, b in zip(st, bits)]
