@@ -482,9 +482,13 @@ extern "C" int qd_hydronet_build(qd_handle c, int n_lat, int n_lon, const uint8_
                     return qd_fail(c, "qd_hydronet_build: non-finite elevation on a land cell or next to one");
         }
     }
+    // a workgroup has 160 KiB of LDS, and the kernel's static part (the scratch of __syncthreads_or's workgroup reduction)
+    // comes out of it: the runtime refuses a dynamic size beyond the rest
     const size_t lds = hn_pitfill_lds(n_lat, n_lon);
-    if (lds > 160 * 1024) return qd_fail(c, "qd_hydronet_build: n_lon too large for the pit fill's LDS rows");
     hipSetDevice(c->desc.device);
+    hipFuncAttributes fa;
+    QD_HIP(c, hipFuncGetAttributes(&fa, (const void*)k_hn_pitfill));
+    if (lds + fa.sharedSizeBytes > 160 * 1024) return qd_fail(c, "qd_hydronet_build: n_lon too large for the pit fill's LDS rows");
     if (lds > 64 * 1024)
         QD_HIP(c, hipFuncSetAttribute((const void*)k_hn_pitfill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int N = (int)cells;

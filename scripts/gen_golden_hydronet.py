@@ -2,9 +2,9 @@
 pit_fill, compute_flow_to_index, identify_lakes, compute_lake_outlets, topo_sort_flow_order).
 
 Needs a checkout of the reference project (default ../reference next to this repository, or --reference DIR); netCDF4 is not
-needed.  Each golden holds the case's inputs (land mask, eps, max_iters; the elevation itself only where qingdai_amd.topography
-does not regenerate it bit for bit), the reference's outputs (the filled elevation over land only: ocean cells are never
-changed), the number of pit-fill sweeps the reference ran, and the spherical_distance tables as the reference computes them
+needed.  Each golden holds the case's inputs (land mask, eps, max_iters; the elevation itself only where neither
+qingdai_amd.topography nor a builder of tests/hydronet_cases.py regenerates it bit for bit), the reference's outputs (the
+filled elevation over land only: ocean cells are never changed), the number of pit-fill sweeps the reference ran, and the spherical_distance tables as the reference computes them
 (scalar np.deg2rad / np.cos per cell pair).
 """
 import argparse
@@ -29,31 +29,6 @@ def ref_tables(grid):
             if 0 <= j + dj < n_lat:
                 cos_pair[j, k] = np.cos(0.5 * (np.deg2rad(grid.lat[j]) + np.deg2rad(grid.lat[j + dj])))
     return lat, lon, cos_pair
-
-
-def valley_field(n_lat, n_lon, seed):
-    """Land everywhere (both pole rows included) but an ocean blob; a seeded rough field, and a closed east-west valley
-    whose floor rises eastward by less than eps per cell: the in-row chain of the pit fill carries along the whole valley."""
-    rng = np.random.default_rng(seed)
-    land = np.ones((n_lat, n_lon), np.uint8)
-    jj, ii = np.meshgrid(np.arange(n_lat), np.arange(n_lon), indexing="ij")
-    land[((jj - n_lat // 4) ** 2 + ((ii - n_lon // 8) / 3.0) ** 2) < 9] = 0
-    elev = 500.0 + 200.0 * np.sin(jj / 3.0) * np.cos(ii / 7.0) + rng.normal(0.0, 30.0, (n_lat, n_lon))
-    j0, a, b = n_lat // 2, n_lon // 8, n_lon - n_lon // 8
-    elev[j0 - 1:j0 + 2, a - 1:b + 1] = 2000.0
-    elev[j0, a:b] = 10.0 + 1e-4 * np.arange(b - a)
-    return land, np.where(land == 1, elev, -100.0)
-
-
-def inland_field(n_lat, n_lon, seed):
-    """Mostly land, quantised elevation (flats and ties in D8 slopes and lake outlets): after a short fill the pits are lakes
-    that touch no ocean and drain through real outlets."""
-    rng = np.random.default_rng(seed)
-    land = np.ones((n_lat, n_lon), np.uint8)
-    land[:3, :] = 0
-    land[-2:, : n_lon // 3] = 0
-    elev = np.round(rng.uniform(0.0, 6.0, (n_lat, n_lon))) * 50.0
-    return land, np.where(land == 1, elev, 0.0)
 
 
 def run_case(ghm, grid_cls, name, n_lat, n_lon, land, elev, elev_src, max_iters, eps=1e-3):
@@ -102,11 +77,13 @@ def main():
         sys.exit(f"reference checkout not found at {ref}")
     sys.path.insert(0, ref)
     sys.path.insert(1, ROOT)
+    sys.path.insert(2, os.path.join(ROOT, "tests"))
     from pygcm.grid import SphericalGrid
     from pygcm import topography as rtopo
     from scripts import generate_hydrology_maps as ghm
     import qingdai_amd as qa
     from qingdai_amd import topography as qtopo
+    import hydronet_cases as hc
 
     def procedural(n_lat, n_lon):
         g = SphericalGrid(n_lat, n_lon)
@@ -123,10 +100,16 @@ def main():
         land, elev, src = procedural(n_lat, n_lon)
         for it in (200, 1, 3):
             run_case(ghm, SphericalGrid, f"proc_{n_lat}x{n_lon}_it{it}", n_lat, n_lon, land, elev, src, it)
-    land, elev = valley_field(25, 400, 5)
+    land, elev = hc.valley_field(25, 400, 5)
     run_case(ghm, SphericalGrid, "valley_25x400", 25, 400, land, elev, "stored", 40)
-    land, elev = inland_field(37, 72, 6)
+    land, elev = hc.inland_field(37, 72, 6)
     run_case(ghm, SphericalGrid, "inland_37x72", 37, 72, land, elev, "stored", 2)
+    # the hostile-terrain cases of tests/hydronet_cases.py: the builder regenerates the field, so none is stored
+    for name, build in hc.GOLDENED.items():
+        land, elev, eps, max_iters = build()
+        again = build()[1]
+        assert np.array_equal(elev.view(np.uint64), again.view(np.uint64))
+        run_case(ghm, SphericalGrid, name, *elev.shape, land, elev, f"case:{name}", max_iters, eps=eps)
 
 
 if __name__ == "__main__":

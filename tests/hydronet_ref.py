@@ -20,6 +20,10 @@ def case_inputs(z):
         elev = np.zeros((n_lat, n_lon))
     elif src == "procedural":
         elev = generate_elevation_map(qa.SphericalGrid(n_lat, n_lon), seed=42)
+    elif src.startswith("case:"):                      # a builder of tests/hydronet_cases.py regenerates the field
+        import hydronet_cases
+        land, elev, _, _ = hydronet_cases.GOLDENED[src[5:]]()
+        assert elev.shape == (n_lat, n_lon) and np.array_equal(land, z["land_mask"]), src
     else:
         elev = np.asarray(z["elevation"], dtype=float)
     return (n_lat, n_lon), np.asarray(z["land_mask"]), elev, float(z["eps"]), int(z["max_iters"])
