@@ -215,7 +215,9 @@ int qd_ocean_mean_next_count(qd_handle h, int64_t* out);
 /* (new, diagnostics) which form of the step kernels this handle takes: out[QD_SF_N].  The timing groups k_dyn_hyper / k_ocn_hyper are
  * shared by the row-streaming and the LDS-tile launchers and ocean_tail by three kernels; this says which.  Read-only, no launch, no
  * wait.  The geometry entries are what the launchers' own shape functions return for the handle's rows (margin 0); the QD_SF_LAST_*
- * entries are what the last atmosphere / ocean step noted where it decided (0 before the first step). */
+ * entries are what the last atmosphere / ocean step noted where it decided (0 before the first step); the QD_SF_CNT_* / QD_SF_MAX_*
+ * entries are host-side tallies since qd_create of the launch-by-launch decisions a latitude band makes (a band's margin shrinks from
+ * launch to launch, so the LAST_* notes keep only the last of several forms): written beside the notes, never read by a launch. */
 enum qd_step_form {
     QD_SF_DYN_STREAM,       /* momentum + del^4 of the atmosphere: 1 = k_dyn_stream, 0 = k_dyn_hyper<TR> (LDS tiles) */
     QD_SF_OCN_STREAM,       /* the same of the ocean sub-step: 1 = k_ocn_stream, 0 = k_ocn_hyper<TR> */
@@ -253,6 +255,26 @@ enum qd_step_form {
     QD_SF_LAST_TAIL_KERNEL, /*   last tail launch: 0 none, 1 k_ocn_tail_fast<false>, 2 k_ocn_tail_fast<true>, 3 k_ocn_tail_stream, 4 k_ocn_fused */
     QD_SF_LAST_DYN_FORM,    /* the last momentum launch of the atmosphere: 0 none (QD_FUSED=0), 1 streaming, 2 tiles */
     QD_SF_LAST_OCN_FORM,    /* the last momentum launch of the ocean: the same */
+    QD_SF_CNT_DYN_STREAM,   /* since qd_create: calls of qd_launch_dyn_hyper that took k_dyn_stream, */
+    QD_SF_CNT_DYN_TILE,     /*   that took k_dyn_hyper<TR>, */
+    QD_SF_CNT_OCN_STREAM,   /*   calls of qd_launch_ocn_hyper that took k_ocn_stream -- the interior and boundary launches of a split sub-step go
+                             *   past that launcher and are not among them; a split whose boundary is REDONE calls it and is counted, here or as a tile, */
+    QD_SF_CNT_OCN_TILE,     /*   that took k_ocn_hyper<TR>, */
+    QD_SF_CNT_SPLIT,        /*   ocean sub-steps whose interior rows were launched between the halo push and the unpack, */
+    QD_SF_CNT_SPLIT_REDO,   /*   of those, the ones whose boundary strips were too thin: the whole launch redone in the other form, */
+    QD_SF_CNT_STREAM_PAIR,  /*   k_ocn_stream_pair launches (the two boundary strips in one launch), */
+    QD_SF_CNT_STREAM_PUSH,  /*   k_ocn_stream_push launches (a row segment with the halo push in front), */
+    QD_SF_CNT_SUB_BAND_TAIL, /*  ocean sub-steps of a band on the band_tail path (one tail launch per row segment), */
+    QD_SF_CNT_SUB_ROUND2,   /*   ocean sub-steps of a band on the round-2 path (k_cont_sstadv + k_sst_outlier_fused), */
+    QD_SF_MAX_TAIL_SEGS,    /*   the most row segments a band tail ran on, */
+    QD_SF_MAX_MOM_SEGS,     /*   the most row segments a call of qd_launch_dyn_hyper / qd_launch_ocn_hyper ran on, */
+    QD_SF_CNT_TAIL_FIX,     /*   band tails that were handed the fix list (one segment, fix_now; the launcher still drops it when the kernel
+                             *   it picks has no finishing wave), */
+    QD_SF_CNT_DYN_TILE_FAST, /*  row tiles of the k_dyn_hyper launches that passed the kernel's own test for the FAST path (qd_fast_tile), */
+    QD_SF_CNT_OCN_TILE_FAST, /*  the same of k_ocn_hyper (qd_fast_tile and QD_OCN_WRAP_OK), */
+    QD_SF_CNT_TILE_EXACT,   /*   row tiles of either that did not (a segment shorter than the plane, an off-slab plane or pole row, QD_FUSED_FAST=0), */
+    QD_SF_CNT_TILE_SHIFT,   /*   FAST row tiles whose plane was shifted to stay on the segment +- 5 rows (p0 != o0 - 5), */
+    QD_SF_CNT_TILE_SLAB_EDGE, /* FAST row tiles whose plane ends on the last row of the slab (qd_lrow(p0) + RA == lrows) */
     QD_SF_N
 };
 int qd_step_forms(qd_handle h, int32_t* out);

@@ -65,10 +65,18 @@ def preferred_halo(n_lat, world, dt=300.0):
 class BandGroup:
     """N band handles of one grid in one process (threads); test vehicle for the band logic."""
 
-    def __init__(self, grid, world, params: QdParams | None = None, halo=None, device=0):
+    def __init__(self, grid, world, params: QdParams | None = None, halo=None, device=0, ranges=None):
+        """ranges: [(row0, n_rows)] per band instead of the even split -- contiguous, south to north, covering 0..n_lat."""
         self.grid = grid
         self.world = int(world)
-        self.ranges = band_ranges(grid.n_lat, world)
+        if ranges is None:
+            self.ranges = band_ranges(grid.n_lat, world)
+        else:
+            self.ranges = [(int(r0), int(n)) for r0, n in ranges]
+            ends = [0] + [r0 + n for r0, n in self.ranges]
+            if len(self.ranges) != self.world or any(n < 1 for _, n in self.ranges) or ends[-1] != grid.n_lat or \
+                    any(r0 != e for (r0, _), e in zip(self.ranges, ends)):
+                raise ValueError(f"BandGroup: ranges {self.ranges} are not {self.world} contiguous bands covering 0..{grid.n_lat}")
         self.halo = int(halo if halo is not None else required_halo(grid.n_lat))
         p = params or QdParams.from_env()
         self.devs = []

@@ -817,6 +817,21 @@ static void qd_tile_init(qd_ctx* c) {
     c->tile = qd_tile_of(c);
 }
 
+// qd_step_forms tallies (host ints, never read by a launch): the kernels' own test for the FAST path, asked on the host for every row tile
+// of the segment that is about to be launched
+template <int TR> static void tile_fast_tally(qd_ctx* c, const QdGeom& G, bool fast, bool ocean) {
+    for (int i0 = G.row0; i0 < G.row0 + G.nrows; i0 += TR) {
+        bool ok = false;
+        if constexpr (QdFast<TR>::ok) {
+            const QdFastTile t = qd_fast_tile<TR>(G, i0);
+            ok = fast && t.fits && (!ocean || QD_OCN_WRAP_OK(G, t));
+            if (ok && t.p0 != i0 - 5) c->form_count(QD_SF_CNT_TILE_SHIFT);
+            if (ok && qd_lrow(G, t.p0) + TR + 10 == G.lrows()) c->form_count(QD_SF_CNT_TILE_SLAB_EDGE);
+        }
+        c->form_count(!ok ? QD_SF_CNT_TILE_EXACT : ocean ? QD_SF_CNT_OCN_TILE_FAST : QD_SF_CNT_DYN_TILE_FAST);
+    }
+}
+
 // one launch per row segment (a whole-globe handle has one; a polar band computing its wrap rows has two)
 template <int TR> static void launch_dyn(qd_ctx* c, const QdDynArgs& P, int margin) {
     // the dynamic-LDS cap is a property of the (kernel, DEVICE) pair: one flag per device, not per process
@@ -824,7 +839,7 @@ template <int TR> static void launch_dyn(qd_ctx* c, const QdDynArgs& P, int marg
     const int dv = c->desc.device >= 0 && c->desc.device < QD_MAX_DEVICES ? c->desc.device : 0;
     if (!once[dv]) { hipFuncSetAttribute((const void*)k_dyn_hyper<TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QdPl<TR>::lds_bytes); once[dv] = c->desc.device == dv; }
     QdDynArgs Q = P;
-    QD_ROWS(c, margin, G, Q.ts.ntr = (G.nrows + TR - 1) / TR; hipLaunchKernelGGL(k_dyn_hyper<TR>, dim3(Q.ts.ntr * Q.ts.ntc), dim3(QD_FBLOCK),
+    QD_ROWS(c, margin, G, Q.ts.ntr = (G.nrows + TR - 1) / TR; tile_fast_tally<TR>(c, G, Q.fast, false); hipLaunchKernelGGL(k_dyn_hyper<TR>, dim3(Q.ts.ntr * Q.ts.ntc), dim3(QD_FBLOCK),
                                              QdPl<TR>::lds_bytes, c->stream, G, c->tabs, Q));
 }
 template <int TR> static void launch_ocn(qd_ctx* c, const QdOcnArgs& P, int margin) {
@@ -832,7 +847,7 @@ template <int TR> static void launch_ocn(qd_ctx* c, const QdOcnArgs& P, int marg
     const int dv = c->desc.device >= 0 && c->desc.device < QD_MAX_DEVICES ? c->desc.device : 0;
     if (!once[dv]) { hipFuncSetAttribute((const void*)k_ocn_hyper<TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QdPl<TR>::lds_bytes); once[dv] = c->desc.device == dv; }
     QdOcnArgs Q = P;
-    QD_ROWS(c, margin, G, Q.ts.ntr = (G.nrows + TR - 1) / TR; hipLaunchKernelGGL(k_ocn_hyper<TR>, dim3(Q.ts.ntr * Q.ts.ntc), dim3(QD_FBLOCK),
+    QD_ROWS(c, margin, G, Q.ts.ntr = (G.nrows + TR - 1) / TR; tile_fast_tally<TR>(c, G, Q.fast, true); hipLaunchKernelGGL(k_ocn_hyper<TR>, dim3(Q.ts.ntr * Q.ts.ntc), dim3(QD_FBLOCK),
                                              QdPl<TR>::lds_bytes, c->stream, G, c->tabs, Q));
 }
 
@@ -846,6 +861,7 @@ template <int TR> static void launch_ocn(qd_ctx* c, const QdOcnArgs& P, int marg
 int qd_launch_dyn_hyper(qd_ctx* c, QdDynArgs& P, int margin) {
     const bool stream = qd_stream_ok(c, margin);
     c->form_note(QD_SF_LAST_DYN_FORM, stream ? 1 : 2);
+    c->form_count(stream ? QD_SF_CNT_DYN_STREAM : QD_SF_CNT_DYN_TILE); c->form_max(QD_SF_MAX_MOM_SEGS, qd_segments(c, margin).n);
     if (stream) return qd_launch_dyn_stream(c, P, margin);
     qd_tile_init(c);
     P.ts = c->tile;
@@ -859,6 +875,7 @@ int qd_launch_dyn_hyper(qd_ctx* c, QdDynArgs& P, int margin) {
 int qd_launch_ocn_hyper(qd_ctx* c, QdOcnArgs& P, int margin) {
     const bool stream = qd_ocn_stream_ok(c, margin);
     c->form_note(QD_SF_LAST_OCN_FORM, stream ? 1 : 2);
+    c->form_count(stream ? QD_SF_CNT_OCN_STREAM : QD_SF_CNT_OCN_TILE); c->form_max(QD_SF_MAX_MOM_SEGS, qd_segments(c, margin).n);
     if (stream) return qd_launch_ocn_stream(c, P, margin);
     if (P.acc_read) return qd_fail(c, "k_ocn_hyper: an unfinished eta mean needs the streaming kernel");
     qd_tile_init(c);

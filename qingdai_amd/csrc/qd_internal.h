@@ -311,9 +311,12 @@ struct qd_ctx {
     int qs_wgs_per_cu[3] = {0, 0, 0};   // resident workgroups per CU of k_dyn_stream<false>, <true>, k_ocn_stream (occupancy query, cached)
     int cloud_eff_valid = 0;
     int last_nsub = 0;
-    // what the launchers of the last step chose (qd_step_forms, QD_SF_LAST_* of include/qingdai_hip.h): host-side notes, never read by a launch
+    // what the launchers of the last step chose and how often since qd_create (qd_step_forms, QD_SF_LAST_* / QD_SF_CNT_* / QD_SF_MAX_* of
+    // include/qingdai_hip.h): host-side notes, never read by a launch
     int form_last[QD_SF_N - QD_SF_LAST_NSUB] = {0};
     void form_note(int slot, int v) { form_last[slot - QD_SF_LAST_NSUB] = v; }
+    void form_count(int slot) { form_last[slot - QD_SF_LAST_NSUB] += 1; }                                   // QD_SF_CNT_*: since qd_create
+    void form_max(int slot, int v) { if (v > form_last[slot - QD_SF_LAST_NSUB]) form_last[slot - QD_SF_LAST_NSUB] = v; }   // QD_SF_MAX_*
     // host staging
     void* stage = nullptr; size_t stage_bytes = 0;
     // latitude bands: validity margin (rows beyond the owned band that hold current data) per slab

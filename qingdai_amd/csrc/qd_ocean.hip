@@ -1027,6 +1027,7 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
                 if (c->own_nrows + 2 * m_int >= 12 && qd_ocn_stream_ok_list(c, Si)) {
                     if (qd_launch_ocn_stream_list(c, O, Si)) return -1;
                     split = true;
+                    c->form_count(QD_SF_CNT_SPLIT);
                 }
                 if (qd_plan_end(c)) return -1;                // wait for both neighbours' rows, copy them into the halos
             }
@@ -1039,6 +1040,7 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
                 QdSegList Sb = qd_segments_rows(c, c->own_row0 - m, m - m_int);
                 Sb = qd_segments_rows(c, c->own_row0 + c->own_nrows + m_int, m - m_int, Sb);
                 if (!qd_ocn_stream_ok_list(c, Sb)) {          // boundary strips too thin for the streaming kernel: redo the whole launch (same values)
+                    c->form_count(QD_SF_CNT_SPLIT_REDO);
                     if (qd_launch_ocn_hyper(c, O, m)) return -1;
                 } else if (qd_launch_ocn_stream_list(c, O, Sb)) return -1;
             } else if (!split) {
@@ -1094,12 +1096,13 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
                 if (m < 0) return -1;
                 A.own0 = c->own_row0; A.own1 = c->own_row0 + c->own_nrows;
                 QdSegs S = qd_segments(c, m);
+                c->form_count(QD_SF_CNT_SUB_BAND_TAIL); c->form_max(QD_SF_MAX_TAIL_SEGS, S.n);
                 size_t off = 0;
                 // peer exchange: the finishing wave of the owned segment's launch all-reduces the band's share itself (no launch)
                 QdPeerFold pf;
                 const bool folded = qd_peer_fold_begin(c, &pf);
                 // one launch that covers the band and has the finishing wave: uo'' / vo'' in place through the fix list, like the whole globe
-                if (fix_now && S.n == 1) { A.fix_count = c->fix_count; A.fix_list = c->fix_list; }
+                if (fix_now && S.n == 1) { A.fix_count = c->fix_count; A.fix_list = c->fix_list; c->form_count(QD_SF_CNT_TAIL_FIX); }
                 for (int k = 0; k < S.n; ++k) {
                     const QdGeom& Gs = S.g[k];
                     const bool owned = Gs.row0 <= c->own_row0 && c->own_row0 < Gs.row0 + Gs.nrows;      // the segment that holds the band's own rows
@@ -1148,6 +1151,7 @@ int qd_ocean_step_impl(qd_ctx* c, double dt, int compute_qnet, int use_ice_mask,
             } else {
                 // halo segments first (their partials are zero-weighted), the owned rows' partials are summed below
                 QdSegs S = qd_segments(c, m);
+                c->form_count(QD_SF_CNT_SUB_ROUND2);
                 size_t off = 0;
                 for (int k = 0; k < S.n; ++k) {
                     hipLaunchKernelGGL(k_cont_sstadv, qd_grid2d(S.g[k]), blk, 0, c->stream, S.g[k], c->tabs, p.a, c->dlat, c->dlon,

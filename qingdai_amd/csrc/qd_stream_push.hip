@@ -63,6 +63,7 @@ k_ocn_stream_pair(QsOcnArgs A, QsSeg2 B) {
 void qd_launch_ocn_stream_pair(qd_ctx* c, const QsOcnArgs& A, const QdGeom& G2, int vb2, int nrs2, int ntc2) {
     QsSeg2 B{G2, vb2, nrs2, ntc2};
     hipLaunchKernelGGL(k_ocn_stream_pair, dim3(A.nrs * A.ntc + nrs2 * ntc2), dim3(192), 0, c->stream, A, B);
+    c->form_count(QD_SF_CNT_STREAM_PAIR);
 }
 
 // true: a deferred push was waiting and has gone out in front of the strips of A (A.nrs x A.ntc of them)
@@ -70,5 +71,6 @@ bool qd_launch_ocn_stream_push(qd_ctx* c, const QsOcnArgs& A) {
     QdPeerPush J;
     if (!qd_peer_take_job(c, &J)) return false;
     hipLaunchKernelGGL(k_ocn_stream_push, dim3(J.nbx * J.nby + A.nrs * A.ntc), dim3(192), 0, c->stream, A, J);
+    c->form_count(QD_SF_CNT_STREAM_PUSH);
     return true;
 }

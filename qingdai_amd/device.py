@@ -665,7 +665,8 @@ class Device:
 
     def step_forms(self):
         """Which form of the step kernels this handle takes and what the last step chose (include/qingdai_hip.h: qd_step_forms,
-        enum qd_step_form), by the enumerators' lower-case names: dyn_stream, ocn_ntc, tile_tr, tail_kernel, last_mean_form, ..."""
+        enum qd_step_form), by the enumerators' lower-case names: dyn_stream, ocn_ntc, tile_tr, tail_kernel, last_mean_form, ...;
+        cnt_* / max_*: tallies since the handle was created of the launch-by-launch decisions a latitude band makes"""
         out = self.call("qd_step_forms", OUT(_lib.C["QD_SF_N"]))
         return {k[len("QD_SF_"):].lower(): int(out[v]) for k, v in _lib.C.items() if k.startswith("QD_SF_") and k != "QD_SF_N"}
 

@@ -109,6 +109,22 @@ def test_field_ids_match_header():
     assert not re.search(r"\bflags\s*&\s*\d", step_n) and step_n.count("flags & QD_STEP_") == 10
 
 
+def test_step_form_tallies_close_the_enum():
+    """qd_step_forms: the tallies since qd_create (QD_SF_CNT_* / QD_SF_MAX_*) are the last enumerators before QD_SF_N, behind the
+    QD_SF_LAST_* notes -- the report's older entries keep their places -- and Device.step_forms names every entry from the header."""
+    from qingdai_amd import _lib
+    sf = sorted((v, k) for k, v in _lib.C.items() if k.startswith("QD_SF_"))
+    assert [v for v, _ in sf] == list(range(len(sf))) and sf[-1] == (_lib.C["QD_SF_N"], "QD_SF_N")
+    names = [k for _, k in sf[:-1]]
+    tallies = ["QD_SF_CNT_DYN_STREAM", "QD_SF_CNT_DYN_TILE", "QD_SF_CNT_OCN_STREAM", "QD_SF_CNT_OCN_TILE", "QD_SF_CNT_SPLIT", "QD_SF_CNT_SPLIT_REDO",
+               "QD_SF_CNT_STREAM_PAIR", "QD_SF_CNT_STREAM_PUSH", "QD_SF_CNT_SUB_BAND_TAIL", "QD_SF_CNT_SUB_ROUND2", "QD_SF_MAX_TAIL_SEGS",
+               "QD_SF_MAX_MOM_SEGS", "QD_SF_CNT_TAIL_FIX", "QD_SF_CNT_DYN_TILE_FAST", "QD_SF_CNT_OCN_TILE_FAST", "QD_SF_CNT_TILE_EXACT",
+               "QD_SF_CNT_TILE_SHIFT", "QD_SF_CNT_TILE_SLAB_EDGE"]
+    assert names[-len(tallies):] == tallies and names[-len(tallies) - 1] == "QD_SF_LAST_OCN_FORM"
+    assert _lib.C["QD_SF_DYN_STREAM"] == 0 and _lib.C["QD_SF_LAST_NSUB"] == 27 and _lib.C["QD_SF_CNT_DYN_STREAM"] == 36
+    assert not [k for k in names if k.startswith(("QD_SF_CNT_", "QD_SF_MAX_")) and k not in tallies]
+
+
 # ---------------------------------------------------------------- the reader, on small header texts
 _TYPES = '''
 #define QD_N 4
