@@ -858,6 +858,41 @@ int qd_spectra_sums_get(qd_handle h, double* sums, int64_t* count);  /* lat_reso
 int qd_spectra_sums_set(qd_handle h, const double* sums, int64_t count);   /* its inverse, for an exact resume (QD_CHECKPOINT) */
 int qd_spectra_reset(qd_handle h);                                   /* log and schedule forgotten, sums and count zeroed */
 
+/* ---- Lagrangian drifters (QD_DRIFTERS), whole-globe handles ----------------------------------------------------------------
+ * Nothing the reference has.  Two populations of particles, `atm` on (U, V) and `ocn` on (UO, VO), resident on the device as f64
+ * structures of arrays (r, c, status [, blocked]: row coordinate in [0, n_lat - 1], column coordinate in [0, n_lon - 1), 1 = dead,
+ * rejected moves onto land).  A span lane without a flag bit whose state MOVES: a schedule given before a qd_step_n span turns the
+ * lane on for that span, EVERY step of the span then advances every live particle by one midpoint step of the span's dt on the
+ * planes as the step leaves them (behind the step's last launch: what qd_download returns after a span that ends there), and a
+ * step whose schedule value is non-zero also leaves ONE record in the lane's log:
+ *     [atm: r | c | status | sample 0 | ...][ocn: r | c | status | blocked | sample 0 | ...]     each block n_pop doubles
+ * the samples being the bilinear values, at the particle's new position, of up to QD_DRIFT_MAX_SAMPLES f64 planes per population.
+ * One launch per advanced step, with or without a record; none while the lane is not scheduled.  The step itself -- index space,
+ * no transcendental on the device, fold at the poles, wrap at the seam, dead and blocked particles -- is stated at the top of
+ * csrc/qd_drift.hip and restated bit for bit by qingdai_amd/drifters.py: advance_reference.  When a sampled plane is one of the
+ * lazily stored diagnostics a recording step stores them.  A span with an ocn population needs the ocean step (bit0). */
+#define QD_DRIFT_MAX 1048576                             /* particles of one population */
+#define QD_DRIFT_MAX_SAMPLES 4                           /* sampled planes of one population */
+#define QD_DRIFT_LOG_MIB 256                             /* the log holds as many records as fit into this many MiB ... */
+#define QD_DRIFT_LOG_CAP_MAX 16                          /* ... at most this many and at least one */
+/* n_pop particles at (r_pop[i], c_pop[i]), status 0, blocked 0; ns_pop sampled planes (field ids); sec_row[n_lat]: the metric table
+ * 1 / max(cos lat_j, sin(dlat / 2)) of the zonal displacement.  *log_cap: the records the log holds between two drains,
+ * max(1, min(QD_DRIFT_LOG_CAP_MAX, floor(QD_DRIFT_LOG_MIB MiB / record bytes))).  Forgets an earlier configuration; n_atm == 0 &&
+ * n_ocn == 0 only releases.  Refused: latitude bands, a count below 0 or above QD_DRIFT_MAX, an initial coordinate that is
+ * non-finite or outside its interval, more than QD_DRIFT_MAX_SAMPLES planes, a sampled field that is not an f64 plane, PRECIP as a
+ * sampled plane (inside a span the hoisted precipitation block has overwritten it with the next step's before the lane reads). */
+int qd_drift_configure(qd_handle h, int n_atm, const double* r_atm, const double* c_atm, int n_ocn, const double* r_ocn,
+                       const double* c_ocn, int ns_atm, const int32_t* planes_atm, int ns_ocn, const int32_t* planes_ocn,
+                       const double* sec_row, int* log_cap);
+int qd_drift_schedule(qd_handle h, int steps, const int32_t* record);  /* the next qd_step_n span advances; non-zero = the step records */
+int qd_drift_advance(qd_handle h, double dt, int record);            /* class seam: one step now, outside a span (one launch) */
+int qd_drift_log(qd_handle h, double* out, int max, int* n);         /* drain: *n records of width doubles, oldest first */
+/* the particle state, for an exact resume: atm [3][n_atm] = r | c | status, ocn [4][n_ocn] = r | c | status | blocked; set refuses
+ * what configure refuses of a position, a status that is neither 0 nor 1 and a blocked count that is negative or non-finite */
+int qd_drift_state_get(qd_handle h, double* atm, double* ocn);
+int qd_drift_state_set(qd_handle h, const double* atm, const double* ocn);
+int qd_drift_reset(qd_handle h);                                     /* log and schedule forgotten; the particles stay */
+
 /* ---- state digest and exact resume (QD_CHECKPOINT), whole-globe handles ---------------------------------------------------
  * Nothing the reference has: its restart file holds 14 planes as f4 and a resumed run does not continue the run that was stopped.
  * qd_state_digest: a 64-bit digest of resident planes, all of them in ONE launch.  The digest of a plane of n elements is

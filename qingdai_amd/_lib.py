@@ -181,6 +181,8 @@ SERIES_STATS = C["QD_SERIES_STATS"]                  # mean, min, max, nan_count
 SPECTRA_MAX_ENTRIES = C["QD_SPECTRA_MAX_ENTRIES"]
 SPECTRA_LOG_CAP = C["QD_SPECTRA_LOG_CAP"]            # records the spectra lane's device log holds between two drains
 SPECTRA_STATS = C["QD_SPECTRA_STATS"]                # the count of non-finite rows behind an entry's n_bins powers
+DRIFT_MAX = C["QD_DRIFT_MAX"]                        # particles of one drifter population
+DRIFT_MAX_SAMPLES = C["QD_DRIFT_MAX_SAMPLES"]        # sampled planes of one drifter population
 STATE_DIGEST_MAX = C["QD_STATE_DIGEST_MAX"]          # refs per qd_state_digest call
 STATE_SCALARS_N = C["QD_STATE_SCALARS_N"]
 # enum qd_state_scalar: the slots of qd_state_scalars_get / set, by their lower-case names

@@ -15,6 +15,8 @@ The file (one NetCDF file through ncio.write_nc, f8 / u1 / i8 only; written to a
   spectra_records, spectra_times, spectra_steps, spectra_clock {i, records, count}, spectra_sums   an open spectra window continues
                       (QD_SPECTRA=1 only); the lat-resolved sum planes (QD_SPECTRA_LAT=1) are resident and digested as SPECTRA_SUMS
   qd_*                the ecology's own exact-resume variables (ecology.py: EcologyAdapter._extension_variables), not restated here
+  drift_atm, drift_ocn, drift_records, drift_times, drift_steps, drift_clock {i, records}   the drifters' particle state (r | c |
+                      status [| blocked], f8) and their open window (QD_DRIFTERS=1 only)
   atm_counter, ocn_counter, step_index, span_mark {step index, atm counter at the last span's end}, t_seconds, t_origin {t0, steps
   since, their dt}, diversity_next_day,
   phyto_clock {phyto_next_time, daily steps}, state_scalars (qd_state_scalars_get: cloud_eff_valid, the ecology sub-step's clock and
@@ -154,6 +156,9 @@ def subsystems(sim):
     spc = getattr(sim, "spectra", None)
     if spc is not None:                 # likewise the spectra lane's
         extra["spectra"] = f"{','.join(spc.names)}|every={int(spc.every)}|lat={int(spc.lat_resolved)}"
+    dri = getattr(sim, "drifters", None)
+    if dri is not None:                 # and the drifters'
+        extra["drifters"] = dri.key()
     return {**{"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
             "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
             "phyto_daily": str(int(sim.phyto_daily is not None)),
@@ -290,6 +295,20 @@ def collect(sim):
         if sums is not None:
             dims["spectra_entry"], dims["spectra_k"] = int(sums.shape[0]), int(sums.shape[2])
             v["spectra_sums"] = ("f8", ("spectra_entry", "lat", "spectra_k"), sums)
+    dri = getattr(sim, "drifters", None)
+    if dri is not None:                                        # the particles as they stand, and the open window's records so far
+        recs, times, steps = dri.window()
+        n = int(len(recs))
+        pad = max(n, 1)
+        dims["drift_time"], dims["drift_width"] = pad, max(1, int(dri.width))
+        v["drift_records"] = ("f8", ("drift_time", "drift_width"), np.concatenate([recs, np.zeros((pad - n, dri.width))]).reshape(pad, -1))
+        v["drift_times"] = ("f8", ("drift_time",), np.concatenate([times, np.zeros(pad - n)]))
+        v["drift_steps"] = ("f8", ("drift_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
+        v["drift_clock"] = ("f8", ("two",), np.array([float(dri.i), float(n)]))
+        for pop, state in dri.state().items():
+            if state.shape[1]:
+                dims[f"drift_{pop}_rows"], dims[f"drift_{pop}_n"] = int(state.shape[0]), int(state.shape[1])
+                v[f"drift_{pop}"] = ("f8", (f"drift_{pop}_rows", f"drift_{pop}_n"), state)
     if sim.eco is not None and sim.eco.pop is not None:
         xd, xv = sim.eco._extension_variables(sim.indiv)
         dims["species"] = int(sim.eco.pop.Ns)
@@ -413,6 +432,9 @@ def check_subsystems(f, sim):
     if got.get("spectra", "-") != want.get("spectra", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the spectra lane is '{got.get('spectra', '-')}' in the file and "
                                 f"'{want.get('spectra', '-')}' in this run")
+    if got.get("drifters", "-") != want.get("drifters", "-"):
+        raise CheckpointRefused(f"the subsystem set differs: the drifters lane is '{got.get('drifters', '-')}' in the file and "
+                                f"'{want.get('drifters', '-')}' in this run")
     for k in want:
         if got.get(k) != want[k]:
             if k == "history":
@@ -546,6 +568,15 @@ def load(sim, path, env=None, out=print):
         sim.spectra.restore_window(np.asarray(v["spectra_records"], dtype=np.float64)[:n], np.asarray(v["spectra_times"])[:n],
                                    np.asarray(v["spectra_steps"])[:n], int(clock[0]),
                                    sums=np.asarray(v["spectra_sums"], dtype=np.float64) if "spectra_sums" in v else None, count=int(clock[2]))
+    dri = getattr(sim, "drifters", None)
+    if dri is not None:
+        clock = np.asarray(v["drift_clock"], dtype=np.float64)
+        n = int(clock[1])
+        dri.restore_window(np.asarray(v["drift_records"], dtype=np.float64)[:n], np.asarray(v["drift_times"])[:n],
+                           np.asarray(v["drift_steps"])[:n], int(clock[0]))
+        dri.restore_state(np.asarray(v["drift_atm"], dtype=np.float64) if "drift_atm" in v else np.empty((3, 0)),
+                          np.asarray(v["drift_ocn"], dtype=np.float64) if "drift_ocn" in v else np.empty((4, 0)))
+        dev.drift_reset()
     # 3. counters, parameters, the host-side scalars (last: the uploads above set some of the flags they carry)
     dev.set_counters(int(f.scalar("atm_counter")), int(f.scalar("ocn_counter")))
     if autotune:

@@ -486,6 +486,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_history_release(c);
     qd_series_release(c);
     qd_spectra_release(c);
+    qd_drift_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -722,6 +723,11 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     const bool with_spectra = qd_spectra_scheduled(c);
     if (with_spectra && !(span.lane[QD_LANE_SPECTRA] = qd_spectra_span_begin(c, n))) return -1;
     const bool spectra_lazy = with_spectra && qd_spectra_reads_lazy(c);
+    // the drifters (qd_drift.hip) are the lane that moves: every step of a span it is scheduled for advances the particles (one launch
+    // behind the step's last), the schedule value says whether the step also records
+    const bool with_drift = qd_drift_scheduled(c);
+    if (with_drift && !(span.lane[QD_LANE_DRIFT] = qd_drift_span_begin(c, n, with_ocean))) return -1;
+    const bool drift_lazy = with_drift && qd_drift_reads_lazy(c);
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -736,6 +742,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (series_fire && (rc = qd_series_begin_step(c))) return rc;
         const bool spectra_fire = with_spectra && span.lane[QD_LANE_SPECTRA]->at(s) != 0.0;
         if (spectra_fire && (rc = qd_spectra_begin_step(c))) return rc;
+        const bool drift_rec = with_drift && span.lane[QD_LANE_DRIFT]->at(s) != 0.0;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
         if (with_pdaily && span.lane[QD_LANE_PHYTO_DAILY]->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
@@ -756,7 +763,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         const QdForcingCall fc{st, st + 3, st[6]};
         // lazy diagnostics: inside a span only the last step stores what nothing inside a span reads -- unless a reader comes with the flags
         c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag || bd_main || (hist_fire && hist_lazy) ||
-                         (series_fire && series_lazy) || (spectra_fire && spectra_lazy)) ? 1 : 0;
+                         (series_fire && series_lazy) || (spectra_fire && spectra_lazy) || (drift_rec && drift_lazy)) ? 1 : 0;
         if (with_phys) {
             const int part = c->precip_done ? 2 : 0;         // the precipitation block may have run inside the previous ocean step
             c->precip_done = 0;
@@ -812,6 +819,8 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (hist_fire && (rc = qd_history_accumulate(c, 1))) return rc;
         if (series_fire && (rc = qd_series_reduce(c, 1))) return rc;
         if (spectra_fire && (rc = qd_spectra_transform(c, 1))) return rc;
+        // drifters: U, V and the patched UO, VO as the step leaves them
+        if (with_drift && (rc = qd_drift_step(c, dt, drift_rec ? 1 : 0))) return rc;
     }
     c->diag_write = 1;
     return qd_launch_check(c, "qd_step_n");

@@ -27,6 +27,7 @@ class Device:
     _series_width = 0         # doubles per record of the last series_configure
     _spectra_n = 0            # entries of the last spectra_configure
     _spectra_lat = False      # ... and whether it keeps the lat-resolved sum planes
+    _drift = (0, 0, 0, 0)     # n_atm, n_ocn, record width and log capacity of the last drift_configure
     _tiles_n = 1              # tiles of the last tile configuration
     _div_shape = None         # [S, lat, lon] of the last eco_diversity call
 
@@ -134,7 +135,7 @@ class Device:
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
                ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None,
-               series=None, spectra=None):
+               series=None, spectra=None, drifters=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  The span lanes, each a participant on this handle whose records stay in its
         device log until the caller has it deliver them: `routing`, a RiverRouting -- bit7, after the hydrology commit (which it
@@ -145,7 +146,9 @@ class Device:
         the span.  `history`, a history.History -- no flag bit either: its window clock names the sampled steps, whose fields are
         added to the resident sums (history_read).  `series`, a series.Series -- no flag bit: its window clock names the sampled
         steps, each of which leaves one record of reduced fields in the lane's log (series_log).  `spectra`, a spectra.Spectra -- no flag bit:
-        likewise, one record of zonal wavenumber spectra per sampled step (spectra_log)."""
+        likewise, one record of zonal wavenumber spectra per sampled step (spectra_log).  `drifters`, a drifters.Drifters -- no flag bit, and the
+        one lane whose state moves: every step of the span advances the particles, its window clock names the steps that also leave a
+        record (drift_log)."""
         self.flush()
         st = _c(stars)
         assert st.ndim == 2 and st.shape[1] == 7
@@ -157,7 +160,7 @@ class Device:
         #   span_restore(clock)       nothing ran (an upload or qd_step_n raised): the clock back to what span_clock gave
         #   _fired(k)                 the span ran: k is what span_schedule returned
         #   span_deliver(dt)          drain the lane's device log and deliver it (print, keep); the caller's move, once per span
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra) if p is not None]
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters) if p is not None]
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -351,6 +354,59 @@ class Device:
 
     def spectra_reset(self):
         self.call("qd_spectra_reset")
+
+    # ---- Lagrangian drifters (qd_drift.hip)
+    def drift_configure(self, atm, ocn, sample_atm, sample_ocn, sec_row):
+        """atm, ocn: (r, c) index coordinates of the two populations' particles (r in [0, n_lat - 1], c in [0, n_lon - 1)), or None;
+        sample_atm, sample_ocn: up to DRIFT_MAX_SAMPLES field names each; sec_row [n_lat]: drifters.sec_table.  Two empty populations
+        release the lane.  -> the records the lane's log holds between two drains."""
+        pops = [(np.empty(0), np.empty(0)) if p is None else (_c(p[0]).reshape(-1), _c(p[1]).reshape(-1)) for p in (atm, ocn)]
+        for r, c in pops:
+            if r.shape != c.shape:
+                raise ValueError("drift_configure: a population holds one column coordinate per row coordinate")
+        n = [int(r.size) for r, _ in pops]
+        if sum(n) and (sec_row is None or np.size(sec_row) != self.shape[0]):
+            raise ValueError("drift_configure: sec_row holds one value per latitude row")
+        names = [list(s or []) if k else [] for s, k in zip((sample_atm, sample_ocn), n)]
+        cap = self.call("qd_drift_configure", n[0], pops[0][0], pops[0][1], n[1], pops[1][0], pops[1][1], len(names[0]),
+                        [F[x] for x in names[0]] or None, len(names[1]), [F[x] for x in names[1]] or None,
+                        None if sec_row is None else _c(sec_row).reshape(-1), OUT)
+        width = n[0] * (3 + len(names[0])) + n[1] * (4 + len(names[1]))
+        self._drift = (n[0], n[1], width, int(cap))
+        return int(cap)
+
+    def drift_schedule(self, record):
+        self.call("qd_drift_schedule", np.size(record), record)
+
+    def drift_advance(self, dt, record=False):
+        """One step of every live particle on the planes as they stand (the class seam); record: it also leaves a record."""
+        self.flush()
+        self.call("qd_drift_advance", dt, bool(record))
+
+    def drift_log(self, max_records=None):
+        """Drain the records -> [n][width], oldest first: [atm: r | c | status | samples][ocn: r | c | status | blocked | samples],
+        each block one double per particle."""
+        cap = max(1, self._drift[3])
+        room = cap if max_records is None else max(0, min(int(max_records), cap))
+        w = max(1, self._drift[2])
+        buf = np.empty(max(1, room) * w, dtype=np.float64)      # a record is large: no zero-filled ctypes buffer here
+        return self._records((buf, self.call("qd_drift_log", buf, room, OUT)), w)
+
+    def drift_state(self):
+        """-> (atm [3][n_atm] = r | c | status, ocn [4][n_ocn] = r | c | status | blocked) as the particles stand."""
+        atm, ocn = np.empty((3, self._drift[0])), np.empty((4, self._drift[1]))
+        self.call("qd_drift_state_get", atm if atm.size else None, ocn if ocn.size else None)
+        return atm, ocn
+
+    def drift_state_set(self, atm, ocn):
+        """The inverse of drift_state, for an exact resume."""
+        atm, ocn = _c(atm).reshape(3, -1), _c(ocn).reshape(4, -1)
+        if (atm.shape[1], ocn.shape[1]) != self._drift[:2]:
+            raise ValueError(f"drift_state_set: expected {self._drift[0]} atm and {self._drift[1]} ocn particles, got {atm.shape[1]} and {ocn.shape[1]}")
+        self.call("qd_drift_state_set", atm if atm.size else None, ocn if ocn.size else None)
+
+    def drift_reset(self):
+        self.call("qd_drift_reset")
 
     # ---- daily phytoplankton step (qd_phyto_daily.hip)
     def phyto_daily_configure(self, params, band_tab, species_tab, shape):

@@ -153,6 +153,15 @@ Not carried over (out of the hot path): plankton.json, plot
 called by its loop) and the diversity annotation of the ecology panel (run_simulation.py:1025-1052: it reads a name that is not
 in scope there and is never drawn).
 
+Lagrangian drifters (QD_DRIFTERS=1, default 0; nothing the reference has): QD_DRIFT_N_ATM particles on the winds and QD_DRIFT_N_OCN
+on the currents (default 4096 each, Fibonacci lattice seeds, the ocean's over ocean cells; none without the ocean) are advanced on the
+device on EVERY step, in index space, by an eighth span lane (qingdai_amd/drifters.py, qd_drift_*): one launch per step.  Every
+QD_DRIFT_EVERY-th (default 24) step of a window of QD_DRIFT_EVERY_DAYS (default 10) planet-days -- history's window clock -- also
+records positions, status, blocked counts and the values of QD_DRIFT_SAMPLE_ATM (default TS,H) / QD_DRIFT_SAMPLE_OCN (default SST) at
+the particles; a chunk ends with a window's last step or where the lane's device log is full, and behind a window
+<QD_OUTPUT_DIR>/drifters/drifters_day_{a}_{b}.nc is written and one [Drifters] line printed.  Under QD_CHECKPOINT=1 the particle
+state and the open window travel in the checkpoint.
+
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
   SpectralModel.time_step(Teq, dt) [no albedo argument, like the reference driver] -> ocean coupling ->
@@ -254,6 +263,7 @@ class Simulation:
     routing = budget = history = None      # enable_routing, enable_budget_diag (QD_BUDGET_DIAG=1), enable_history (QD_HISTORY=1)
     series = None                          # enable_series (QD_SERIES=1)
     spectra = None                         # enable_spectra (QD_SPECTRA=1)
+    drifters = None                        # enable_drifters (QD_DRIFTERS=1)
     truecolor = stateframe = figures = None
     plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
     _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
@@ -844,12 +854,15 @@ class Simulation:
         """n steps through _run_lanes; under QD_HISTORY=1 cut so that a chunk ends with a window's last step, behind which the
         window's file is written (the sums then start the next window from zero); under QD_SERIES=1 likewise with its windows."""
         hist, ser, spc = self.history, self.series, getattr(self, "spectra", None)
+        dri = getattr(self, "drifters", None)
         while n > 0:
             k = n if hist is None else min(n, hist.steps_to_window_end())
             if ser is not None:
                 k = min(k, ser.steps_to_window_end())
             if spc is not None:
                 k = min(k, spc.steps_to_window_end())
+            if dri is not None:
+                k = min(k, dri.steps_to_window_end())              # (its window's end, or the step that fills its device log)
             self._run_lanes(k, energy_diag)
             n -= k
             if hist is not None and hist.window_closed():
@@ -858,6 +871,8 @@ class Simulation:
                 self.flush_series()
             if spc is not None and spc.window_closed():
                 self.flush_spectra()
+            if dri is not None and dri.window_closed():
+                self.flush_drifters()
 
     def flush_history(self, complete=1):
         """Write the history window that stands in the accumulators -> the path or None.  A failure is reported and the window is
@@ -874,6 +889,11 @@ class Simulation:
         reported and the window is dropped: output never stops the run."""
         return self._nonfatal(lambda: self.spectra.flush(complete=complete), "[Spectra] window skipped: {}", cleanup=self.spectra.drop)
 
+    def flush_drifters(self, complete=1):
+        """Write the drifter window that stands on the host -> the path or None.  A failure is reported and the window is dropped:
+        output never stops the run."""
+        return self._nonfatal(lambda: self.drifters.flush(complete=complete), "[Drifters] window skipped: {}", cleanup=self.drifters.drop)
+
     def _run_lanes(self, n, energy_diag=False):
         """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
         individuals')."""
@@ -885,7 +905,8 @@ class Simulation:
             self.budget.routed = self.routing is not None
         lanes = {k: p for k, p in (("phyto_daily", self.phyto_daily), ("routing", self.routing), ("budget", self.budget),
                                    ("eco_daily", eco_daily), ("history", self.history), ("series", self.series),
-                                   ("spectra", getattr(self, "spectra", None))) if p is not None}
+                                   ("spectra", getattr(self, "spectra", None)),
+                                   ("drifters", getattr(self, "drifters", None))) if p is not None}
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
         # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
@@ -959,6 +980,14 @@ class Simulation:
         self.spectra = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
                                 dt=float(self.dt), day=self.day_seconds)
         return self.spectra
+
+    def enable_drifters(self, env=None):
+        """QD_DRIFTERS=1: Lagrangian drifters on the winds and the currents, advanced by a device lane on every step and written per
+        window to <QD_OUTPUT_DIR>/drifters/ (qingdai_amd/drifters.py) -> the Drifters or None.  The run-local step index the
+        windows count on starts where this is called.  An unknown sampled field raises here, before the loop."""
+        from .drifters import from_env
+        self.drifters = from_env(self, os.environ if env is None else env)
+        return self.drifters
 
     def enable_routing(self, env=None):
         """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
@@ -1227,6 +1256,8 @@ def main(argv=None):
         sim.enable_series(env)
     if getattr(sim, "enable_spectra", None) is not None:       # (likewise)
         sim.enable_spectra(env)
+    if getattr(sim, "enable_drifters", None) is not None:      # (likewise)
+        sim.enable_drifters(env)
     if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
         try:
             sim.load_checkpoint(ck_file, env)
@@ -1314,6 +1345,8 @@ def main(argv=None):
         sim.flush_series(complete=0)                           # likewise the open series window
     if getattr(sim, "spectra", None) is not None and not (ck["enabled"] and autosave_on):
         sim.flush_spectra(complete=0)                          # and the open spectra window
+    if getattr(sim, "drifters", None) is not None and not (ck["enabled"] and autosave_on):
+        sim.flush_drifters(complete=0)                         # and the open drifter window
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")
