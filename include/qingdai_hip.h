@@ -893,6 +893,45 @@ int qd_drift_state_get(qd_handle h, double* atm, double* ocn);
 int qd_drift_state_set(qd_handle h, const double* atm, const double* ocn);
 int qd_drift_reset(qd_handle h);                                     /* log and schedule forgotten; the particles stay */
 
+/* ---- streamfunction and velocity potential (QD_FLOW), whole-globe handles ------------------------------------------------
+ * Nothing the reference has (it defines vorticity and divergence and stops there).  A span lane without a flag bit and with a
+ * device log, like the spectra: on every sampled step the resident (U, V) give
+ *     zeta, delta   SphericalGrid.vorticity / .divergence on the rows 1 .. n_lat - 2, bit for bit; on the two pole rows the
+ *                   circulation and the outflow of the polar cap of radius dlat / 2, constant along the row
+ *     psi, chi      the solutions of L psi = zeta - mean(zeta), L chi = delta - mean(delta) with the finite-volume Laplacian L
+ *                   stated in qingdai_amd/flow.py (helmholtz_reference, the definition), both of weighted mean zero: a row FFT,
+ *                   one tridiagonal solve in latitude per zonal wavenumber (two prefix sums for wavenumber 0), an inverse row FFT
+ * and ONE record of QD_FLOW_REC_W doubles (enum qd_flow_rec) in the lane's log, which holds QD_FLOW_LOG_CAP records between two
+ * drains; psi, chi, zeta, delta are added into four resident sum planes [4][n_lat][n_lon] (qd_flow_sums_get / _set).  A
+ * non-finite value anywhere in U or V makes psi and chi NaN in every cell, and the rows that hold one are counted.  Row lengths
+ * 2^a 3^b 5^c take the FFT form, every other length the direct form (QD_FLOW_FORM=direct in the environment of the configure
+ * call: the direct form everywhere).  Six launches on a sampled step, behind the step's last launch; none on any other step. */
+#define QD_FLOW_LOG_CAP 256                              /* records the flow log holds between two drains */
+#define QD_FLOW_TAB 6                                    /* rows of the grid table: flow.py: grid_tables */
+#define QD_FLOW_PLANES 4                                 /* the sum planes: psi, chi, zeta, delta */
+enum qd_flow_rec {
+    QD_FLOW_ZETA_MEAN = 0, QD_FLOW_DIV_MEAN, QD_FLOW_ZETA_RMS, QD_FLOW_DIV_RMS, QD_FLOW_ZETA_MAXABS, QD_FLOW_DIV_MAXABS,
+    QD_FLOW_PSI_MIN, QD_FLOW_PSI_MAX, QD_FLOW_CHI_MIN, QD_FLOW_CHI_MAX, QD_FLOW_KE, QD_FLOW_KE_ROT, QD_FLOW_KE_DIV, QD_FLOW_BAD,
+    QD_FLOW_REC_W
+};
+/* tab [QD_FLOW_TAB][n_lat], lam [n_lon / 2 + 1], geom [3] = {a, dlat, dlon}: the grid quantities of the discrete system as
+ * flow.grid_tables forms them (the host is their one source).  Allocates the log, the twiddle table, the work and the sum planes;
+ * forgets an earlier configuration; tab == NULL only releases.  Refused: latitude bands, a row whose working set does not fit the
+ * LDS a workgroup may take. */
+int qd_flow_configure(qd_handle h, const double* tab, const double* lam, const double* geom);
+int qd_flow_schedule(qd_handle h, int steps, const int32_t* sample);   /* the next qd_step_n span: non-zero = the step is sampled */
+int qd_flow_sample(qd_handle h);                                     /* class seam: one record now from the resident U, V, outside a span */
+int qd_flow_log(qd_handle h, double* out, int max, int* n);          /* drain: *n records of QD_FLOW_REC_W doubles, oldest first */
+int qd_flow_sums_get(qd_handle h, double* sums, int64_t* count);     /* the sums [QD_FLOW_PLANES][n_lat][n_lon] and the samples in them */
+int qd_flow_sums_set(qd_handle h, const double* sums, int64_t count);   /* its inverse, for an exact resume (QD_CHECKPOINT) */
+int qd_flow_reset(qd_handle h);                                      /* log and schedule forgotten, sums and count zeroed */
+/* class seam on host planes [n_lat][n_lon], outside a span: the kernels of a sample on (u, v) instead of the resident winds; the
+ * record goes to the log, the sums and their count stay as they are */
+int qd_flow_solve(qd_handle h, const double* u, const double* v, double* zeta, double* delta, double* psi, double* chi);
+/* the same kernels without a handle, on a grid of any n_lat >= 3, n_lon >= 4 (qd_create needs five rows): rec [QD_FLOW_REC_W] */
+int qd_flow_solve_grid(int n_lat, int n_lon, int device, const double* tab, const double* lam, const double* geom, const double* u,
+                       const double* v, double* zeta, double* delta, double* psi, double* chi, double* rec);
+
 /* ---- state digest and exact resume (QD_CHECKPOINT), whole-globe handles ---------------------------------------------------
  * Nothing the reference has: its restart file holds 14 planes as f4 and a resumed run does not continue the run that was stopped.
  * qd_state_digest: a 64-bit digest of resident planes, all of them in ONE launch.  The digest of a plane of n elements is
@@ -913,6 +952,7 @@ enum qd_state_ref {
 #define QD_STATE_REF_TRACERS 64                         /* index range of QD_SR_PHYTO_TRACER */
 #define QD_STATE_REF_HISTORY_SUMS QD_HISTORY_MAX_ENTRIES   /* index range of QD_SR_HISTORY_SUM */
 #define QD_STATE_REF_SPECTRA_SUMS 500                   /* one more ref: the lat-resolved sums of the spectra lane, [n][n_lat][n_bins] as ONE plane */
+#define QD_STATE_REF_FLOW_SUMS 501                      /* and the sum planes of the flow lane, [QD_FLOW_PLANES][n_lat][n_lon] as ONE plane */
 #define QD_STATE_DIGEST_MAX 64
 /* n <= 64 refs -> out[n].  Refused: latitude bands, an unknown ref, a ref whose subsystem is not configured (the line names it). */
 int qd_state_digest(qd_handle h, int n, const int32_t* refs, uint64_t* out);

@@ -15,6 +15,8 @@ The file (one NetCDF file through ncio.write_nc, f8 / u1 / i8 only; written to a
   spectra_records, spectra_times, spectra_steps, spectra_clock {i, records, count}, spectra_sums   an open spectra window continues
                       (QD_SPECTRA=1 only); the lat-resolved sum planes (QD_SPECTRA_LAT=1) are resident and digested as SPECTRA_SUMS
   qd_*                the ecology's own exact-resume variables (ecology.py: EcologyAdapter._extension_variables), not restated here
+  flow_records, flow_times, flow_steps, flow_clock {i, records, count}, flow_sums   an open flow window continues (QD_FLOW=1 only);
+                      the four sum planes are resident and digested as FLOW_SUMS
   drift_atm, drift_ocn, drift_records, drift_times, drift_steps, drift_clock {i, records}   the drifters' particle state (r | c |
                       status [| blocked], f8) and their open window (QD_DRIFTERS=1 only)
   atm_counter, ocn_counter, step_index, span_mark {step index, atm counter at the last span's end}, t_seconds, t_origin {t0, steps
@@ -159,6 +161,9 @@ def subsystems(sim):
     dri = getattr(sim, "drifters", None)
     if dri is not None:                 # and the drifters'
         extra["drifters"] = dri.key()
+    flw = getattr(sim, "flow", None)
+    if flw is not None:                 # and the flow lane's
+        extra["flow"] = f"every={int(flw.every)}"
     return {**{"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
             "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
             "phyto_daily": str(int(sim.phyto_daily is not None)),
@@ -184,6 +189,8 @@ def plane_names(sim):
     spc = getattr(sim, "spectra", None)
     if spc is not None and spc.lat_resolved:
         names.append("SPECTRA_SUMS")
+    if getattr(sim, "flow", None) is not None:
+        names.append("FLOW_SUMS")
     return names
 
 
@@ -295,6 +302,18 @@ def collect(sim):
         if sums is not None:
             dims["spectra_entry"], dims["spectra_k"] = int(sums.shape[0]), int(sums.shape[2])
             v["spectra_sums"] = ("f8", ("spectra_entry", "lat", "spectra_k"), sums)
+    flw = getattr(sim, "flow", None)
+    if flw is not None:
+        recs, times, steps = flw.window()
+        n = int(len(recs))
+        pad = max(n, 1)
+        sums, count = flw.sums()
+        dims["flow_time"], dims["flow_width"], dims["flow_plane"] = pad, int(flw.width), int(sums.shape[0])
+        v["flow_records"] = ("f8", ("flow_time", "flow_width"), np.concatenate([recs, np.zeros((pad - n, flw.width))]))
+        v["flow_times"] = ("f8", ("flow_time",), np.concatenate([times, np.zeros(pad - n)]))
+        v["flow_steps"] = ("f8", ("flow_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
+        v["flow_clock"] = ("f8", ("three",), np.array([float(flw.i), float(n), float(count)]))
+        v["flow_sums"] = ("f8", ("flow_plane", "lat", "lon"), sums)
     dri = getattr(sim, "drifters", None)
     if dri is not None:                                        # the particles as they stand, and the open window's records so far
         recs, times, steps = dri.window()
@@ -381,7 +400,8 @@ class CheckpointFile:
         if key is not None:
             return np.asarray(v[key], dtype=np.float64)[int(idx)]
         key = {"ROUTE_BUFFER": "route_buffer", "ROUTE_FLOW": "route_flow", "ROUTE_LAKES": "route_lakes", "ECO_LAI_STACK": "qd_LAI_layers_SK",
-               "INDIV_E_DAY": "qd_indiv_E_day", "INDIV_STRESS": "qd_indiv_stress_days", "SPECTRA_SUMS": "spectra_sums"}[name]
+               "INDIV_E_DAY": "qd_indiv_E_day", "INDIV_STRESS": "qd_indiv_stress_days", "SPECTRA_SUMS": "spectra_sums",
+               "FLOW_SUMS": "flow_sums"}[name]
         return np.asarray(v[key], dtype=np.float64)
 
     def subsystems(self):
@@ -432,6 +452,9 @@ def check_subsystems(f, sim):
     if got.get("spectra", "-") != want.get("spectra", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the spectra lane is '{got.get('spectra', '-')}' in the file and "
                                 f"'{want.get('spectra', '-')}' in this run")
+    if got.get("flow", "-") != want.get("flow", "-"):
+        raise CheckpointRefused(f"the subsystem set differs: the flow lane is '{got.get('flow', '-')}' in the file and "
+                                f"'{want.get('flow', '-')}' in this run")
     if got.get("drifters", "-") != want.get("drifters", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the drifters lane is '{got.get('drifters', '-')}' in the file and "
                                 f"'{want.get('drifters', '-')}' in this run")
@@ -481,6 +504,8 @@ def _file_plane_names(f):
         names += [f"HISTORY_SUM:{k}" for k in range(np.shape(v["hist_sums"])[0])]
     if "spectra_sums" in v:
         names.append("SPECTRA_SUMS")
+    if "flow_sums" in v:
+        names.append("FLOW_SUMS")
     return names
 
 
@@ -568,6 +593,12 @@ def load(sim, path, env=None, out=print):
         sim.spectra.restore_window(np.asarray(v["spectra_records"], dtype=np.float64)[:n], np.asarray(v["spectra_times"])[:n],
                                    np.asarray(v["spectra_steps"])[:n], int(clock[0]),
                                    sums=np.asarray(v["spectra_sums"], dtype=np.float64) if "spectra_sums" in v else None, count=int(clock[2]))
+    if getattr(sim, "flow", None) is not None:
+        clock = np.asarray(v["flow_clock"], dtype=np.float64)
+        n = int(clock[1])
+        sim.flow.restore_window(np.asarray(v["flow_records"], dtype=np.float64)[:n], np.asarray(v["flow_times"])[:n],
+                                np.asarray(v["flow_steps"])[:n], int(clock[0]),
+                                sums=np.asarray(v["flow_sums"], dtype=np.float64), count=int(clock[2]))
     dri = getattr(sim, "drifters", None)
     if dri is not None:
         clock = np.asarray(v["drift_clock"], dtype=np.float64)

@@ -487,6 +487,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_series_release(c);
     qd_spectra_release(c);
     qd_drift_release(c);
+    qd_flow_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -728,6 +729,9 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     const bool with_drift = qd_drift_scheduled(c);
     if (with_drift && !(span.lane[QD_LANE_DRIFT] = qd_drift_span_begin(c, n, with_ocean))) return -1;
     const bool drift_lazy = with_drift && qd_drift_reads_lazy(c);
+    // the flow lane (qd_flow.hip): a sampled step solves for streamfunction and velocity potential from U, V as the step leaves them
+    const bool with_flow = qd_flow_scheduled(c);
+    if (with_flow && !(span.lane[QD_LANE_FLOW] = qd_flow_span_begin(c, n))) return -1;
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -821,6 +825,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (spectra_fire && (rc = qd_spectra_transform(c, 1))) return rc;
         // drifters: U, V and the patched UO, VO as the step leaves them
         if (with_drift && (rc = qd_drift_step(c, dt, drift_rec ? 1 : 0))) return rc;
+        if (with_flow && span.lane[QD_LANE_FLOW]->at(s) != 0.0 && (rc = qd_flow_step(c))) return rc;
     }
     c->diag_write = 1;
     return qd_launch_check(c, "qd_step_n");

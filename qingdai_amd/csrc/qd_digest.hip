@@ -72,7 +72,8 @@ static const char* dg_ref_name(int ref, char* buf, size_t nb) {
     else if (ref >= QD_SR_HISTORY_SUM && ref < QD_SR_HISTORY_SUM + QD_HISTORY_MAX_ENTRIES) snprintf(buf, nb, "HISTORY_SUM + %d", ref - QD_SR_HISTORY_SUM);
     else snprintf(buf, nb, "%s", ref == QD_SR_ROUTE_BUFFER ? "ROUTE_BUFFER" : ref == QD_SR_ROUTE_FLOW ? "ROUTE_FLOW" : ref == QD_SR_ROUTE_LAKES ? "ROUTE_LAKES" :
                                  ref == QD_SR_ECO_LAI_STACK ? "ECO_LAI_STACK" : ref == QD_SR_INDIV_E_DAY ? "INDIV_E_DAY" :
-                                 ref == QD_SR_INDIV_STRESS ? "INDIV_STRESS" : ref == QD_STATE_REF_SPECTRA_SUMS ? "SPECTRA_SUMS" : "?");
+                                 ref == QD_SR_INDIV_STRESS ? "INDIV_STRESS" : ref == QD_STATE_REF_SPECTRA_SUMS ? "SPECTRA_SUMS" :
+                                 ref == QD_STATE_REF_FLOW_SUMS ? "FLOW_SUMS" : "?");
     return buf;
 }
 
@@ -110,6 +111,10 @@ static int dg_resolve(qd_ctx* c, int ref, QdDigestEntry* e) {
     } else if (ref == QD_STATE_REF_SPECTRA_SUMS) {
         const double* sums;
         if (!qd_spectra_planes(c, &sums, &n)) { why = "the lat-resolved spectra sums are not configured (qd_spectra_configure)"; n = cells; }
+        else p = sums;
+    } else if (ref == QD_STATE_REF_FLOW_SUMS) {
+        const double* sums;
+        if (!qd_flow_planes(c, &sums, &n)) { why = "the flow lane is not configured (qd_flow_configure)"; n = cells; }
         else p = sums;
     } else {
         return qd_fail(c, ("qd_state_digest: unknown ref " + std::to_string(ref)).c_str());

@@ -215,6 +215,7 @@ struct qd_ctx {
     struct QdHistory* history = nullptr;     // time-mean history: entry table, sum planes, sample count, schedule (qd_history.hip)
     struct QdSeries* series = nullptr;       // per-step series: entry table, row weights, row results, record log, schedule (qd_series.hip)
     struct QdSpectra* spectra = nullptr;     // zonal spectra: entry table, twiddles, row powers, sum planes, record log, schedule (qd_spectra.hip)
+    struct QdFlow* flow = nullptr;           // streamfunction / velocity potential: tables, work and sum planes, record log, schedule (qd_flow.hip)
     struct QdDrift* drift = nullptr;         // Lagrangian drifters: particle state, metric table, record log, schedule (qd_drift.hip)
     unsigned long long* digest_out = nullptr; // [64] results of qd_state_digest, allocated at its first call (qd_digest.hip)
     double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
@@ -556,6 +557,12 @@ bool qd_drift_scheduled(const qd_ctx* c);
 bool qd_drift_reads_lazy(const qd_ctx* c);
 struct QdSpanLane* qd_drift_span_begin(qd_ctx* c, int n, int with_ocean);
 int  qd_drift_step(qd_ctx* c, double dt, int record);
+// qd_flow.hip: the spectra's protocol; sample is the six launches of a sampled step, behind the step's last launch
+void qd_flow_release(qd_ctx* c);
+bool qd_flow_scheduled(const qd_ctx* c);
+struct QdSpanLane* qd_flow_span_begin(qd_ctx* c, int n);
+int  qd_flow_step(qd_ctx* c);
+bool qd_flow_planes(const qd_ctx* c, const double** sums, size_t* n);         // the four sum planes as one plane (qd_state_digest)
 // what qd_state_digest and the exact resume (qd_digest.hip) need from the feature modules: their resident planes, and their firing
 // counts (set >= 0 stores it; -> the count as it then stands, 0 when the module is not configured)
 bool qd_route_planes(const qd_ctx* c, const double** buf, const double** flow, const double** lakes, int* n_lakes);    // qd_route.hip

@@ -39,6 +39,7 @@
 #include "qd_span.h"
 #include "qd_entry.h"
 #include "qd_blockred.h"
+#include "qd_rowfft.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -46,7 +47,6 @@
 
 #define QD_SPEC_NSTAT 1                 // the count of non-finite rows behind an entry's bins (include/qingdai_hip.h: QD_SPECTRA_STATS)
 #define QD_SPEC_LDS_LIMIT (150 * 1024)  // bytes of the CU's 160 KB LDS one workgroup may take here (k_zonal_filter's limit)
-#define QD_SPEC_MAX_PASSES 16
 #define QD_SPEC_CBINS 4                 // bins per k_spectra_combine workgroup
 #define QD_SPEC_CROUNDS 4               // rows per lane whose loads are in flight together
 static_assert(QD_SPECTRA_MAX_ENTRIES == QD_ENTRY_MAX, "the spectra table is the shared entry table");
@@ -55,61 +55,8 @@ static_assert(QD_BLOCK == 64 * QD_SPEC_CBINS, "k_spectra_combine: 64 lanes x QD_
 
 struct QdSpecEntry { const double* a; const double* b; int slot; int pad_; };          // b == nullptr: op 0; slot: the entry's place in the record
 struct QdSpecTab { QdSpecEntry e[QD_ENTRY_MAX]; int n; };
-struct QdSpecPlan { int m, step, even, nf; int r[QD_SPEC_MAX_PASSES]; };               // fft: length, table step n / m, n even, the passes
 
-#ifndef QD_SPEC_SKEW_SHIFT
-#define QD_SPEC_SKEW_SHIFT 5          // one 8-byte pad per 32 elements
-#endif
-#define QS_SK(i) ((i) + ((i) >> QD_SPEC_SKEW_SHIFT))
-
-struct qs_cx { double r, i; };
-__device__ __forceinline__ qs_cx qs_add(qs_cx a, qs_cx b) { return {a.r + b.r, a.i + b.i}; }
-__device__ __forceinline__ qs_cx qs_sub(qs_cx a, qs_cx b) { return {a.r - b.r, a.i - b.i}; }
-__device__ __forceinline__ qs_cx qs_mul(qs_cx a, qs_cx w) { return {a.r * w.r - a.i * w.i, a.r * w.i + a.i * w.r}; }
-__device__ __forceinline__ qs_cx qs_mji(qs_cx a) { return {a.i, -a.r}; }               // a * (-i)
-__device__ __forceinline__ qs_cx qs_scale(qs_cx a, double f) { return {a.r * f, a.i * f}; }
-__device__ __forceinline__ qs_cx qs_tw(const double* __restrict__ tw, int n, int idx) { return {tw[idx], -tw[n + idx]}; }   // exp(-2 pi i idx / n)
-__device__ __forceinline__ qs_cx qs_ld(const double* re, const double* im, int i) { const int k = QS_SK(i); return {re[k], im[k]}; }
-__device__ __forceinline__ void qs_st(double* re, double* im, int i, qs_cx v) { const int k = QS_SK(i); re[k] = v.r; im[k] = v.i; }
-
-// one Stockham pass of radix R over the whole sequence (every thread of the workgroup; the caller's barrier follows)
-template <int R>
-__device__ __forceinline__ void qs_pass(const double* sr, const double* si, double* dr, double* di, int m, int s, int step, int n,
-                                        const double* __restrict__ tw) {
-    const int nb = m / R;                                   // butterflies; the sub-length is L = m / s, L / R = nb / s
-    const bool last = nb == s;                              // L == R: p == 0 everywhere, every twiddle is 1
-    for (int b = threadIdx.x; b < nb; b += QD_BLOCK) {
-        const int p = b / s, q = b - p * s;
-        qs_cx a[R], y[R];
-#pragma unroll
-        for (int t = 0; t < R; ++t) a[t] = qs_ld(sr, si, b + t * nb);
-        if (R == 2) {
-            y[0] = qs_add(a[0], a[1]); y[1] = qs_sub(a[0], a[1]);
-        } else if (R == 4) {
-            const qs_cx t0 = qs_add(a[0], a[2]), t1 = qs_sub(a[0], a[2]), t2 = qs_add(a[1], a[3]), t3 = qs_mji(qs_sub(a[1], a[3]));
-            y[0] = qs_add(t0, t2); y[1] = qs_add(t1, t3); y[2] = qs_sub(t0, t2); y[3] = qs_sub(t1, t3);
-        } else if (R == 3) {
-            const double h = 0.86602540378443864676;        // sin(2 pi / 3)
-            const qs_cx sm = qs_add(a[1], a[2]), d = qs_scale(qs_mji(qs_sub(a[1], a[2])), h);
-            const qs_cx md = qs_sub(a[0], qs_scale(sm, 0.5));
-            y[0] = qs_add(a[0], sm); y[1] = qs_add(md, d); y[2] = qs_sub(md, d);
-        } else {
-            const double c1 = 0.30901699437494742410, c2 = -0.80901699437494742410;     // cos(2 pi / 5), cos(4 pi / 5)
-            const double s1 = 0.95105651629515357212, s2 = 0.58778525229247312917;      // sin(2 pi / 5), sin(4 pi / 5)
-            const qs_cx s14 = qs_add(a[1], a[4]), d14 = qs_sub(a[1], a[4]), s23 = qs_add(a[2], a[3]), d23 = qs_sub(a[2], a[3]);
-            const qs_cx m1 = qs_add(a[0], qs_add(qs_scale(s14, c1), qs_scale(s23, c2)));
-            const qs_cx m2 = qs_add(a[0], qs_add(qs_scale(s14, c2), qs_scale(s23, c1)));
-            const qs_cx n1 = qs_mji(qs_add(qs_scale(d14, s1), qs_scale(d23, s2)));
-            const qs_cx n2 = qs_mji(qs_sub(qs_scale(d14, s2), qs_scale(d23, s1)));
-            y[0] = qs_add(a[0], qs_add(s14, s23));
-            y[1] = qs_add(m1, n1); y[4] = qs_sub(m1, n1); y[2] = qs_add(m2, n2); y[3] = qs_sub(m2, n2);
-        }
-        const int o = q + s * R * p, base = p * s * step;   // u base < m step = n: no wrap
-        qs_st(dr, di, o, y[0]);
-#pragma unroll
-        for (int u = 1; u < R; ++u) qs_st(dr, di, o + s * u, last ? y[u] : qs_mul(y[u], qs_tw(tw, n, u * base)));
-    }
-}
+// qs_cx, QS_SK, qs_ld / qs_st, qs_pass and QdSpecPlan: qd_rowfft.h, shared with the flow lane
 
 // FORM 0: fft, 1: direct.  Dynamic LDS: one flag word of 8 bytes, then the form's arrays.
 template <int FORM>
@@ -289,17 +236,11 @@ void qd_spectra_release(qd_ctx* c) {
     c->spectra = nullptr;
 }
 
-// n = 2^a 3^b 5^c -> the radix list of the length-m transform (4s first), or false
+// n = 2^a 3^b 5^c -> the radix list of the length-m transform (qd_rowfft.h), or false
 static bool spectra_plan(int n, QdSpecPlan& F) {
     F = QdSpecPlan{};
     F.even = (n % 2 == 0) ? 1 : 0;
-    F.m = F.even ? n / 2 : n;
-    F.step = F.even ? 2 : 1;
-    int m = F.m;
-    const int radix[] = {4, 2, 3, 5};
-    for (int r : radix)
-        while (m % r == 0) { if (F.nf == QD_SPEC_MAX_PASSES) return false; F.r[F.nf++] = r; m /= r; }
-    return m == 1;
+    return qd_rowfft_plan(F.even ? n / 2 : n, F.even ? 2 : 1, F);
 }
 
 extern "C" int qd_spectra_configure(qd_handle c, int n, const int32_t* op, const int32_t* a, const int32_t* b, int lat_resolved, const double* w_row) {
@@ -324,11 +265,7 @@ extern "C" int qd_spectra_configure(qd_handle c, int n, const int32_t* op, const
     s->nbins = nlon / 2 + 1;
     s->lane.width = n * (s->nbins + QD_SPEC_NSTAT);
     s->lane.cap = QD_SPECTRA_LOG_CAP;
-    std::vector<double> tw(2 * (size_t)nlon);
-    for (int k = 0; k < nlon; ++k) {
-        const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)nlon;
-        tw[k] = (double)cosl(ang); tw[nlon + k] = (double)sinl(ang);
-    }
+    const std::vector<double> tw = qd_rowfft_table(nlon);
     const size_t logb = s->lane.log_doubles() * sizeof(double), planeb = s->plane_doubles(c) * sizeof(double),
                  badb = (size_t)n * nlat * sizeof(double), twb = tw.size() * sizeof(double);
     bool ok = hipMalloc(&s->tw, twb) == hipSuccess && hipMalloc(&s->wrow, (size_t)nlat * sizeof(double)) == hipSuccess &&

@@ -135,7 +135,7 @@ class Device:
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
                ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None,
-               series=None, spectra=None, drifters=None):
+               series=None, spectra=None, drifters=None, flow=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  The span lanes, each a participant on this handle whose records stay in its
         device log until the caller has it deliver them: `routing`, a RiverRouting -- bit7, after the hydrology commit (which it
@@ -148,7 +148,8 @@ class Device:
         steps, each of which leaves one record of reduced fields in the lane's log (series_log).  `spectra`, a spectra.Spectra -- no flag bit:
         likewise, one record of zonal wavenumber spectra per sampled step (spectra_log).  `drifters`, a drifters.Drifters -- no flag bit, and the
         one lane whose state moves: every step of the span advances the particles, its window clock names the steps that also leave a
-        record (drift_log)."""
+        record (drift_log).  `flow`, a flow.Flow -- no flag bit: one record of flow kinematics per sampled step (flow_log), and the
+        sampled psi, chi, zeta, delta in resident sum planes (flow_sums)."""
         self.flush()
         st = _c(stars)
         assert st.ndim == 2 and st.shape[1] == 7
@@ -160,7 +161,7 @@ class Device:
         #   span_restore(clock)       nothing ran (an upload or qd_step_n raised): the clock back to what span_clock gave
         #   _fired(k)                 the span ran: k is what span_schedule returned
         #   span_deliver(dt)          drain the lane's device log and deliver it (print, keep); the caller's move, once per span
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters) if p is not None]
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters, flow) if p is not None]
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -407,6 +408,58 @@ class Device:
 
     def drift_reset(self):
         self.call("qd_drift_reset")
+
+    # ---- streamfunction and velocity potential (qd_flow.hip)
+    def flow_configure(self, tables):
+        """tables: flow.grid_tables(grid, radius), the grid quantities of the discrete system; None releases the lane.
+        QD_FLOW_FORM=direct in the environment of this call forces the direct row transforms."""
+        if tables is None:
+            self.call("qd_flow_configure", None, None, None)
+        else:
+            if (tables.n_lat, tables.n_lon) != self.shape:
+                raise ValueError(f"flow_configure: the tables are for a {tables.n_lat} x {tables.n_lon} grid, the handle's is {self.shape}")
+            self.call("qd_flow_configure", tables.tab, tables.lam, tables.geom)
+        self._flow = tables is not None
+
+    def flow_schedule(self, sample):
+        self.call("qd_flow_schedule", np.size(sample), sample)
+
+    def flow_sample(self):
+        """One record from the resident U, V as they stand, added to the sum planes (the class seam)."""
+        self.flush()
+        self.call("qd_flow_sample")
+
+    def flow_log(self, max_records=None):
+        """Drain the records -> [n][QD_FLOW_REC_W] (flow.REC), oldest first.  max_records: what the caller knows to be queued at most."""
+        room = _lib.C["QD_FLOW_LOG_CAP"] if max_records is None else max(0, min(int(max_records), _lib.C["QD_FLOW_LOG_CAP"]))
+        w = _lib.C["QD_FLOW_REC_W"]
+        buf = np.empty(max(1, room) * w, dtype=np.float64)
+        return self._records((buf, self.call("qd_flow_log", buf, room, OUT)), w)
+
+    def flow_sums(self):
+        """-> (sums [4][n_lat][n_lon] of psi, chi, zeta, delta over the samples of the window, sample count)."""
+        out = np.empty((_lib.C["QD_FLOW_PLANES"],) + self.shape, dtype=np.float64)
+        return out, self.call("qd_flow_sums_get", out, OUT)
+
+    def flow_sums_set(self, sums, count):
+        """The inverse of flow_sums, for an exact resume."""
+        want = (_lib.C["QD_FLOW_PLANES"],) + self.shape
+        if np.shape(sums) != want:
+            raise ValueError(f"flow_sums_set: expected sums of shape {want}, got {np.shape(sums)}")
+        self.call("qd_flow_sums_set", _c(sums), count)
+
+    def flow_reset(self):
+        self.call("qd_flow_reset")
+
+    def flow_solve(self, u, v):
+        """The kernels of a sample on host planes (the class seam, outside any span) -> (zeta, delta, psi, chi); the record goes
+        to the log (flow_log), the sum planes stay as they are."""
+        u, v = (_c(x) for x in (u, v))
+        if u.shape != self.shape or v.shape != self.shape:
+            raise ValueError(f"flow_solve: u and v are planes of shape {self.shape}")
+        zeta, delta, psi, chi = (np.empty(self.shape, dtype=np.float64) for _ in range(4))
+        self.call("qd_flow_solve", u, v, zeta, delta, psi, chi)
+        return zeta, delta, psi, chi
 
     # ---- daily phytoplankton step (qd_phyto_daily.hip)
     def phyto_daily_configure(self, params, band_tab, species_tab, shape):
@@ -736,7 +789,7 @@ class Device:
     def digest(self, names):
         """The 64-bit digests of resident planes (include/qingdai_hip.h: qd_state_digest), one launch per 64 of them -> np.uint64[n].
         names: what _lib.state_ref takes -- field names, LAND_MASK, ICE_MASK, ROUTE_BUFFER, ROUTE_FLOW, ROUTE_LAKES, ECO_LAI_STACK,
-        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
+        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, FLOW_SUMS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
         self.flush()
         refs = [_lib.state_ref(n) for n in names]
         out = np.zeros(len(refs), dtype=np.uint64)

@@ -161,6 +161,14 @@ records positions, status, blocked counts and the values of QD_DRIFT_SAMPLE_ATM 
 the particles; a chunk ends with a window's last step or where the lane's device log is full, and behind a window
 <QD_OUTPUT_DIR>/drifters/drifters_day_{a}_{b}.nc is written and one [Drifters] line printed.  Under QD_CHECKPOINT=1 the particle
 state and the open window travel in the checkpoint.
+Flow kinematics (QD_FLOW=1, default 0; the reference defines vorticity and divergence and stops there): on every QD_FLOW_EVERY-th
+(default 24) step of a window of QD_FLOW_EVERY_DAYS (default 10) planet-days -- history's window clock -- the resident (U, V) give
+relative vorticity and divergence, and streamfunction and velocity potential by a Poisson solve on the device (row FFT, one
+tridiagonal solve in latitude per zonal wavenumber, inverse row FFT), by a ninth span lane (qingdai_amd/flow.py, qd_flow_*): six
+launches on a sampled step, one record of scalars in a device log, the four planes added into resident sum planes.  A chunk ends
+with a window's last step, behind which <QD_OUTPUT_DIR>/flow/flow_day_{a}_{b}.nc (psi_mean, chi_mean, vort_mean, div_mean [lat][lon],
+the scalar series [time], time_seconds, step, dt_seconds, sample_every, n_samples, complete) is written and one [Flow] line printed.
+The normal end of main writes the open window with complete = 0; under QD_CHECKPOINT=1 the checkpoint carries it instead.
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -264,6 +272,7 @@ class Simulation:
     series = None                          # enable_series (QD_SERIES=1)
     spectra = None                         # enable_spectra (QD_SPECTRA=1)
     drifters = None                        # enable_drifters (QD_DRIFTERS=1)
+    flow = None                            # enable_flow (QD_FLOW=1)
     truecolor = stateframe = figures = None
     plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
     _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
@@ -854,7 +863,7 @@ class Simulation:
         """n steps through _run_lanes; under QD_HISTORY=1 cut so that a chunk ends with a window's last step, behind which the
         window's file is written (the sums then start the next window from zero); under QD_SERIES=1 likewise with its windows."""
         hist, ser, spc = self.history, self.series, getattr(self, "spectra", None)
-        dri = getattr(self, "drifters", None)
+        dri, flw = getattr(self, "drifters", None), getattr(self, "flow", None)
         while n > 0:
             k = n if hist is None else min(n, hist.steps_to_window_end())
             if ser is not None:
@@ -863,8 +872,12 @@ class Simulation:
                 k = min(k, spc.steps_to_window_end())
             if dri is not None:
                 k = min(k, dri.steps_to_window_end())              # (its window's end, or the step that fills its device log)
+            if flw is not None:
+                k = min(k, flw.steps_to_window_end())
             self._run_lanes(k, energy_diag)
             n -= k
+            if flw is not None and flw.window_closed():
+                self.flush_flow()
             if hist is not None and hist.window_closed():
                 self.flush_history()
             if ser is not None and ser.window_closed():
@@ -894,6 +907,11 @@ class Simulation:
         output never stops the run."""
         return self._nonfatal(lambda: self.drifters.flush(complete=complete), "[Drifters] window skipped: {}", cleanup=self.drifters.drop)
 
+    def flush_flow(self, complete=1):
+        """Write the flow window that stands on the host (and in the device's sum planes) -> the path or None.  A failure is
+        reported and the window is dropped: output never stops the run."""
+        return self._nonfatal(lambda: self.flow.flush(complete=complete), "[Flow] window skipped: {}", cleanup=self.flow.drop)
+
     def _run_lanes(self, n, energy_diag=False):
         """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
         individuals')."""
@@ -906,7 +924,7 @@ class Simulation:
         lanes = {k: p for k, p in (("phyto_daily", self.phyto_daily), ("routing", self.routing), ("budget", self.budget),
                                    ("eco_daily", eco_daily), ("history", self.history), ("series", self.series),
                                    ("spectra", getattr(self, "spectra", None)),
-                                   ("drifters", getattr(self, "drifters", None))) if p is not None}
+                                   ("drifters", getattr(self, "drifters", None)), ("flow", getattr(self, "flow", None))) if p is not None}
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
         # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
@@ -980,6 +998,14 @@ class Simulation:
         self.spectra = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
                                 dt=float(self.dt), day=self.day_seconds)
         return self.spectra
+
+    def enable_flow(self, env=None):
+        """QD_FLOW=1: vorticity, divergence, streamfunction and velocity potential of the winds, solved by a device lane and written
+        per window to <QD_OUTPUT_DIR>/flow/ (qingdai_amd/flow.py) -> the Flow or None.  The run-local step index the windows count
+        on starts where this is called."""
+        from .flow import from_env
+        self.flow = from_env(self.dev, self.grid, os.environ if env is None else env, dt=float(self.dt), day=self.day_seconds)
+        return self.flow
 
     def enable_drifters(self, env=None):
         """QD_DRIFTERS=1: Lagrangian drifters on the winds and the currents, advanced by a device lane on every step and written per
@@ -1258,6 +1284,8 @@ def main(argv=None):
         sim.enable_spectra(env)
     if getattr(sim, "enable_drifters", None) is not None:      # (likewise)
         sim.enable_drifters(env)
+    if getattr(sim, "enable_flow", None) is not None:          # (likewise)
+        sim.enable_flow(env)
     if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
         try:
             sim.load_checkpoint(ck_file, env)
@@ -1347,6 +1375,8 @@ def main(argv=None):
         sim.flush_spectra(complete=0)                          # and the open spectra window
     if getattr(sim, "drifters", None) is not None and not (ck["enabled"] and autosave_on):
         sim.flush_drifters(complete=0)                         # and the open drifter window
+    if getattr(sim, "flow", None) is not None and not (ck["enabled"] and autosave_on):
+        sim.flush_flow(complete=0)                             # and the open flow window
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")
