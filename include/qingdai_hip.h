@@ -932,6 +932,48 @@ int qd_flow_solve(qd_handle h, const double* u, const double* v, double* zeta, d
 int qd_flow_solve_grid(int n_lat, int n_lon, int device, const double* tab, const double* lam, const double* geom, const double* u,
                        const double* v, double* zeta, double* delta, double* psi, double* chi, double* rec);
 
+/* ---- spherical-harmonic power spectra (QD_SPHARM), whole-globe handles ----------------------------------------------------
+ * Nothing the reference has.  A span lane without a flag bit and with a device log, like the spectra: on every sampled step each
+ * entry's plane is analysed into spherical-harmonic coefficients x_n^m, 0 <= m <= n <= N, N the triangular truncation
+ * min((n_lat - 1) / 2, (n_lon - 1) / 2), as qingdai_amd/spharm.py defines them (analyse_reference): a row transform (the row FFT
+ * of the spectra and flow lanes for n_lon = 2^a 3^b 5^c, direct sums otherwise or under QD_SPHARM_FORM=direct in the environment
+ * of the configure call), then per (entry, m) the Legendre recurrence in n fused with the Clenshaw-Curtis quadrature over the
+ * latitude rows, all f64 and in a fixed order.  An entry is a history entry (op 0: the f64 plane a; op 1: sqrt(a*a + b*b)) or one
+ * of this lane's own: QD_SPHARM_OP_VORT / _DIV, the flow lane's relative vorticity and divergence of the resident (U, V), produced
+ * by the flow lane's kernel (qd_flow_configure is not needed).  The entries' results, in configure order, are ONE record of
+ * n * (N + 1 + QD_SPHARM_STATS) doubles -- per entry P(0 .. N), P(n) = sum_m c_m |x_n^m|^2, then the mean square (1/2) sum_j w_j
+ * mean_i x^2 and the count of rows that hold a non-finite value (one of those makes every coefficient and every bin of the entry
+ * NaN) -- in the lane's log, which holds QD_SPHARM_LOG_CAP records between two drains.  With two_d the terms c_m |x_n^m|^2 are also
+ * added into resident sum planes [entry][N + 1 (n)][N + 1 (m)] (qd_spharm_sums_get / _set).  Sampling places are history's: the
+ * entries that read PRECIP in front of the ocean step, every other entry behind the step's last launch. */
+#define QD_SPHARM_LOG_CAP 256                            /* records the lane's log holds between two drains */
+#define QD_SPHARM_MAX_ENTRIES 32                         /* entries of one configuration */
+#define QD_SPHARM_STATS 2                                /* the mean square and the bad-row count behind an entry's N + 1 powers */
+#define QD_SPHARM_OP_VORT 2                              /* entry ops beside history's 0 and 1 */
+#define QD_SPHARM_OP_DIV 3
+#define QD_SPHARM_MAX_LAT 1535                           /* rows the Legendre kernel's widest form takes (12 latitude pairs per lane) */
+/* n entries (op, a, b as qd_history_configure takes them; a and b are ignored for QD_SPHARM_OP_VORT / _DIV), trunc = N, and the
+ * host's tables as spharm.tables forms them (the host is their one source): w, mu [n_lat], seed [N + 1][(n_lat + 1) / 2] =
+ * Pbar_m^m(mu_j) on the rows of the southern half, A, B [N + 1][N + 1] indexed [m][n]; flow_tab [QD_FLOW_TAB][n_lat] and flow_geom
+ * [3] as qd_flow_configure takes them, needed when an entry is VORT or DIV.  Allocates the log, the work planes and, with two_d,
+ * the sum planes; forgets an earlier configuration; n == 0 or w == NULL only releases.  Refused: latitude bands, N < 1 or not the
+ * grid's truncation, more than QD_SPHARM_MAX_LAT rows, a row whose working set does not fit the LDS a workgroup may take. */
+int qd_spharm_configure(qd_handle h, int n, const int32_t* op, const int32_t* a, const int32_t* b, int two_d, int trunc, const double* w,
+                        const double* mu, const double* seed, const double* A, const double* B, const double* flow_tab,
+                        const double* flow_geom);
+int qd_spharm_schedule(qd_handle h, int steps, const int32_t* sample);   /* the next qd_step_n span: non-zero = the step is sampled */
+int qd_spharm_sample(qd_handle h);                                   /* class seam: one record now from the resident fields, outside a span */
+int qd_spharm_log(qd_handle h, double* out, int max, int* n);        /* drain: *n records, oldest first */
+int qd_spharm_sums_get(qd_handle h, double* sums, int64_t* count);   /* the 2D sums [n][N + 1][N + 1] and the samples in them */
+int qd_spharm_sums_set(qd_handle h, const double* sums, int64_t count);   /* its inverse, for an exact resume (QD_CHECKPOINT) */
+int qd_spharm_reset(qd_handle h);                                    /* log and schedule forgotten, sums and count zeroed */
+/* class seam on a host plane [n_lat][n_lon], outside a span: the kernels of one entry on the plane -> coef_re, coef_im
+ * [N + 1 (m)][N + 1 (n)] (zero for n < m) and rec [N + 1 + QD_SPHARM_STATS]; the log, the sums and their count stay as they are */
+int qd_spharm_analyse(qd_handle h, const double* plane, double* coef_re, double* coef_im, double* rec);
+/* the same kernels without a handle, on any grid with N >= 1 (qd_create needs five rows) */
+int qd_spharm_analyse_grid(int n_lat, int n_lon, int device, int trunc, const double* w, const double* mu, const double* seed,
+                           const double* A, const double* B, const double* plane, double* coef_re, double* coef_im, double* rec);
+
 /* ---- state digest and exact resume (QD_CHECKPOINT), whole-globe handles ---------------------------------------------------
  * Nothing the reference has: its restart file holds 14 planes as f4 and a resumed run does not continue the run that was stopped.
  * qd_state_digest: a 64-bit digest of resident planes, all of them in ONE launch.  The digest of a plane of n elements is
@@ -953,6 +995,7 @@ enum qd_state_ref {
 #define QD_STATE_REF_HISTORY_SUMS QD_HISTORY_MAX_ENTRIES   /* index range of QD_SR_HISTORY_SUM */
 #define QD_STATE_REF_SPECTRA_SUMS 500                   /* one more ref: the lat-resolved sums of the spectra lane, [n][n_lat][n_bins] as ONE plane */
 #define QD_STATE_REF_FLOW_SUMS 501                      /* and the sum planes of the flow lane, [QD_FLOW_PLANES][n_lat][n_lon] as ONE plane */
+#define QD_STATE_REF_SPHARM_SUMS 502                    /* and the 2D sums of the spherical-harmonic lane, [n][N + 1][N + 1] as ONE plane */
 #define QD_STATE_DIGEST_MAX 64
 /* n <= 64 refs -> out[n].  Refused: latitude bands, an unknown ref, a ref whose subsystem is not configured (the line names it). */
 int qd_state_digest(qd_handle h, int n, const int32_t* refs, uint64_t* out);

@@ -17,6 +17,8 @@ The file (one NetCDF file through ncio.write_nc, f8 / u1 / i8 only; written to a
   qd_*                the ecology's own exact-resume variables (ecology.py: EcologyAdapter._extension_variables), not restated here
   flow_records, flow_times, flow_steps, flow_clock {i, records, count}, flow_sums   an open flow window continues (QD_FLOW=1 only);
                       the four sum planes are resident and digested as FLOW_SUMS
+  spharm_records, spharm_times, spharm_steps, spharm_clock {i, records, count}, spharm_sums   an open spherical-harmonic window
+                      continues (QD_SPHARM=1 only); the 2D sum planes (QD_SPHARM_2D=1) are resident and digested as SPHARM_SUMS
   drift_atm, drift_ocn, drift_records, drift_times, drift_steps, drift_clock {i, records}   the drifters' particle state (r | c |
                       status [| blocked], f8) and their open window (QD_DRIFTERS=1 only)
   atm_counter, ocn_counter, step_index, span_mark {step index, atm counter at the last span's end}, t_seconds, t_origin {t0, steps
@@ -164,6 +166,9 @@ def subsystems(sim):
     flw = getattr(sim, "flow", None)
     if flw is not None:                 # and the flow lane's
         extra["flow"] = f"every={int(flw.every)}"
+    sph = getattr(sim, "spharm", None)
+    if sph is not None:                 # and the spherical-harmonic lane's
+        extra["spharm"] = sph.key()
     return {**{"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
             "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
             "phyto_daily": str(int(sim.phyto_daily is not None)),
@@ -191,6 +196,9 @@ def plane_names(sim):
         names.append("SPECTRA_SUMS")
     if getattr(sim, "flow", None) is not None:
         names.append("FLOW_SUMS")
+    sph = getattr(sim, "spharm", None)
+    if sph is not None and sph.two_d:
+        names.append("SPHARM_SUMS")
     return names
 
 
@@ -314,6 +322,20 @@ def collect(sim):
         v["flow_steps"] = ("f8", ("flow_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
         v["flow_clock"] = ("f8", ("three",), np.array([float(flw.i), float(n), float(count)]))
         v["flow_sums"] = ("f8", ("flow_plane", "lat", "lon"), sums)
+    sph = getattr(sim, "spharm", None)
+    if sph is not None:
+        recs, times, steps = sph.window()
+        n = int(len(recs))
+        pad = max(n, 1)
+        dims["spharm_time"], dims["spharm_width"] = pad, int(sph.width)
+        v["spharm_records"] = ("f8", ("spharm_time", "spharm_width"), np.concatenate([recs, np.zeros((pad - n, sph.width))]))
+        v["spharm_times"] = ("f8", ("spharm_time",), np.concatenate([times, np.zeros(pad - n)]))
+        v["spharm_steps"] = ("f8", ("spharm_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
+        sums, count = sph.sums()
+        v["spharm_clock"] = ("f8", ("three",), np.array([float(sph.i), float(n), float(count)]))
+        if sums is not None:
+            dims["spharm_entry"], dims["spharm_degree"] = int(sums.shape[0]), int(sums.shape[1])
+            v["spharm_sums"] = ("f8", ("spharm_entry", "spharm_degree", "spharm_degree"), sums)
     dri = getattr(sim, "drifters", None)
     if dri is not None:                                        # the particles as they stand, and the open window's records so far
         recs, times, steps = dri.window()
@@ -401,7 +423,7 @@ class CheckpointFile:
             return np.asarray(v[key], dtype=np.float64)[int(idx)]
         key = {"ROUTE_BUFFER": "route_buffer", "ROUTE_FLOW": "route_flow", "ROUTE_LAKES": "route_lakes", "ECO_LAI_STACK": "qd_LAI_layers_SK",
                "INDIV_E_DAY": "qd_indiv_E_day", "INDIV_STRESS": "qd_indiv_stress_days", "SPECTRA_SUMS": "spectra_sums",
-               "FLOW_SUMS": "flow_sums"}[name]
+               "FLOW_SUMS": "flow_sums", "SPHARM_SUMS": "spharm_sums"}[name]
         return np.asarray(v[key], dtype=np.float64)
 
     def subsystems(self):
@@ -455,6 +477,9 @@ def check_subsystems(f, sim):
     if got.get("flow", "-") != want.get("flow", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the flow lane is '{got.get('flow', '-')}' in the file and "
                                 f"'{want.get('flow', '-')}' in this run")
+    if got.get("spharm", "-") != want.get("spharm", "-"):
+        raise CheckpointRefused(f"the subsystem set differs: the spharm lane is '{got.get('spharm', '-')}' in the file and "
+                                f"'{want.get('spharm', '-')}' in this run")
     if got.get("drifters", "-") != want.get("drifters", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the drifters lane is '{got.get('drifters', '-')}' in the file and "
                                 f"'{want.get('drifters', '-')}' in this run")
@@ -506,6 +531,8 @@ def _file_plane_names(f):
         names.append("SPECTRA_SUMS")
     if "flow_sums" in v:
         names.append("FLOW_SUMS")
+    if "spharm_sums" in v:
+        names.append("SPHARM_SUMS")
     return names
 
 
@@ -599,6 +626,12 @@ def load(sim, path, env=None, out=print):
         sim.flow.restore_window(np.asarray(v["flow_records"], dtype=np.float64)[:n], np.asarray(v["flow_times"])[:n],
                                 np.asarray(v["flow_steps"])[:n], int(clock[0]),
                                 sums=np.asarray(v["flow_sums"], dtype=np.float64), count=int(clock[2]))
+    if getattr(sim, "spharm", None) is not None:
+        clock = np.asarray(v["spharm_clock"], dtype=np.float64)
+        n = int(clock[1])
+        sim.spharm.restore_window(np.asarray(v["spharm_records"], dtype=np.float64)[:n], np.asarray(v["spharm_times"])[:n],
+                                  np.asarray(v["spharm_steps"])[:n], int(clock[0]),
+                                  sums=np.asarray(v["spharm_sums"], dtype=np.float64) if "spharm_sums" in v else None, count=int(clock[2]))
     dri = getattr(sim, "drifters", None)
     if dri is not None:
         clock = np.asarray(v["drift_clock"], dtype=np.float64)

@@ -488,6 +488,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_spectra_release(c);
     qd_drift_release(c);
     qd_flow_release(c);
+    qd_spharm_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -732,6 +733,10 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     // the flow lane (qd_flow.hip): a sampled step solves for streamfunction and velocity potential from U, V as the step leaves them
     const bool with_flow = qd_flow_scheduled(c);
     if (with_flow && !(span.lane[QD_LANE_FLOW] = qd_flow_span_begin(c, n))) return -1;
+    // the spherical-harmonic spectra (qd_spharm.hip): the zonal spectra's protocol and sampling places
+    const bool with_spharm = qd_spharm_scheduled(c);
+    if (with_spharm && !(span.lane[QD_LANE_SPHARM] = qd_spharm_span_begin(c, n))) return -1;
+    const bool spharm_lazy = with_spharm && qd_spharm_reads_lazy(c);
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -746,6 +751,8 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (series_fire && (rc = qd_series_begin_step(c))) return rc;
         const bool spectra_fire = with_spectra && span.lane[QD_LANE_SPECTRA]->at(s) != 0.0;
         if (spectra_fire && (rc = qd_spectra_begin_step(c))) return rc;
+        const bool spharm_fire = with_spharm && span.lane[QD_LANE_SPHARM]->at(s) != 0.0;
+        if (spharm_fire && (rc = qd_spharm_begin_step(c))) return rc;
         const bool drift_rec = with_drift && span.lane[QD_LANE_DRIFT]->at(s) != 0.0;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
@@ -767,7 +774,8 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         const QdForcingCall fc{st, st + 3, st[6]};
         // lazy diagnostics: inside a span only the last step stores what nothing inside a span reads -- unless a reader comes with the flags
         c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag || bd_main || (hist_fire && hist_lazy) ||
-                         (series_fire && series_lazy) || (spectra_fire && spectra_lazy) || (drift_rec && drift_lazy)) ? 1 : 0;
+                         (series_fire && series_lazy) || (spectra_fire && spectra_lazy) || (drift_rec && drift_lazy) ||
+                         (spharm_fire && spharm_lazy)) ? 1 : 0;
         if (with_phys) {
             const int part = c->precip_done ? 2 : 0;         // the precipitation block may have run inside the previous ocean step
             c->precip_done = 0;
@@ -800,6 +808,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (hist_fire && (rc = qd_history_accumulate(c, 0))) return rc;
         if (series_fire && (rc = qd_series_reduce(c, 0))) return rc;
         if (spectra_fire && (rc = qd_spectra_transform(c, 0))) return rc;
+        if (spharm_fire && (rc = qd_spharm_transform(c, 0))) return rc;
         // The precipitation block of step s + 1 (run_simulation.py:1740-1790) reads u, v and P_cond as time_step left them and
         // nothing the ocean step, the tracers, the individuals or the bucket touch, and writes only what the rest of step s + 1's
         // driver physics reads: it is queued inside the ocean step, between the stress kernel and the host's wait for the CFL maxima.
@@ -826,6 +835,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // drifters: U, V and the patched UO, VO as the step leaves them
         if (with_drift && (rc = qd_drift_step(c, dt, drift_rec ? 1 : 0))) return rc;
         if (with_flow && span.lane[QD_LANE_FLOW]->at(s) != 0.0 && (rc = qd_flow_step(c))) return rc;
+        if (spharm_fire && (rc = qd_spharm_transform(c, 1))) return rc;
     }
     c->diag_write = 1;
     return qd_launch_check(c, "qd_step_n");

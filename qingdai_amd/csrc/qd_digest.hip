@@ -73,7 +73,7 @@ static const char* dg_ref_name(int ref, char* buf, size_t nb) {
     else snprintf(buf, nb, "%s", ref == QD_SR_ROUTE_BUFFER ? "ROUTE_BUFFER" : ref == QD_SR_ROUTE_FLOW ? "ROUTE_FLOW" : ref == QD_SR_ROUTE_LAKES ? "ROUTE_LAKES" :
                                  ref == QD_SR_ECO_LAI_STACK ? "ECO_LAI_STACK" : ref == QD_SR_INDIV_E_DAY ? "INDIV_E_DAY" :
                                  ref == QD_SR_INDIV_STRESS ? "INDIV_STRESS" : ref == QD_STATE_REF_SPECTRA_SUMS ? "SPECTRA_SUMS" :
-                                 ref == QD_STATE_REF_FLOW_SUMS ? "FLOW_SUMS" : "?");
+                                 ref == QD_STATE_REF_FLOW_SUMS ? "FLOW_SUMS" : ref == QD_STATE_REF_SPHARM_SUMS ? "SPHARM_SUMS" : "?");
     return buf;
 }
 
@@ -115,6 +115,10 @@ static int dg_resolve(qd_ctx* c, int ref, QdDigestEntry* e) {
     } else if (ref == QD_STATE_REF_FLOW_SUMS) {
         const double* sums;
         if (!qd_flow_planes(c, &sums, &n)) { why = "the flow lane is not configured (qd_flow_configure)"; n = cells; }
+        else p = sums;
+    } else if (ref == QD_STATE_REF_SPHARM_SUMS) {
+        const double* sums;
+        if (!qd_spharm_planes(c, &sums, &n)) { why = "the 2D sums of the spherical-harmonic lane are not configured (qd_spharm_configure)"; n = cells; }
         else p = sums;
     } else {
         return qd_fail(c, ("qd_state_digest: unknown ref " + std::to_string(ref)).c_str());

@@ -697,3 +697,15 @@ extern "C" int qd_flow_solve_grid(int n_lat, int n_lon, int device, const double
     hipStreamDestroy(st);
     return rc;
 }
+
+// ---- the vorticity / divergence launch for another lane (qd_spharm.hip: its VORT and DIV entries), on that lane's own buffers: tab
+// [QD_FLOW_TAB][nlat] on the device, geom {a, dlat, dlon}, Z and D [nlat][nlon], rowstat [QF_NROW1][nlat].  prepare: once, at that
+// lane's configure time (a row of 3 nlon doubles may need more than the default 64 KB of dynamic LDS).
+bool qd_flow_vortdiv_prepare(size_t lds_limit) {
+    return hipFuncSetAttribute((const void*)k_flow_vortdiv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit) == hipSuccess;
+}
+void qd_flow_vortdiv_launch(qd_ctx* c, hipStream_t st, int nlat, int nlon, const double* tab, const double* geom, const double* U, const double* V,
+                            double* Z, double* D, double* rowstat) {
+    const QdFlowGrid G{nlat, nlon, nlon / 2 + 1, geom[0], geom[1], geom[2], tab, nullptr, nullptr};
+    QF_LAUNCH(c, "spharm_vortdiv", k_flow_vortdiv, dim3(nlat), 3 * (size_t)nlon * sizeof(double), st, G, U, V, Z, D, rowstat);
+}

@@ -216,6 +216,7 @@ struct qd_ctx {
     struct QdSeries* series = nullptr;       // per-step series: entry table, row weights, row results, record log, schedule (qd_series.hip)
     struct QdSpectra* spectra = nullptr;     // zonal spectra: entry table, twiddles, row powers, sum planes, record log, schedule (qd_spectra.hip)
     struct QdFlow* flow = nullptr;           // streamfunction / velocity potential: tables, work and sum planes, record log, schedule (qd_flow.hip)
+    struct QdSpharm* spharm = nullptr;       // spherical-harmonic spectra: entry table, host tables, work and sum planes, record log, schedule (qd_spharm.hip)
     struct QdDrift* drift = nullptr;         // Lagrangian drifters: particle state, metric table, record log, schedule (qd_drift.hip)
     unsigned long long* digest_out = nullptr; // [64] results of qd_state_digest, allocated at its first call (qd_digest.hip)
     double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
@@ -563,6 +564,18 @@ bool qd_flow_scheduled(const qd_ctx* c);
 struct QdSpanLane* qd_flow_span_begin(qd_ctx* c, int n);
 int  qd_flow_step(qd_ctx* c);
 bool qd_flow_planes(const qd_ctx* c, const double** sums, size_t* n);         // the four sum planes as one plane (qd_state_digest)
+bool qd_flow_vortdiv_prepare(size_t lds_limit);                               // k_flow_vortdiv for another lane (qd_spharm.hip), on its buffers
+void qd_flow_vortdiv_launch(qd_ctx* c, hipStream_t st, int nlat, int nlon, const double* tab, const double* geom, const double* U, const double* V,
+                            double* Z, double* D, double* rowstat);
+// qd_spharm.hip: the spectra's protocol; transform is the launches of a sampling position (vorticity / divergence when selected, row
+// stage, Legendre stage, record)
+void qd_spharm_release(qd_ctx* c);
+bool qd_spharm_scheduled(const qd_ctx* c);
+bool qd_spharm_reads_lazy(const qd_ctx* c);
+struct QdSpanLane* qd_spharm_span_begin(qd_ctx* c, int n);
+int  qd_spharm_begin_step(qd_ctx* c);
+int  qd_spharm_transform(qd_ctx* c, int group);
+bool qd_spharm_planes(const qd_ctx* c, const double** sums, size_t* n);       // the 2D sums as one plane (qd_state_digest)
 // what qd_state_digest and the exact resume (qd_digest.hip) need from the feature modules: their resident planes, and their firing
 // counts (set >= 0 stores it; -> the count as it then stands, 0 when the module is not configured)
 bool qd_route_planes(const qd_ctx* c, const double** buf, const double** flow, const double** lakes, int* n_lakes);    // qd_route.hip

@@ -27,6 +27,8 @@ class Device:
     _series_width = 0         # doubles per record of the last series_configure
     _spectra_n = 0            # entries of the last spectra_configure
     _spectra_lat = False      # ... and whether it keeps the lat-resolved sum planes
+    _spharm_n = _spharm_N = 0 # entries and truncation of the last spharm_configure
+    _spharm_2d = False        # ... and whether it keeps the 2D sum planes
     _drift = (0, 0, 0, 0)     # n_atm, n_ocn, record width and log capacity of the last drift_configure
     _tiles_n = 1              # tiles of the last tile configuration
     _div_shape = None         # [S, lat, lon] of the last eco_diversity call
@@ -135,7 +137,7 @@ class Device:
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
                ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None,
-               series=None, spectra=None, drifters=None, flow=None):
+               series=None, spectra=None, drifters=None, flow=None, spharm=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  The span lanes, each a participant on this handle whose records stay in its
         device log until the caller has it deliver them: `routing`, a RiverRouting -- bit7, after the hydrology commit (which it
@@ -149,7 +151,8 @@ class Device:
         likewise, one record of zonal wavenumber spectra per sampled step (spectra_log).  `drifters`, a drifters.Drifters -- no flag bit, and the
         one lane whose state moves: every step of the span advances the particles, its window clock names the steps that also leave a
         record (drift_log).  `flow`, a flow.Flow -- no flag bit: one record of flow kinematics per sampled step (flow_log), and the
-        sampled psi, chi, zeta, delta in resident sum planes (flow_sums)."""
+        sampled psi, chi, zeta, delta in resident sum planes (flow_sums).  `spharm`, a spharm.Spharm -- no flag bit: one record of
+        spherical-harmonic power spectra per sampled step (spharm_log), the 2D terms in resident sum planes (spharm_sums)."""
         self.flush()
         st = _c(stars)
         assert st.ndim == 2 and st.shape[1] == 7
@@ -161,7 +164,7 @@ class Device:
         #   span_restore(clock)       nothing ran (an upload or qd_step_n raised): the clock back to what span_clock gave
         #   _fired(k)                 the span ran: k is what span_schedule returned
         #   span_deliver(dt)          drain the lane's device log and deliver it (print, keep); the caller's move, once per span
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters, flow) if p is not None]
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters, flow, spharm) if p is not None]
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -355,6 +358,70 @@ class Device:
 
     def spectra_reset(self):
         self.call("qd_spectra_reset")
+
+    # ---- spherical-harmonic power spectra (qd_spharm.hip)
+    def spharm_configure(self, entries, two_d, tables, flow_tables=None):
+        """entries: [(op, a, b)] as history_configure takes them, or (QD_SPHARM_OP_VORT / _DIV, None, None); two_d: the terms
+        c_m |x_n^m|^2 are also summed in resident planes (spharm_sums); tables: spharm.tables(n_lat, n_lon); flow_tables:
+        flow.grid_tables(grid, radius), needed when an entry is VORT or DIV.  An empty list (or tables None) releases the lane.
+        QD_SPHARM_FORM=direct in the environment of this call forces the direct row sums."""
+        if not len(entries) or tables is None:
+            self.call("qd_spharm_configure", 0, None, None, None, 0, 0, None, None, None, None, None, None, None)
+            self._spharm_n, self._spharm_2d, self._spharm_N = 0, False, 0
+            return
+        if (tables.n_lat, tables.n_lon) != self.shape:
+            raise ValueError(f"spharm_configure: the tables are for a {tables.n_lat} x {tables.n_lon} grid, the handle's is {self.shape}")
+        own = (_lib.C["QD_SPHARM_OP_VORT"], _lib.C["QD_SPHARM_OP_DIV"])
+        if flow_tables is None and any(e[0] in own for e in entries):
+            raise ValueError("spharm_configure: a VORT or DIV entry needs the flow lane's grid tables (flow.grid_tables)")
+        self.call("qd_spharm_configure", len(entries), [e[0] for e in entries], [F[e[1]] if e[1] is not None else -1 for e in entries],
+                  [F[e[2]] if e[2] is not None else -1 for e in entries], int(bool(two_d)), tables.N, tables.w, tables.mu,
+                  tables.seed_pairs, tables.A, tables.B, None if flow_tables is None else flow_tables.tab,
+                  None if flow_tables is None else flow_tables.geom)
+        self._spharm_n, self._spharm_2d, self._spharm_N = len(entries), bool(two_d), int(tables.N)
+
+    def spharm_schedule(self, sample):
+        self.call("qd_spharm_schedule", np.size(sample), sample)
+
+    def spharm_sample(self):
+        """One record of every entry from the fields as they stand, added to the 2D sums (the class seam)."""
+        self.flush()
+        self.call("qd_spharm_sample")
+
+    def spharm_log(self, max_records=None):
+        """Drain the records -> [n][width], oldest first; width = entries * (N + 1 + QD_SPHARM_STATS), per entry P(0 .. N), the mean
+        square and the count of bad rows.  max_records: what the caller knows to be queued at most."""
+        cap = _lib.C["QD_SPHARM_LOG_CAP"]
+        room = cap if max_records is None else max(0, min(int(max_records), cap))
+        w = max(1, self._spharm_n * (self._spharm_N + 1 + _lib.C["QD_SPHARM_STATS"]))
+        buf = np.empty(max(1, room) * w, dtype=np.float64)
+        return self._records((buf, self.call("qd_spharm_log", buf, room, OUT)), w)
+
+    def spharm_sums(self):
+        """-> (sums [n][N + 1 (n)][N + 1 (m)] of c_m |x_n^m|^2, sample count); 2D configurations only."""
+        out = np.empty((self._spharm_n, self._spharm_N + 1, self._spharm_N + 1), dtype=np.float64)
+        return out, self.call("qd_spharm_sums_get", out, OUT)
+
+    def spharm_sums_set(self, sums, count):
+        """The inverse of spharm_sums, for an exact resume."""
+        want = (self._spharm_n, self._spharm_N + 1, self._spharm_N + 1)
+        if np.shape(sums) != want:
+            raise ValueError(f"spharm_sums_set: expected sums of shape {want}, got {np.shape(sums)}")
+        self.call("qd_spharm_sums_set", _c(sums), count)
+
+    def spharm_reset(self):
+        self.call("qd_spharm_reset")
+
+    def spharm_analyse(self, plane):
+        """The kernels of one entry on a host plane (the class seam, outside any span) -> (coef [m][n] complex, rec
+        [N + 1 + QD_SPHARM_STATS]); the log and the 2D sums stay as they are."""
+        x = _c(plane)
+        if x.shape != self.shape:
+            raise ValueError(f"spharm_analyse: the plane is of shape {self.shape}")
+        n1 = self._spharm_N + 1
+        re, im, rec = np.empty((n1, n1)), np.empty((n1, n1)), np.empty(n1 + _lib.C["QD_SPHARM_STATS"])
+        self.call("qd_spharm_analyse", x, re, im, rec)
+        return re + 1j * im, rec
 
     # ---- Lagrangian drifters (qd_drift.hip)
     def drift_configure(self, atm, ocn, sample_atm, sample_ocn, sec_row):
@@ -789,7 +856,7 @@ class Device:
     def digest(self, names):
         """The 64-bit digests of resident planes (include/qingdai_hip.h: qd_state_digest), one launch per 64 of them -> np.uint64[n].
         names: what _lib.state_ref takes -- field names, LAND_MASK, ICE_MASK, ROUTE_BUFFER, ROUTE_FLOW, ROUTE_LAKES, ECO_LAI_STACK,
-        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, FLOW_SUMS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
+        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, FLOW_SUMS, SPHARM_SUMS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
         self.flush()
         refs = [_lib.state_ref(n) for n in names]
         out = np.zeros(len(refs), dtype=np.uint64)

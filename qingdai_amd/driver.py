@@ -169,6 +169,15 @@ launches on a sampled step, one record of scalars in a device log, the four plan
 with a window's last step, behind which <QD_OUTPUT_DIR>/flow/flow_day_{a}_{b}.nc (psi_mean, chi_mean, vort_mean, div_mean [lat][lon],
 the scalar series [time], time_seconds, step, dt_seconds, sample_every, n_samples, complete) is written and one [Flow] line printed.
 The normal end of main writes the open window with complete = 0; under QD_CHECKPOINT=1 the checkpoint carries it instead.
+Spherical-harmonic power spectra (QD_SPHARM=1, default 0; nothing the reference has): on every QD_SPHARM_EVERY-th (default 24) step
+of a window of QD_SPHARM_EVERY_DAYS (default 10) planet-days -- history's window clock -- every field of QD_SPHARM_FIELDS (default
+VORT,DIV,H; history's parser, ocean-only rule and sampling places, and VORT, DIV: the flow lane's vorticity and divergence of the
+winds) is analysed on the device into spherical-harmonic coefficients up to the triangular truncation N = min((n_lat - 1) // 2,
+(n_lon - 1) // 2) (row FFT, then a Legendre recurrence fused with Clenshaw-Curtis quadrature over the latitude rows), by a tenth span
+lane (qingdai_amd/spharm.py, qd_spharm_*) whose records -- power per total wavenumber, mean square, bad rows -- stay in a device log
+until the chunk ends; under QD_SPHARM_2D=1 (default) the terms c_m |x_n^m|^2 are also summed in resident planes.  A chunk ends with a
+window's last step, behind which <QD_OUTPUT_DIR>/spharm/spharm_day_{a}_{b}.nc is written and one [SphSpec] line printed.  The normal
+end of main writes the open window with complete = 0; under QD_CHECKPOINT=1 the checkpoint carries it instead.
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -273,6 +282,7 @@ class Simulation:
     spectra = None                         # enable_spectra (QD_SPECTRA=1)
     drifters = None                        # enable_drifters (QD_DRIFTERS=1)
     flow = None                            # enable_flow (QD_FLOW=1)
+    spharm = None                          # enable_spharm (QD_SPHARM=1)
     truecolor = stateframe = figures = None
     plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
     _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
@@ -864,6 +874,7 @@ class Simulation:
         window's file is written (the sums then start the next window from zero); under QD_SERIES=1 likewise with its windows."""
         hist, ser, spc = self.history, self.series, getattr(self, "spectra", None)
         dri, flw = getattr(self, "drifters", None), getattr(self, "flow", None)
+        sph = getattr(self, "spharm", None)
         while n > 0:
             k = n if hist is None else min(n, hist.steps_to_window_end())
             if ser is not None:
@@ -874,10 +885,14 @@ class Simulation:
                 k = min(k, dri.steps_to_window_end())              # (its window's end, or the step that fills its device log)
             if flw is not None:
                 k = min(k, flw.steps_to_window_end())
+            if sph is not None:
+                k = min(k, sph.steps_to_window_end())
             self._run_lanes(k, energy_diag)
             n -= k
             if flw is not None and flw.window_closed():
                 self.flush_flow()
+            if sph is not None and sph.window_closed():
+                self.flush_spharm()
             if hist is not None and hist.window_closed():
                 self.flush_history()
             if ser is not None and ser.window_closed():
@@ -912,6 +927,11 @@ class Simulation:
         reported and the window is dropped: output never stops the run."""
         return self._nonfatal(lambda: self.flow.flush(complete=complete), "[Flow] window skipped: {}", cleanup=self.flow.drop)
 
+    def flush_spharm(self, complete=1):
+        """Write the spherical-harmonic window that stands on the host (and in the device's sum planes) -> the path or None.  A
+        failure is reported and the window is dropped: output never stops the run."""
+        return self._nonfatal(lambda: self.spharm.flush(complete=complete), "[SphSpec] window skipped: {}", cleanup=self.spharm.drop)
+
     def _run_lanes(self, n, energy_diag=False):
         """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
         individuals')."""
@@ -924,7 +944,8 @@ class Simulation:
         lanes = {k: p for k, p in (("phyto_daily", self.phyto_daily), ("routing", self.routing), ("budget", self.budget),
                                    ("eco_daily", eco_daily), ("history", self.history), ("series", self.series),
                                    ("spectra", getattr(self, "spectra", None)),
-                                   ("drifters", getattr(self, "drifters", None)), ("flow", getattr(self, "flow", None))) if p is not None}
+                                   ("drifters", getattr(self, "drifters", None)), ("flow", getattr(self, "flow", None)),
+                                   ("spharm", getattr(self, "spharm", None))) if p is not None}
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
         # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
@@ -1006,6 +1027,15 @@ class Simulation:
         from .flow import from_env
         self.flow = from_env(self.dev, self.grid, os.environ if env is None else env, dt=float(self.dt), day=self.day_seconds)
         return self.flow
+
+    def enable_spharm(self, env=None):
+        """QD_SPHARM=1: spherical-harmonic power spectra of the selected fields, analysed by a device lane and written per window to
+        <QD_OUTPUT_DIR>/spharm/ (qingdai_amd/spharm.py) -> the Spharm or None.  The run-local step index the windows count on
+        starts where this is called."""
+        from .spharm import from_env
+        self.spharm = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
+                               dt=float(self.dt), day=self.day_seconds)
+        return self.spharm
 
     def enable_drifters(self, env=None):
         """QD_DRIFTERS=1: Lagrangian drifters on the winds and the currents, advanced by a device lane on every step and written per
@@ -1286,6 +1316,8 @@ def main(argv=None):
         sim.enable_drifters(env)
     if getattr(sim, "enable_flow", None) is not None:          # (likewise)
         sim.enable_flow(env)
+    if getattr(sim, "enable_spharm", None) is not None:        # (likewise)
+        sim.enable_spharm(env)
     if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
         try:
             sim.load_checkpoint(ck_file, env)
@@ -1377,6 +1409,8 @@ def main(argv=None):
         sim.flush_drifters(complete=0)                         # and the open drifter window
     if getattr(sim, "flow", None) is not None and not (ck["enabled"] and autosave_on):
         sim.flush_flow(complete=0)                             # and the open flow window
+    if getattr(sim, "spharm", None) is not None and not (ck["enabled"] and autosave_on):
+        sim.flush_spharm(complete=0)                           # and the open spherical-harmonic window
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")
