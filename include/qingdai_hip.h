@@ -974,6 +974,32 @@ int qd_spharm_analyse(qd_handle h, const double* plane, double* coef_re, double*
 int qd_spharm_analyse_grid(int n_lat, int n_lon, int device, int trunc, const double* w, const double* mu, const double* seed,
                            const double* A, const double* B, const double* plane, double* coef_re, double* coef_im, double* rec);
 
+/* ---- eddy statistics: time sums of products of two fields (QD_EDDY), whole-globe handles --------------------------------------
+ * Nothing the reference has.  A span lane without a flag bit and without a log, like the history accumulators: a configuration names
+ * F <= QD_EDDY_MAX_FIELDS distinct f64 planes and P <= QD_EDDY_MAX_PAIRS pairs (p, q) of indices into that list (p == q: a variance).
+ * Resident: anchors r[F], first-moment sums S[F] and pair sums C[P], each [n_lat][n_lon] f64.  One sample, per cell, behind the
+ * step's last launch (history's late group): the first sample of a window stores r_f = a_f; then d_f = a_f - r_f, S_f = S_f + d_f,
+ * C_k = C_k + (d_p * d_q), every operation rounded on its own, no compensation, non-finite values as they come (the top of
+ * qingdai_amd/csrc/qd_eddy.hip is the definition, eddy.accumulate_reference its restatement).  One launch per sample. */
+#define QD_EDDY_MAX_FIELDS 16
+#define QD_EDDY_MAX_PAIRS 32
+#define QD_EDDY_ZONAL_SUMS 4                             /* row sums per pair of qd_eddy_zonal: S_p, S_q, C_k, S_p * S_q */
+/* fields[n_fields]: qd_field ids; p, q [n_pairs]: indices into fields.  Allocates and zeroes the planes; forgets an earlier
+ * configuration; n_fields == 0 only releases.  Refused, each with one line that begins "eddy:": latitude bands, more fields or pairs
+ * than the limits or no pair, an unknown plane or one that is not f64, PRECIP (sampled in front of the ocean step, every other field
+ * behind the step's last launch: a product across the two places has no meaning), a field named twice, a pair index out of range, a
+ * pair named twice in either order. */
+int qd_eddy_configure(qd_handle h, int n_fields, const int32_t* fields, int n_pairs, const int32_t* p, const int32_t* q);
+int qd_eddy_schedule(qd_handle h, int steps, const int32_t* sample);     /* the next qd_step_n span: non-zero = the step is sampled */
+int qd_eddy_sample(qd_handle h);                                        /* class seam: one sample now from the resident fields, outside a span */
+/* anchors [F][n_lat][n_lon], sums [F][n_lat][n_lon], pair_sums [P][n_lat][n_lon] and the samples in them */
+int qd_eddy_read(qd_handle h, double* anchors, double* sums, double* pair_sums, int64_t* count);
+int qd_eddy_restore(qd_handle h, const double* anchors, const double* sums, const double* pair_sums, int64_t count);   /* its inverse (QD_CHECKPOINT) */
+/* out [P][QD_EDDY_ZONAL_SUMS][n_lat]: per pair and row the sums over all n_lon columns of S_p, S_q, C_k and S_p * S_q (the product
+ * rounded), one wavefront per (pair, row) in the order of the series lane's row stage */
+int qd_eddy_zonal(qd_handle h, double* out);
+int qd_eddy_reset(qd_handle h);                                         /* sums and count zeroed, schedule forgotten: the next sample is a window's first */
+
 /* ---- state digest and exact resume (QD_CHECKPOINT), whole-globe handles ---------------------------------------------------
  * Nothing the reference has: its restart file holds 14 planes as f4 and a resumed run does not continue the run that was stopped.
  * qd_state_digest: a 64-bit digest of resident planes, all of them in ONE launch.  The digest of a plane of n elements is
@@ -996,6 +1022,8 @@ enum qd_state_ref {
 #define QD_STATE_REF_SPECTRA_SUMS 500                   /* one more ref: the lat-resolved sums of the spectra lane, [n][n_lat][n_bins] as ONE plane */
 #define QD_STATE_REF_FLOW_SUMS 501                      /* and the sum planes of the flow lane, [QD_FLOW_PLANES][n_lat][n_lon] as ONE plane */
 #define QD_STATE_REF_SPHARM_SUMS 502                    /* and the 2D sums of the spherical-harmonic lane, [n][N + 1][N + 1] as ONE plane */
+#define QD_STATE_REF_EDDY_SUMS 503                      /* and the eddy lane's first-moment and pair sums, [F + P] planes of even stride as ONE plane */
+#define QD_STATE_REF_EDDY_ANCHORS 504                   /* and its anchors, [F] planes of even stride as ONE plane */
 #define QD_STATE_DIGEST_MAX 64
 /* n <= 64 refs -> out[n].  Refused: latitude bands, an unknown ref, a ref whose subsystem is not configured (the line names it). */
 int qd_state_digest(qd_handle h, int n, const int32_t* refs, uint64_t* out);

@@ -19,6 +19,8 @@ The file (one NetCDF file through ncio.write_nc, f8 / u1 / i8 only; written to a
                       the four sum planes are resident and digested as FLOW_SUMS
   spharm_records, spharm_times, spharm_steps, spharm_clock {i, records, count}, spharm_sums   an open spherical-harmonic window
                       continues (QD_SPHARM=1 only); the 2D sum planes (QD_SPHARM_2D=1) are resident and digested as SPHARM_SUMS
+  eddy_anchors, eddy_sums, eddy_pair_sums, eddy_clock {i, t_first, t_last, n_open, count}   an open eddy window continues (QD_EDDY=1
+                      only); the planes are resident and digested as EDDY_ANCHORS and EDDY_SUMS (sums and pair sums as one plane)
   drift_atm, drift_ocn, drift_records, drift_times, drift_steps, drift_clock {i, records}   the drifters' particle state (r | c |
                       status [| blocked], f8) and their open window (QD_DRIFTERS=1 only)
   atm_counter, ocn_counter, step_index, span_mark {step index, atm counter at the last span's end}, t_seconds, t_origin {t0, steps
@@ -169,6 +171,9 @@ def subsystems(sim):
     sph = getattr(sim, "spharm", None)
     if sph is not None:                 # and the spherical-harmonic lane's
         extra["spharm"] = sph.key()
+    edd = getattr(sim, "eddy", None)
+    if edd is not None:                 # and the eddy lane's
+        extra["eddy"] = edd.key()
     return {**{"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
             "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
             "phyto_daily": str(int(sim.phyto_daily is not None)),
@@ -199,6 +204,8 @@ def plane_names(sim):
     sph = getattr(sim, "spharm", None)
     if sph is not None and sph.two_d:
         names.append("SPHARM_SUMS")
+    if getattr(sim, "eddy", None) is not None:
+        names += ["EDDY_SUMS", "EDDY_ANCHORS"]
     return names
 
 
@@ -336,6 +343,14 @@ def collect(sim):
         if sums is not None:
             dims["spharm_entry"], dims["spharm_degree"] = int(sums.shape[0]), int(sums.shape[1])
             v["spharm_sums"] = ("f8", ("spharm_entry", "spharm_degree", "spharm_degree"), sums)
+    edd = getattr(sim, "eddy", None)
+    if edd is not None:
+        anchors, sums, pair_sums, count = dev.eddy_read()
+        dims["eddy_field"], dims["eddy_pair"] = int(sums.shape[0]), int(pair_sums.shape[0])
+        v["eddy_anchors"] = ("f8", ("eddy_field", "lat", "lon"), anchors)
+        v["eddy_sums"] = ("f8", ("eddy_field", "lat", "lon"), sums)
+        v["eddy_pair_sums"] = ("f8", ("eddy_pair", "lat", "lon"), pair_sums)
+        v["eddy_clock"] = ("f8", ("five",), np.array([float(edd.i), _nan(edd.t_first), _nan(edd.t_last), float(edd.n_open), float(count)]))
     dri = getattr(sim, "drifters", None)
     if dri is not None:                                        # the particles as they stand, and the open window's records so far
         recs, times, steps = dri.window()
@@ -418,6 +433,10 @@ class CheckpointFile:
         if name in FIELDS:
             a = np.asarray(v["f_" + name], dtype=np.float64)
             return a.astype(np.float32) if (self.subsystems().get("eco_f32") == "1" and name in F32_MAPS) else a
+        if name in ("EDDY_SUMS", "EDDY_ANCHORS"):                  # the device keeps each plane at an even stride: a cell of +0.0 behind an odd one
+            keys = ("eddy_sums", "eddy_pair_sums") if name == "EDDY_SUMS" else ("eddy_anchors",)
+            planes = np.concatenate([np.asarray(v[k], dtype=np.float64).reshape(np.shape(v[k])[0], -1) for k in keys])
+            return np.pad(planes, ((0, 0), (0, planes.shape[1] & 1)))
         key = {"PHYTO_TRACER": "phyto_C", "HISTORY_SUM": "hist_sums"}.get(base)
         if key is not None:
             return np.asarray(v[key], dtype=np.float64)[int(idx)]
@@ -480,6 +499,9 @@ def check_subsystems(f, sim):
     if got.get("spharm", "-") != want.get("spharm", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the spharm lane is '{got.get('spharm', '-')}' in the file and "
                                 f"'{want.get('spharm', '-')}' in this run")
+    if got.get("eddy", "-") != want.get("eddy", "-"):
+        raise CheckpointRefused(f"the subsystem set differs: the eddy lane is '{got.get('eddy', '-')}' in the file and "
+                                f"'{want.get('eddy', '-')}' in this run")
     if got.get("drifters", "-") != want.get("drifters", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the drifters lane is '{got.get('drifters', '-')}' in the file and "
                                 f"'{want.get('drifters', '-')}' in this run")
@@ -533,6 +555,8 @@ def _file_plane_names(f):
         names.append("FLOW_SUMS")
     if "spharm_sums" in v:
         names.append("SPHARM_SUMS")
+    if "eddy_sums" in v:
+        names += ["EDDY_SUMS", "EDDY_ANCHORS"]
     return names
 
 
@@ -632,6 +656,11 @@ def load(sim, path, env=None, out=print):
         sim.spharm.restore_window(np.asarray(v["spharm_records"], dtype=np.float64)[:n], np.asarray(v["spharm_times"])[:n],
                                   np.asarray(v["spharm_steps"])[:n], int(clock[0]),
                                   sums=np.asarray(v["spharm_sums"], dtype=np.float64) if "spharm_sums" in v else None, count=int(clock[2]))
+    if getattr(sim, "eddy", None) is not None:
+        e, clock = sim.eddy, np.asarray(v["eddy_clock"], dtype=np.float64)
+        dev.eddy_restore(np.asarray(v["eddy_anchors"], dtype=np.float64), np.asarray(v["eddy_sums"], dtype=np.float64),
+                         np.asarray(v["eddy_pair_sums"], dtype=np.float64), int(clock[4]))
+        e.i, e.t_first, e.t_last, e.n_open = int(clock[0]), _none(clock[1]), _none(clock[2]), int(clock[3])
     dri = getattr(sim, "drifters", None)
     if dri is not None:
         clock = np.asarray(v["drift_clock"], dtype=np.float64)

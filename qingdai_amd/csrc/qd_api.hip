@@ -489,6 +489,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_drift_release(c);
     qd_flow_release(c);
     qd_spharm_release(c);
+    qd_eddy_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -737,6 +738,10 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     const bool with_spharm = qd_spharm_scheduled(c);
     if (with_spharm && !(span.lane[QD_LANE_SPHARM] = qd_spharm_span_begin(c, n))) return -1;
     const bool spharm_lazy = with_spharm && qd_spharm_reads_lazy(c);
+    // the eddy statistics (qd_eddy.hip): a sampled step adds deviations and their products to resident planes, one launch
+    const bool with_eddy = qd_eddy_scheduled(c);
+    if (with_eddy && !(span.lane[QD_LANE_EDDY] = qd_eddy_span_begin(c, n))) return -1;
+    const bool eddy_lazy = with_eddy && qd_eddy_reads_lazy(c);
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -754,6 +759,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         const bool spharm_fire = with_spharm && span.lane[QD_LANE_SPHARM]->at(s) != 0.0;
         if (spharm_fire && (rc = qd_spharm_begin_step(c))) return rc;
         const bool drift_rec = with_drift && span.lane[QD_LANE_DRIFT]->at(s) != 0.0;
+        const bool eddy_fire = with_eddy && span.lane[QD_LANE_EDDY]->at(s) != 0.0;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
         if (with_pdaily && span.lane[QD_LANE_PHYTO_DAILY]->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
@@ -775,7 +781,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // lazy diagnostics: inside a span only the last step stores what nothing inside a span reads -- unless a reader comes with the flags
         c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag || bd_main || (hist_fire && hist_lazy) ||
                          (series_fire && series_lazy) || (spectra_fire && spectra_lazy) || (drift_rec && drift_lazy) ||
-                         (spharm_fire && spharm_lazy)) ? 1 : 0;
+                         (spharm_fire && spharm_lazy) || (eddy_fire && eddy_lazy)) ? 1 : 0;
         if (with_phys) {
             const int part = c->precip_done ? 2 : 0;         // the precipitation block may have run inside the previous ocean step
             c->precip_done = 0;
@@ -836,6 +842,8 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (with_drift && (rc = qd_drift_step(c, dt, drift_rec ? 1 : 0))) return rc;
         if (with_flow && span.lane[QD_LANE_FLOW]->at(s) != 0.0 && (rc = qd_flow_step(c))) return rc;
         if (spharm_fire && (rc = qd_spharm_transform(c, 1))) return rc;
+        // eddy statistics: every field as the step leaves it
+        if (eddy_fire && (rc = qd_eddy_accumulate(c))) return rc;
     }
     c->diag_write = 1;
     return qd_launch_check(c, "qd_step_n");

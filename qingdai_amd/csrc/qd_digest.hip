@@ -73,7 +73,8 @@ static const char* dg_ref_name(int ref, char* buf, size_t nb) {
     else snprintf(buf, nb, "%s", ref == QD_SR_ROUTE_BUFFER ? "ROUTE_BUFFER" : ref == QD_SR_ROUTE_FLOW ? "ROUTE_FLOW" : ref == QD_SR_ROUTE_LAKES ? "ROUTE_LAKES" :
                                  ref == QD_SR_ECO_LAI_STACK ? "ECO_LAI_STACK" : ref == QD_SR_INDIV_E_DAY ? "INDIV_E_DAY" :
                                  ref == QD_SR_INDIV_STRESS ? "INDIV_STRESS" : ref == QD_STATE_REF_SPECTRA_SUMS ? "SPECTRA_SUMS" :
-                                 ref == QD_STATE_REF_FLOW_SUMS ? "FLOW_SUMS" : ref == QD_STATE_REF_SPHARM_SUMS ? "SPHARM_SUMS" : "?");
+                                 ref == QD_STATE_REF_FLOW_SUMS ? "FLOW_SUMS" : ref == QD_STATE_REF_SPHARM_SUMS ? "SPHARM_SUMS" :
+                                 ref == QD_STATE_REF_EDDY_SUMS ? "EDDY_SUMS" : ref == QD_STATE_REF_EDDY_ANCHORS ? "EDDY_ANCHORS" : "?");
     return buf;
 }
 
@@ -120,6 +121,11 @@ static int dg_resolve(qd_ctx* c, int ref, QdDigestEntry* e) {
         const double* sums;
         if (!qd_spharm_planes(c, &sums, &n)) { why = "the 2D sums of the spherical-harmonic lane are not configured (qd_spharm_configure)"; n = cells; }
         else p = sums;
+    } else if (ref == QD_STATE_REF_EDDY_SUMS || ref == QD_STATE_REF_EDDY_ANCHORS) {
+        const double *anchors, *sums; size_t na, ns;
+        if (!qd_eddy_planes(c, &anchors, &na, &sums, &ns)) { why = "the eddy statistics are not configured (qd_eddy_configure)"; n = cells; }
+        else if (ref == QD_STATE_REF_EDDY_SUMS) { p = sums; n = ns; }
+        else { p = anchors; n = na; }
     } else {
         return qd_fail(c, ("qd_state_digest: unknown ref " + std::to_string(ref)).c_str());
     }

@@ -217,6 +217,7 @@ struct qd_ctx {
     struct QdSpectra* spectra = nullptr;     // zonal spectra: entry table, twiddles, row powers, sum planes, record log, schedule (qd_spectra.hip)
     struct QdFlow* flow = nullptr;           // streamfunction / velocity potential: tables, work and sum planes, record log, schedule (qd_flow.hip)
     struct QdSpharm* spharm = nullptr;       // spherical-harmonic spectra: entry table, host tables, work and sum planes, record log, schedule (qd_spharm.hip)
+    struct QdEddy* eddy = nullptr;           // eddy statistics: field and pair tables, anchor / sum / pair-sum planes, sample count, schedule (qd_eddy.hip)
     struct QdDrift* drift = nullptr;         // Lagrangian drifters: particle state, metric table, record log, schedule (qd_drift.hip)
     unsigned long long* digest_out = nullptr; // [64] results of qd_state_digest, allocated at its first call (qd_digest.hip)
     double budget_fire = 0.0;                // set by qd_step_n around the ocean step: != 0 -> the [OceanE] reduction runs in front of the polar fill
@@ -576,6 +577,14 @@ struct QdSpanLane* qd_spharm_span_begin(qd_ctx* c, int n);
 int  qd_spharm_begin_step(qd_ctx* c);
 int  qd_spharm_transform(qd_ctx* c, int group);
 bool qd_spharm_planes(const qd_ctx* c, const double** sums, size_t* n);       // the 2D sums as one plane (qd_state_digest)
+// qd_eddy.hip: history's protocol with one sampling place, behind the step's last launch; accumulate is the one launch of a sample
+void qd_eddy_release(qd_ctx* c);
+bool qd_eddy_scheduled(const qd_ctx* c);
+bool qd_eddy_reads_lazy(const qd_ctx* c);                                       // a field is a lazily stored diagnostic (lazy_diag)
+struct QdSpanLane* qd_eddy_span_begin(qd_ctx* c, int n);
+int  qd_eddy_accumulate(qd_ctx* c);
+// the anchors [F] and the sums [F + P], each group as one plane of n doubles (qd_state_digest)
+bool qd_eddy_planes(const qd_ctx* c, const double** anchors, size_t* n_anchors, const double** sums, size_t* n_sums);
 // what qd_state_digest and the exact resume (qd_digest.hip) need from the feature modules: their resident planes, and their firing
 // counts (set >= 0 stores it; -> the count as it then stands, 0 when the module is not configured)
 bool qd_route_planes(const qd_ctx* c, const double** buf, const double** flow, const double** lakes, int* n_lakes);    // qd_route.hip

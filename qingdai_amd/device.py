@@ -29,6 +29,7 @@ class Device:
     _spectra_lat = False      # ... and whether it keeps the lat-resolved sum planes
     _spharm_n = _spharm_N = 0 # entries and truncation of the last spharm_configure
     _spharm_2d = False        # ... and whether it keeps the 2D sum planes
+    _eddy = (0, 0)            # fields and pairs of the last eddy_configure
     _drift = (0, 0, 0, 0)     # n_atm, n_ocn, record width and log capacity of the last drift_configure
     _tiles_n = 1              # tiles of the last tile configuration
     _div_shape = None         # [S, lat, lon] of the last eco_diversity call
@@ -137,7 +138,7 @@ class Device:
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
                ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None,
-               series=None, spectra=None, drifters=None, flow=None, spharm=None):
+               series=None, spectra=None, drifters=None, flow=None, spharm=None, eddy=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  The span lanes, each a participant on this handle whose records stay in its
         device log until the caller has it deliver them: `routing`, a RiverRouting -- bit7, after the hydrology commit (which it
@@ -152,7 +153,9 @@ class Device:
         one lane whose state moves: every step of the span advances the particles, its window clock names the steps that also leave a
         record (drift_log).  `flow`, a flow.Flow -- no flag bit: one record of flow kinematics per sampled step (flow_log), and the
         sampled psi, chi, zeta, delta in resident sum planes (flow_sums).  `spharm`, a spharm.Spharm -- no flag bit: one record of
-        spherical-harmonic power spectra per sampled step (spharm_log), the 2D terms in resident sum planes (spharm_sums)."""
+        spherical-harmonic power spectra per sampled step (spharm_log), the 2D terms in resident sum planes (spharm_sums).  `eddy`, an
+        eddy.Eddy -- no flag bit and no log: a sampled step adds the fields' deviations from their anchors and the products of
+        pairs of them to resident planes (eddy_read)."""
         self.flush()
         st = _c(stars)
         assert st.ndim == 2 and st.shape[1] == 7
@@ -164,7 +167,7 @@ class Device:
         #   span_restore(clock)       nothing ran (an upload or qd_step_n raised): the clock back to what span_clock gave
         #   _fired(k)                 the span ran: k is what span_schedule returned
         #   span_deliver(dt)          drain the lane's device log and deliver it (print, keep); the caller's move, once per span
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters, flow, spharm) if p is not None]
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters, flow, spharm, eddy) if p is not None]
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -422,6 +425,48 @@ class Device:
         re, im, rec = np.empty((n1, n1)), np.empty((n1, n1)), np.empty(n1 + _lib.C["QD_SPHARM_STATS"])
         self.call("qd_spharm_analyse", x, re, im, rec)
         return re + 1j * im, rec
+
+    # ---- eddy statistics (qd_eddy.hip)
+    def eddy_configure(self, fields, pairs):
+        """fields: names of distinct f64 planes; pairs: [(p, q)] indices into them (p == q: a variance).  An empty field list
+        releases the lane."""
+        if not len(fields):
+            self.call("qd_eddy_configure", 0, None, 0, None, None)
+            self._eddy = (0, 0)
+            return
+        self.call("qd_eddy_configure", len(fields), [F[n] for n in fields], len(pairs), [int(a) for a, _ in pairs], [int(b) for _, b in pairs])
+        self._eddy = (len(fields), len(pairs))
+
+    def eddy_schedule(self, sample):
+        self.call("qd_eddy_schedule", np.size(sample), sample)
+
+    def eddy_sample(self):
+        """One sample of every field and pair from the planes as they stand (the class seam)."""
+        self.flush()
+        self.call("qd_eddy_sample")
+
+    def eddy_read(self):
+        """-> (anchors [F][n_lat][n_lon], sums [F][n_lat][n_lon], pair sums [P][n_lat][n_lon], sample count)"""
+        nf, npair = self._eddy
+        r, s, c = (np.empty((n,) + self.shape, dtype=np.float64) for n in (nf, nf, npair))
+        return r, s, c, self.call("qd_eddy_read", r, s, c, OUT)
+
+    def eddy_restore(self, anchors, sums, pair_sums, count):
+        """The inverse of eddy_read, for an exact resume."""
+        nf, npair = self._eddy
+        for name, a, n in (("anchors", anchors, nf), ("sums", sums, nf), ("pair_sums", pair_sums, npair)):
+            if np.shape(a) != (n,) + self.shape:
+                raise ValueError(f"eddy_restore: expected {name} of shape {(n,) + self.shape}, got {np.shape(a)}")
+        self.call("qd_eddy_restore", anchors, sums, pair_sums, count)
+
+    def eddy_zonal(self):
+        """-> [P][4][n_lat]: per pair and row the sums over the columns of S_p, S_q, C and S_p * S_q (k_eddy_zonal)"""
+        out = np.empty((self._eddy[1], _lib.C["QD_EDDY_ZONAL_SUMS"], self.shape[0]), dtype=np.float64)
+        self.call("qd_eddy_zonal", out)
+        return out
+
+    def eddy_reset(self):
+        self.call("qd_eddy_reset")
 
     # ---- Lagrangian drifters (qd_drift.hip)
     def drift_configure(self, atm, ocn, sample_atm, sample_ocn, sec_row):
@@ -856,7 +901,7 @@ class Device:
     def digest(self, names):
         """The 64-bit digests of resident planes (include/qingdai_hip.h: qd_state_digest), one launch per 64 of them -> np.uint64[n].
         names: what _lib.state_ref takes -- field names, LAND_MASK, ICE_MASK, ROUTE_BUFFER, ROUTE_FLOW, ROUTE_LAKES, ECO_LAI_STACK,
-        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, FLOW_SUMS, SPHARM_SUMS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
+        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, FLOW_SUMS, SPHARM_SUMS, EDDY_SUMS, EDDY_ANCHORS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
         self.flush()
         refs = [_lib.state_ref(n) for n in names]
         out = np.zeros(len(refs), dtype=np.uint64)

@@ -178,6 +178,14 @@ lane (qingdai_amd/spharm.py, qd_spharm_*) whose records -- power per total waven
 until the chunk ends; under QD_SPHARM_2D=1 (default) the terms c_m |x_n^m|^2 are also summed in resident planes.  A chunk ends with a
 window's last step, behind which <QD_OUTPUT_DIR>/spharm/spharm_day_{a}_{b}.nc is written and one [SphSpec] line printed.  The normal
 end of main writes the open window with complete = 0; under QD_CHECKPOINT=1 the checkpoint carries it instead.
+Eddy statistics (QD_EDDY=1, default 0; nothing the reference has): on every QD_EDDY_SAMPLE_EVERY-th (default 4) step of a window of
+QD_EDDY_EVERY_DAYS (default 10) planet-days -- history's window clock -- the fields named by the pairs of QD_EDDY_PAIRS (default
+U*V,V*TS,V*Q,V*H,U*U,V*V,H*H,TS*TS; names through history's field table, PRECIP and derived entries refused) give, per cell, their
+deviations from an anchor and the products of the pairs, added to resident planes by a twelfth span lane (qingdai_amd/eddy.py,
+qd_eddy_*; one launch per sampled step, behind the step's last).  A chunk ends with a window's last step, behind which
+<QD_OUTPUT_DIR>/eddy/eddy_day_{a}_{b}.nc (per pair the zonal-mean total, mean meridional, stationary and transient parts over lat,
+with QD_EDDY_MAPS=1 the transient covariance and the time means as maps) is written and one [Eddy] line printed.  The normal end of
+main writes the open window with complete = 0; under QD_CHECKPOINT=1 the checkpoint carries it instead.
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -283,6 +291,7 @@ class Simulation:
     drifters = None                        # enable_drifters (QD_DRIFTERS=1)
     flow = None                            # enable_flow (QD_FLOW=1)
     spharm = None                          # enable_spharm (QD_SPHARM=1)
+    eddy = None                            # enable_eddy (QD_EDDY=1)
     truecolor = stateframe = figures = None
     plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
     _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
@@ -874,7 +883,7 @@ class Simulation:
         window's file is written (the sums then start the next window from zero); under QD_SERIES=1 likewise with its windows."""
         hist, ser, spc = self.history, self.series, getattr(self, "spectra", None)
         dri, flw = getattr(self, "drifters", None), getattr(self, "flow", None)
-        sph = getattr(self, "spharm", None)
+        sph, edd = getattr(self, "spharm", None), getattr(self, "eddy", None)
         while n > 0:
             k = n if hist is None else min(n, hist.steps_to_window_end())
             if ser is not None:
@@ -887,12 +896,16 @@ class Simulation:
                 k = min(k, flw.steps_to_window_end())
             if sph is not None:
                 k = min(k, sph.steps_to_window_end())
+            if edd is not None:
+                k = min(k, edd.steps_to_window_end())
             self._run_lanes(k, energy_diag)
             n -= k
             if flw is not None and flw.window_closed():
                 self.flush_flow()
             if sph is not None and sph.window_closed():
                 self.flush_spharm()
+            if edd is not None and edd.window_closed():
+                self.flush_eddy()
             if hist is not None and hist.window_closed():
                 self.flush_history()
             if ser is not None and ser.window_closed():
@@ -932,6 +945,11 @@ class Simulation:
         failure is reported and the window is dropped: output never stops the run."""
         return self._nonfatal(lambda: self.spharm.flush(complete=complete), "[SphSpec] window skipped: {}", cleanup=self.spharm.drop)
 
+    def flush_eddy(self, complete=1):
+        """Write the eddy window that stands in the device's planes -> the path or None.  A failure is reported and the window is
+        dropped (the next one starts from zero): output never stops the run."""
+        return self._nonfatal(lambda: self.eddy.flush(complete=complete), "[Eddy] window skipped: {}", cleanup=self.eddy.drop)
+
     def _run_lanes(self, n, energy_diag=False):
         """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
         individuals')."""
@@ -945,7 +963,7 @@ class Simulation:
                                    ("eco_daily", eco_daily), ("history", self.history), ("series", self.series),
                                    ("spectra", getattr(self, "spectra", None)),
                                    ("drifters", getattr(self, "drifters", None)), ("flow", getattr(self, "flow", None)),
-                                   ("spharm", getattr(self, "spharm", None))) if p is not None}
+                                   ("spharm", getattr(self, "spharm", None)), ("eddy", getattr(self, "eddy", None))) if p is not None}
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
         # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
@@ -1036,6 +1054,15 @@ class Simulation:
         self.spharm = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
                                dt=float(self.dt), day=self.day_seconds)
         return self.spharm
+
+    def enable_eddy(self, env=None):
+        """QD_EDDY=1: covariances and transports of the selected pairs of fields, accumulated by a device lane and written per
+        window to <QD_OUTPUT_DIR>/eddy/ (qingdai_amd/eddy.py) -> the Eddy or None.  The run-local step index the windows count on
+        starts where this is called."""
+        from .eddy import from_env
+        self.eddy = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
+                             dt=float(self.dt), day=self.day_seconds)
+        return self.eddy
 
     def enable_drifters(self, env=None):
         """QD_DRIFTERS=1: Lagrangian drifters on the winds and the currents, advanced by a device lane on every step and written per
@@ -1318,6 +1345,8 @@ def main(argv=None):
         sim.enable_flow(env)
     if getattr(sim, "enable_spharm", None) is not None:        # (likewise)
         sim.enable_spharm(env)
+    if getattr(sim, "enable_eddy", None) is not None:          # (likewise)
+        sim.enable_eddy(env)
     if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
         try:
             sim.load_checkpoint(ck_file, env)
@@ -1411,6 +1440,8 @@ def main(argv=None):
         sim.flush_flow(complete=0)                             # and the open flow window
     if getattr(sim, "spharm", None) is not None and not (ck["enabled"] and autosave_on):
         sim.flush_spharm(complete=0)                           # and the open spherical-harmonic window
+    if getattr(sim, "eddy", None) is not None and not (ck["enabled"] and autosave_on):
+        sim.flush_eddy(complete=0)                             # and the open eddy window
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")
