@@ -1000,6 +1000,43 @@ int qd_eddy_restore(qd_handle h, const double* anchors, const double* sums, cons
 int qd_eddy_zonal(qd_handle h, double* out);
 int qd_eddy_reset(qd_handle h);                                         /* sums and count zeroed, schedule forgotten: the next sample is a window's first */
 
+/* ---- extremes, spells and distributions (QD_EXTREMES), whole-globe handles -----------------------------------------------------
+ * Nothing the reference has.  A span lane of history's kind (no flag bit, no log, early and late sampling places): a configuration
+ * names E <= QD_EXTREMES_MAX_ENTRIES entries (op, a, b) as the history accumulators take them, T <= QD_EXTREMES_MAX_THRESHOLDS
+ * thresholds (entry, cmp, value) and B <= QD_EXTREMES_MAX_HISTS binned entries, each with nb + 1 strictly increasing finite edges,
+ * 1 <= nb <= QD_EXTREMES_MAX_BINS.  Resident, reset at a window's start; k is the 0-based index of the sample in its window:
+ *   per entry and cell      vmax, vmin (f64, -inf / +inf), tmax, tmin (i32, -1), nan (i32, 0):
+ *                           if (x > vmax) { vmax = x; tmax = k; }  if (x < vmin) { vmin = x; tmin = k; }  nan += (x != x)
+ *   per threshold and cell  one 16-byte item {count, run, longest, spells} (u32, 0): hit = x cmp value (false for a NaN);
+ *                           spells += hit && run == 0; run = hit ? run + 1 : 0; count += hit; longest = max(longest, run)
+ *   per binned entry, row   hist[nb + 3] (i64, 0), columns [under, bin 0 .. bin nb - 1, over, nan]: a NaN to nan, x < e_0 to under,
+ *                           x >= e_nb to over, anything else to the bin np.searchsorted(edges, x, side="right") - 1
+ * Selections and integer counts only: the state does not depend on the launch geometry (the top of qingdai_amd/csrc/qd_extremes.hip
+ * is the definition, extremes.accumulate_reference its restatement).  At most two launches on a sampled step, none otherwise. */
+#define QD_EXTREMES_MAX_ENTRIES 16
+#define QD_EXTREMES_MAX_THRESHOLDS 16
+#define QD_EXTREMES_MAX_HISTS 8
+#define QD_EXTREMES_MAX_BINS 256
+#define QD_EXTREMES_CMP_LT 60                            /* '<' */
+#define QD_EXTREMES_CMP_GT 62                            /* '>' */
+/* op, a, b [n_entries]: as qd_history_configure; thr_entry, thr_cmp, thr_value [n_thresholds]: an index into the entries, one of
+ * QD_EXTREMES_CMP_*, a finite value; hist_entry, hist_nb [n_hists]: an index into the entries and the bin count; edges: the
+ * sum(nb + 1) edges of all tables, one behind the other.  Allocates the state at its start values; forgets an earlier configuration;
+ * n_entries == 0 only releases.  Refused, each with one line that begins "extremes:": latitude bands, more entries, thresholds,
+ * histograms or bins than the limits, what the entry table refuses, a threshold or histogram whose entry index is out of range, a cmp
+ * that is neither, a non-finite threshold, fewer than 2 edges, edges that are not finite and strictly increasing. */
+int qd_extremes_configure(qd_handle h, int n_entries, const int32_t* op, const int32_t* a, const int32_t* b, int n_thresholds,
+                          const int32_t* thr_entry, const int32_t* thr_cmp, const double* thr_value, int n_hists,
+                          const int32_t* hist_entry, const int32_t* hist_nb, const double* edges);
+int qd_extremes_schedule(qd_handle h, int steps, const int32_t* sample);   /* the next qd_step_n span: non-zero = the step is sampled */
+int qd_extremes_sample(qd_handle h);                                    /* class seam: one sample of every entry now, k = the lane's count */
+/* values [2][E][n_lat][n_lon] (vmax, vmin); counts [3][E][n_lat][n_lon] (tmax, tmin, nan); thresholds [T][n_lat][n_lon][4] (count, run,
+ * longest, spells; u32 carried as int32); hist: per binned entry [n_lat][nb + 3], one behind the other; and the samples in them */
+int qd_extremes_read(qd_handle h, double* values, int32_t* counts, int32_t* thresholds, int64_t* hist, int64_t* count);
+int qd_extremes_restore(qd_handle h, const double* values, const int32_t* counts, const int32_t* thresholds, const int64_t* hist,
+                        int64_t count);                                   /* its inverse (QD_CHECKPOINT) */
+int qd_extremes_reset(qd_handle h);                                     /* start values, count 0, schedule forgotten: the next sample is a window's first */
+
 /* ---- state digest and exact resume (QD_CHECKPOINT), whole-globe handles ---------------------------------------------------
  * Nothing the reference has: its restart file holds 14 planes as f4 and a resumed run does not continue the run that was stopped.
  * qd_state_digest: a 64-bit digest of resident planes, all of them in ONE launch.  The digest of a plane of n elements is
@@ -1024,6 +1061,9 @@ enum qd_state_ref {
 #define QD_STATE_REF_SPHARM_SUMS 502                    /* and the 2D sums of the spherical-harmonic lane, [n][N + 1][N + 1] as ONE plane */
 #define QD_STATE_REF_EDDY_SUMS 503                      /* and the eddy lane's first-moment and pair sums, [F + P] planes of even stride as ONE plane */
 #define QD_STATE_REF_EDDY_ANCHORS 504                   /* and its anchors, [F] planes of even stride as ONE plane */
+#define QD_STATE_REF_EXTREMES_VALUES 505                /* and the extremes lane's vmax and vmin, [2][E] f64 planes as ONE plane */
+#define QD_STATE_REF_EXTREMES_COUNTS 506                /* and every 4-byte plane of it, [T][cells][4] thresholds then [3][E] tmax / tmin / nan, as ONE plane */
+#define QD_STATE_REF_EXTREMES_HIST 507                  /* and its histograms, the i64 tables one behind the other, as ONE plane */
 #define QD_STATE_DIGEST_MAX 64
 /* n <= 64 refs -> out[n].  Refused: latitude bands, an unknown ref, a ref whose subsystem is not configured (the line names it). */
 int qd_state_digest(qd_handle h, int n, const int32_t* refs, uint64_t* out);

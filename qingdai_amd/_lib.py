@@ -195,7 +195,7 @@ STATE_REF_COUNT = {"PHYTO_TRACER": C["QD_STATE_REF_TRACERS"], "HISTORY_SUM": C["
 def state_ref(name):
     """A plane's name -> the ref qd_state_digest takes: a field name of F (f64 fields and the two masks), a name of STATE_REFS, or
     an indexed one, "PHYTO_TRACER:s" / "HISTORY_SUM:k", or "SPECTRA_SUMS" / "FLOW_SUMS" / "SPHARM_SUMS" / "EDDY_SUMS" /
-    "EDDY_ANCHORS"."""
+    "EDDY_ANCHORS" / "EXTREMES_VALUES" / "EXTREMES_COUNTS" / "EXTREMES_HIST"."""
     if name in FIELDS or name in ("LAND_MASK", "ICE_MASK"):
         return F[name]
     if name == "SPECTRA_SUMS":                        # a ref of its own beside the enum (QD_STATE_REF_SPECTRA_SUMS)
@@ -205,6 +205,8 @@ def state_ref(name):
     if name == "SPHARM_SUMS":                         # likewise (QD_STATE_REF_SPHARM_SUMS)
         return C["QD_STATE_REF_SPHARM_SUMS"]
     if name in ("EDDY_SUMS", "EDDY_ANCHORS"):         # likewise (QD_STATE_REF_EDDY_SUMS, QD_STATE_REF_EDDY_ANCHORS)
+        return C["QD_STATE_REF_" + name]
+    if name in ("EXTREMES_VALUES", "EXTREMES_COUNTS", "EXTREMES_HIST"):     # likewise (QD_STATE_REF_EXTREMES_*)
         return C["QD_STATE_REF_" + name]
     base, _, idx = str(name).partition(":")
     if base in STATE_REF_COUNT and idx.isdigit() and int(idx) < STATE_REF_COUNT[base]:

@@ -21,6 +21,10 @@ The file (one NetCDF file through ncio.write_nc, f8 / u1 / i8 only; written to a
                       continues (QD_SPHARM=1 only); the 2D sum planes (QD_SPHARM_2D=1) are resident and digested as SPHARM_SUMS
   eddy_anchors, eddy_sums, eddy_pair_sums, eddy_clock {i, t_first, t_last, n_open, count}   an open eddy window continues (QD_EDDY=1
                       only); the planes are resident and digested as EDDY_ANCHORS and EDDY_SUMS (sums and pair sums as one plane)
+  extremes_values [2][E] (vmax, vmin), extremes_counts [3][E] (tmax, tmin, nan; i4), extremes_thresholds [T][lat][lon][4] (i4: the
+                      u32 words), extremes_hist (every table, one behind the other), extremes_clock {i, t_first, t_last, n_open,
+                      count}   an open extremes window continues (QD_EXTREMES=1 only); digested as EXTREMES_VALUES,
+                      EXTREMES_COUNTS (thresholds, then counts, as one plane of 4-byte words) and EXTREMES_HIST
   drift_atm, drift_ocn, drift_records, drift_times, drift_steps, drift_clock {i, records}   the drifters' particle state (r | c |
                       status [| blocked], f8) and their open window (QD_DRIFTERS=1 only)
   atm_counter, ocn_counter, step_index, span_mark {step index, atm counter at the last span's end}, t_seconds, t_origin {t0, steps
@@ -174,6 +178,9 @@ def subsystems(sim):
     edd = getattr(sim, "eddy", None)
     if edd is not None:                 # and the eddy lane's
         extra["eddy"] = edd.key()
+    ext = getattr(sim, "extremes", None)
+    if ext is not None:                 # and the extremes lane's
+        extra["extremes"] = ext.key()
     return {**{"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
             "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
             "phyto_daily": str(int(sim.phyto_daily is not None)),
@@ -206,6 +213,9 @@ def plane_names(sim):
         names.append("SPHARM_SUMS")
     if getattr(sim, "eddy", None) is not None:
         names += ["EDDY_SUMS", "EDDY_ANCHORS"]
+    ext = getattr(sim, "extremes", None)
+    if ext is not None:
+        names += ["EXTREMES_VALUES", "EXTREMES_COUNTS"] + (["EXTREMES_HIST"] if ext.hists else [])
     return names
 
 
@@ -351,6 +361,18 @@ def collect(sim):
         v["eddy_sums"] = ("f8", ("eddy_field", "lat", "lon"), sums)
         v["eddy_pair_sums"] = ("f8", ("eddy_pair", "lat", "lon"), pair_sums)
         v["eddy_clock"] = ("f8", ("five",), np.array([float(edd.i), _nan(edd.t_first), _nan(edd.t_last), float(edd.n_open), float(count)]))
+    ext = getattr(sim, "extremes", None)
+    if ext is not None:
+        st = dev.extremes_read()
+        hist = np.concatenate([h.reshape(-1) for h in st["hist"]]) if st["hist"] else np.zeros(1, dtype=np.int64)
+        dims["extremes_entry"], dims["extremes_threshold"], dims["extremes_hist"] = int(st["vmax"].shape[0]), max(1, int(st["thr"].shape[0])), int(hist.size)
+        dims["four"] = 4
+        thr = st["thr"].view(np.int32) if st["thr"].shape[0] else np.zeros((1,) + st["thr"].shape[1:], dtype=np.int32)
+        v["extremes_values"] = ("f8", ("two", "extremes_entry", "lat", "lon"), np.stack([st["vmax"], st["vmin"]]))
+        v["extremes_counts"] = ("i4", ("three", "extremes_entry", "lat", "lon"), np.stack([st["tmax"], st["tmin"], st["nan"]]))
+        v["extremes_thresholds"] = ("i4", ("extremes_threshold", "lat", "lon", "four"), thr)
+        v["extremes_hist"] = (_i8(), ("extremes_hist",), hist)
+        v["extremes_clock"] = ("f8", ("five",), np.array([float(ext.i), _nan(ext.t_first), _nan(ext.t_last), float(ext.n_open), float(st["n"])]))
     dri = getattr(sim, "drifters", None)
     if dri is not None:                                        # the particles as they stand, and the open window's records so far
         recs, times, steps = dri.window()
@@ -437,6 +459,14 @@ class CheckpointFile:
             keys = ("eddy_sums", "eddy_pair_sums") if name == "EDDY_SUMS" else ("eddy_anchors",)
             planes = np.concatenate([np.asarray(v[k], dtype=np.float64).reshape(np.shape(v[k])[0], -1) for k in keys])
             return np.pad(planes, ((0, 0), (0, planes.shape[1] & 1)))
+        if name == "EXTREMES_VALUES":
+            return np.asarray(v["extremes_values"], dtype=np.float64)
+        if name == "EXTREMES_COUNTS":                              # every 4-byte plane as one: the thresholds (as far as there are any), then the counts
+            n_thr = len([t for t in self.subsystems().get("extremes", "||").split("|")[1].split(",") if t])
+            thr = np.asarray(v["extremes_thresholds"]).astype(np.int32)[:n_thr]
+            return np.concatenate([thr.reshape(-1), np.asarray(v["extremes_counts"]).astype(np.int32).reshape(-1)])
+        if name == "EXTREMES_HIST":
+            return np.asarray(v["extremes_hist"]).astype(np.int64)
         key = {"PHYTO_TRACER": "phyto_C", "HISTORY_SUM": "hist_sums"}.get(base)
         if key is not None:
             return np.asarray(v[key], dtype=np.float64)[int(idx)]
@@ -502,6 +532,9 @@ def check_subsystems(f, sim):
     if got.get("eddy", "-") != want.get("eddy", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the eddy lane is '{got.get('eddy', '-')}' in the file and "
                                 f"'{want.get('eddy', '-')}' in this run")
+    if got.get("extremes", "-") != want.get("extremes", "-"):
+        raise CheckpointRefused(f"the subsystem set differs: the extremes lane is '{got.get('extremes', '-')}' in the file and "
+                                f"'{want.get('extremes', '-')}' in this run")
     if got.get("drifters", "-") != want.get("drifters", "-"):
         raise CheckpointRefused(f"the subsystem set differs: the drifters lane is '{got.get('drifters', '-')}' in the file and "
                                 f"'{want.get('drifters', '-')}' in this run")
@@ -557,6 +590,8 @@ def _file_plane_names(f):
         names.append("SPHARM_SUMS")
     if "eddy_sums" in v:
         names += ["EDDY_SUMS", "EDDY_ANCHORS"]
+    if "extremes_values" in v:
+        names += ["EXTREMES_VALUES", "EXTREMES_COUNTS"] + (["EXTREMES_HIST"] if "digest_EXTREMES_HIST" in f.attrs else [])
     return names
 
 
@@ -661,6 +696,18 @@ def load(sim, path, env=None, out=print):
         dev.eddy_restore(np.asarray(v["eddy_anchors"], dtype=np.float64), np.asarray(v["eddy_sums"], dtype=np.float64),
                          np.asarray(v["eddy_pair_sums"], dtype=np.float64), int(clock[4]))
         e.i, e.t_first, e.t_last, e.n_open = int(clock[0]), _none(clock[1]), _none(clock[2]), int(clock[3])
+    if getattr(sim, "extremes", None) is not None:
+        x, clock = sim.extremes, np.asarray(v["extremes_clock"], dtype=np.float64)
+        values, counts = np.asarray(v["extremes_values"], dtype=np.float64), np.asarray(v["extremes_counts"]).astype(np.int32)
+        thr = np.ascontiguousarray(np.asarray(v["extremes_thresholds"]).astype(np.int32)[:len(x.thresholds)]).view(np.uint32)
+        flat, tables, o = np.asarray(v["extremes_hist"]).astype(np.int64), [], 0
+        for _, edges in x.hists:
+            w = edges.size - 1 + 3
+            tables.append(flat[o:o + values.shape[2] * w].reshape(values.shape[2], w))
+            o += values.shape[2] * w
+        dev.extremes_restore({"vmax": values[0], "vmin": values[1], "tmax": counts[0], "tmin": counts[1], "nan": counts[2],
+                              "thr": thr, "hist": tables, "n": int(clock[4])})
+        x.i, x.t_first, x.t_last, x.n_open = int(clock[0]), _none(clock[1]), _none(clock[2]), int(clock[3])
     dri = getattr(sim, "drifters", None)
     if dri is not None:
         clock = np.asarray(v["drift_clock"], dtype=np.float64)

@@ -490,6 +490,7 @@ extern "C" int qd_destroy(qd_handle c) {
     qd_flow_release(c);
     qd_spharm_release(c);
     qd_eddy_release(c);
+    qd_extremes_release(c);
     for (int f = 0; f < QD_F_COUNT_F64; ++f) if (c->f[f]) hipFree(c->f[f]);
     for (int s = 0; s < QD_NSCRATCH; ++s) if (c->scratch[s]) hipFree(c->scratch[s]);
     for (double* t : c->tab_alloc) hipFree(t);
@@ -742,6 +743,10 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
     const bool with_eddy = qd_eddy_scheduled(c);
     if (with_eddy && !(span.lane[QD_LANE_EDDY] = qd_eddy_span_begin(c, n))) return -1;
     const bool eddy_lazy = with_eddy && qd_eddy_reads_lazy(c);
+    // extremes, spells and distributions (qd_extremes.hip): history's two sampling places, at most two launches on a sampled step
+    const bool with_ext = qd_extremes_scheduled(c);
+    if (with_ext && !(span.lane[QD_LANE_EXTREMES] = qd_extremes_span_begin(c, n))) return -1;
+    const bool ext_lazy = with_ext && qd_extremes_reads_lazy(c);
     span.begun = true;
     for (int s = 0; s < n; ++s) {
         const double* st = stars + (size_t)7 * s;
@@ -760,6 +765,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (spharm_fire && (rc = qd_spharm_begin_step(c))) return rc;
         const bool drift_rec = with_drift && span.lane[QD_LANE_DRIFT]->at(s) != 0.0;
         const bool eddy_fire = with_eddy && span.lane[QD_LANE_EDDY]->at(s) != 0.0;
+        const bool ext_fire = with_ext && span.lane[QD_LANE_EXTREMES]->at(s) != 0.0;
         // PhytoManager.step_daily (run_simulation.py:2051-2061) reads only this step's insolation (in registers), the tracers and SST / T_s
         // as the previous step left them: at the top of the step, so that its WATER_ALPHA reaches this step's albedo launch
         if (with_pdaily && span.lane[QD_LANE_PHYTO_DAILY]->at(s) != 0.0 && (rc = qd_phyto_daily_step_impl(c, st, with_ocean ? 1 : 0))) return rc;
@@ -781,7 +787,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         // lazy diagnostics: inside a span only the last step stores what nothing inside a span reads -- unless a reader comes with the flags
         c->diag_write = (!c->lazy_diag || s == n - 1 || with_hydro || with_eco || with_phyto || want_diag || bd_main || (hist_fire && hist_lazy) ||
                          (series_fire && series_lazy) || (spectra_fire && spectra_lazy) || (drift_rec && drift_lazy) ||
-                         (spharm_fire && spharm_lazy) || (eddy_fire && eddy_lazy)) ? 1 : 0;
+                         (spharm_fire && spharm_lazy) || (eddy_fire && eddy_lazy) || (ext_fire && ext_lazy)) ? 1 : 0;
         if (with_phys) {
             const int part = c->precip_done ? 2 : 0;         // the precipitation block may have run inside the previous ocean step
             c->precip_done = 0;
@@ -812,6 +818,7 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (with_ocean && want_diag && s == 0 && (rc = qd_energy_diag_impl(c, c->last_diag))) return rc;
         // history: PRECIP is this step's until the block below overwrites it with the next step's -- its entries are sampled here
         if (hist_fire && (rc = qd_history_accumulate(c, 0))) return rc;
+        if (ext_fire && (rc = qd_extremes_accumulate(c, 0))) return rc;
         if (series_fire && (rc = qd_series_reduce(c, 0))) return rc;
         if (spectra_fire && (rc = qd_spectra_transform(c, 0))) return rc;
         if (spharm_fire && (rc = qd_spharm_transform(c, 0))) return rc;
@@ -844,6 +851,8 @@ extern "C" int qd_step_n(qd_handle c, int n, double dt, int flags, const double*
         if (spharm_fire && (rc = qd_spharm_transform(c, 1))) return rc;
         // eddy statistics: every field as the step leaves it
         if (eddy_fire && (rc = qd_eddy_accumulate(c))) return rc;
+        // extremes: every entry but PRECIP's as the step leaves it
+        if (ext_fire && (rc = qd_extremes_accumulate(c, 1))) return rc;
     }
     c->diag_write = 1;
     return qd_launch_check(c, "qd_step_n");

@@ -74,7 +74,9 @@ static const char* dg_ref_name(int ref, char* buf, size_t nb) {
                                  ref == QD_SR_ECO_LAI_STACK ? "ECO_LAI_STACK" : ref == QD_SR_INDIV_E_DAY ? "INDIV_E_DAY" :
                                  ref == QD_SR_INDIV_STRESS ? "INDIV_STRESS" : ref == QD_STATE_REF_SPECTRA_SUMS ? "SPECTRA_SUMS" :
                                  ref == QD_STATE_REF_FLOW_SUMS ? "FLOW_SUMS" : ref == QD_STATE_REF_SPHARM_SUMS ? "SPHARM_SUMS" :
-                                 ref == QD_STATE_REF_EDDY_SUMS ? "EDDY_SUMS" : ref == QD_STATE_REF_EDDY_ANCHORS ? "EDDY_ANCHORS" : "?");
+                                 ref == QD_STATE_REF_EDDY_SUMS ? "EDDY_SUMS" : ref == QD_STATE_REF_EDDY_ANCHORS ? "EDDY_ANCHORS" :
+                                 ref == QD_STATE_REF_EXTREMES_VALUES ? "EXTREMES_VALUES" : ref == QD_STATE_REF_EXTREMES_COUNTS ? "EXTREMES_COUNTS" :
+                                 ref == QD_STATE_REF_EXTREMES_HIST ? "EXTREMES_HIST" : "?");
     return buf;
 }
 
@@ -126,6 +128,11 @@ static int dg_resolve(qd_ctx* c, int ref, QdDigestEntry* e) {
         if (!qd_eddy_planes(c, &anchors, &na, &sums, &ns)) { why = "the eddy statistics are not configured (qd_eddy_configure)"; n = cells; }
         else if (ref == QD_STATE_REF_EDDY_SUMS) { p = sums; n = ns; }
         else { p = anchors; n = na; }
+    } else if (ref == QD_STATE_REF_EXTREMES_VALUES || ref == QD_STATE_REF_EXTREMES_COUNTS || ref == QD_STATE_REF_EXTREMES_HIST) {
+        const int which = ref - QD_STATE_REF_EXTREMES_VALUES;
+        if (!qd_extremes_planes(c, which, &p, &n)) { why = "the extremes lane is not configured (qd_extremes_configure)"; n = cells; }
+        else if (!p) why = "the extremes lane has no histogram";
+        else esz = which == 1 ? 4 : 8;
     } else {
         return qd_fail(c, ("qd_state_digest: unknown ref " + std::to_string(ref)).c_str());
     }

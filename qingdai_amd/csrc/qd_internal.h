@@ -217,6 +217,7 @@ struct qd_ctx {
     struct QdSpectra* spectra = nullptr;     // zonal spectra: entry table, twiddles, row powers, sum planes, record log, schedule (qd_spectra.hip)
     struct QdFlow* flow = nullptr;           // streamfunction / velocity potential: tables, work and sum planes, record log, schedule (qd_flow.hip)
     struct QdSpharm* spharm = nullptr;       // spherical-harmonic spectra: entry table, host tables, work and sum planes, record log, schedule (qd_spharm.hip)
+    struct QdExtremes* extremes = nullptr;   // extremes, spells and distributions: entry, threshold and histogram tables, resident state, sample count, schedule (qd_extremes.hip)
     struct QdEddy* eddy = nullptr;           // eddy statistics: field and pair tables, anchor / sum / pair-sum planes, sample count, schedule (qd_eddy.hip)
     struct QdDrift* drift = nullptr;         // Lagrangian drifters: particle state, metric table, record log, schedule (qd_drift.hip)
     unsigned long long* digest_out = nullptr; // [64] results of qd_state_digest, allocated at its first call (qd_digest.hip)
@@ -585,6 +586,14 @@ struct QdSpanLane* qd_eddy_span_begin(qd_ctx* c, int n);
 int  qd_eddy_accumulate(qd_ctx* c);
 // the anchors [F] and the sums [F + P], each group as one plane of n doubles (qd_state_digest)
 bool qd_eddy_planes(const qd_ctx* c, const double** anchors, size_t* n_anchors, const double** sums, size_t* n_sums);
+// qd_extremes.hip: history's protocol and sampling places; group 0: the early entries, 1: the late ones (the count moves on), 2: all
+void qd_extremes_release(qd_ctx* c);
+bool qd_extremes_scheduled(const qd_ctx* c);
+bool qd_extremes_reads_lazy(const qd_ctx* c);
+struct QdSpanLane* qd_extremes_span_begin(qd_ctx* c, int n);
+int  qd_extremes_accumulate(qd_ctx* c, int group);
+// which: 0 the f64 planes, 1 every 4-byte plane, 2 the i64 histograms -> the group as one plane of n elements (qd_state_digest)
+bool qd_extremes_planes(const qd_ctx* c, int which, const void** p, size_t* n);
 // what qd_state_digest and the exact resume (qd_digest.hip) need from the feature modules: their resident planes, and their firing
 // counts (set >= 0 stores it; -> the count as it then stands, 0 when the module is not configured)
 bool qd_route_planes(const qd_ctx* c, const double** buf, const double** flow, const double** lakes, int* n_lakes);    // qd_route.hip

@@ -9,7 +9,8 @@
 // scheduled for advances the particles, and the schedule value says whether the step also leaves a record; its cap follows the
 // record size.  The flow lane (qd_flow.hip: streamfunction and velocity potential) is a lane of the spectra's kind, QD_FLOW_LOG_CAP,
 // and so are the spherical-harmonic spectra (qd_spharm.hip), QD_SPHARM_LOG_CAP.  The eddy statistics (qd_eddy.hip) are a lane of
-// history's kind: resident sum planes, no log (width 0).
+// history's kind: resident sum planes, no log (width 0); so are the extremes, spells and distributions (qd_extremes.hip), whose
+// resident planes hold selections and integer counts, sampled at history's two places.
 //   qd_X_schedule           qd_lane_schedule: one value per step of the NEXT span, 0 = the step does not fire
 //   qd_step_n, before work  qd_lane_span_begin: exactly n steps scheduled, and their firings fit into the log behind the cursor
 //   qd_step_n, step s       at(s) != 0: X runs (not when full()) and writes its record at next()
@@ -20,7 +21,7 @@
 #include "qd_internal.h"
 
 // QD_SPAN_LOG_CAP, the records a lane holds between two drains, is the public header's (the host sizes its drain buffers by it)
-enum { QD_LANE_ROUTE = 0, QD_LANE_PHYTO_DAILY, QD_LANE_ECO_DAILY, QD_LANE_INDIV_DAILY, QD_LANE_BUDGET, QD_LANE_HISTORY, QD_LANE_SERIES, QD_LANE_SPECTRA, QD_LANE_DRIFT, QD_LANE_FLOW, QD_LANE_SPHARM, QD_LANE_EDDY, QD_N_LANES };
+enum { QD_LANE_ROUTE = 0, QD_LANE_PHYTO_DAILY, QD_LANE_ECO_DAILY, QD_LANE_INDIV_DAILY, QD_LANE_BUDGET, QD_LANE_HISTORY, QD_LANE_EXTREMES, QD_LANE_SERIES, QD_LANE_SPECTRA, QD_LANE_DRIFT, QD_LANE_FLOW, QD_LANE_SPHARM, QD_LANE_EDDY, QD_N_LANES };
 
 struct QdSpanLane {
     double* log = nullptr;          // device, [cap][width]; the subsystem sets width (and cap), allocates and frees it

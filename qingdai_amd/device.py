@@ -30,6 +30,7 @@ class Device:
     _spharm_n = _spharm_N = 0 # entries and truncation of the last spharm_configure
     _spharm_2d = False        # ... and whether it keeps the 2D sum planes
     _eddy = (0, 0)            # fields and pairs of the last eddy_configure
+    _extremes = (0, 0, ())    # entries, thresholds and the bin counts of the histograms of the last extremes_configure
     _drift = (0, 0, 0, 0)     # n_atm, n_ocn, record width and log capacity of the last drift_configure
     _tiles_n = 1              # tiles of the last tile configuration
     _div_shape = None         # [S, lat, lon] of the last eco_diversity call
@@ -138,7 +139,7 @@ class Device:
 
     def step_n(self, stars, dt, with_ocean=False, with_physics=False, pass_albedo=True, with_hydrology=False, energy_diag=False,
                ecology=False, phyto=False, routing=None, phyto_daily=None, t0=None, eco_daily=None, budget=None, history=None,
-               series=None, spectra=None, drifters=None, flow=None, spharm=None, eddy=None):
+               series=None, spectra=None, drifters=None, flow=None, spharm=None, eddy=None, extremes=None):
         """benchmark_jax.py:124-158 as one resident loop (qd_step_n).  `stars`: [n][7] host
         scalars from ThermalForcing.star_table().  The span lanes, each a participant on this handle whose records stay in its
         device log until the caller has it deliver them: `routing`, a RiverRouting -- bit7, after the hydrology commit (which it
@@ -155,7 +156,8 @@ class Device:
         sampled psi, chi, zeta, delta in resident sum planes (flow_sums).  `spharm`, a spharm.Spharm -- no flag bit: one record of
         spherical-harmonic power spectra per sampled step (spharm_log), the 2D terms in resident sum planes (spharm_sums).  `eddy`, an
         eddy.Eddy -- no flag bit and no log: a sampled step adds the fields' deviations from their anchors and the products of
-        pairs of them to resident planes (eddy_read)."""
+        pairs of them to resident planes (eddy_read).  `extremes`, an extremes.Extremes -- no flag bit and no log: a sampled step
+        updates per-cell extremes, threshold counts and spells, and per-row histograms in resident planes (extremes_read)."""
         self.flush()
         st = _c(stars)
         assert st.ndim == 2 and st.shape[1] == 7
@@ -167,7 +169,7 @@ class Device:
         #   span_restore(clock)       nothing ran (an upload or qd_step_n raised): the clock back to what span_clock gave
         #   _fired(k)                 the span ran: k is what span_schedule returned
         #   span_deliver(dt)          drain the lane's device log and deliver it (print, keep); the caller's move, once per span
-        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters, flow, spharm, eddy) if p is not None]
+        lanes = [p for p in (phyto_daily, routing, eco_daily, budget, history, series, spectra, drifters, flow, spharm, eddy, extremes) if p is not None]
         for p in lanes:
             if p.dev is not self:
                 raise ValueError(f"step_n: the {type(p).__name__} runs on another device handle")
@@ -286,6 +288,69 @@ class Device:
 
     def history_reset(self):
         self.call("qd_history_reset")
+
+    # ---- extremes, spells and distributions (qd_extremes.hip)
+    def extremes_configure(self, entries, thresholds=(), hists=()):
+        """entries: [(op, a, b)] as history_configure takes them; thresholds: [(entry index, '<' or '>', value)]; hists: [(entry
+        index, edges)], nb + 1 strictly increasing finite edges each.  An empty entry list releases the lane."""
+        if not len(entries):
+            self.call("qd_extremes_configure", 0, None, None, None, 0, None, None, None, 0, None, None, None)
+            self._extremes = (0, 0, ())
+            return
+        cmp = [ord(c) if isinstance(c, str) and len(c) == 1 else int(c) for _, c, _ in thresholds]
+        edges = [np.asarray(e, dtype=np.float64).reshape(-1) for _, e in hists]
+        self.call("qd_extremes_configure", len(entries), [e[0] for e in entries], [F[e[1]] for e in entries],
+                  [F[e[2]] if e[2] is not None else -1 for e in entries],
+                  len(thresholds), [int(t[0]) for t in thresholds] or None, cmp or None, [float(t[2]) for t in thresholds] or None,
+                  len(hists), [int(h[0]) for h in hists] or None, [e.size - 1 for e in edges] or None,
+                  np.concatenate(edges) if edges else None)
+        self._extremes = (len(entries), len(thresholds), tuple(e.size - 1 for e in edges))
+
+    def extremes_schedule(self, sample):
+        self.call("qd_extremes_schedule", np.size(sample), sample)
+
+    def extremes_sample(self):
+        """One sample of every entry from the fields as they stand (the class seam); k is the lane's own count."""
+        self.flush()
+        self.call("qd_extremes_sample")
+
+    def extremes_read(self):
+        """-> the lane's state as extremes.accumulate_reference returns it: {vmax, vmin [E][n_lat][n_lon] f64; tmax, tmin, nan
+        [E][n_lat][n_lon] i32; thr [T][n_lat][n_lon][4] u32 (count, run, longest, spells); hist: a list of [n_lat][nb + 3] i64;
+        n: the sample count}"""
+        ne, nt, nbs = self._extremes
+        nlat = self.shape[0]
+        values = np.empty((2, ne) + self.shape, dtype=np.float64)
+        counts = np.empty((3, ne) + self.shape, dtype=np.int32)
+        thr = np.empty((nt,) + self.shape + (4,), dtype=np.int32)
+        hist = np.empty(sum(nlat * (nb + 3) for nb in nbs), dtype=np.int64)
+        n = self.call("qd_extremes_read", values, counts, thr if nt else None, hist if nbs else None, OUT)
+        tables, o = [], 0
+        for nb in nbs:
+            tables.append(hist[o:o + nlat * (nb + 3)].reshape(nlat, nb + 3).copy())
+            o += nlat * (nb + 3)
+        return {"vmax": values[0], "vmin": values[1], "tmax": counts[0], "tmin": counts[1], "nan": counts[2],
+                "thr": thr.view(np.uint32), "hist": tables, "n": int(n)}
+
+    def extremes_restore(self, state):
+        """The inverse of extremes_read, for an exact resume."""
+        ne, nt, nbs = self._extremes
+        nlat = self.shape[0]
+        for name in ("vmax", "vmin", "tmax", "tmin", "nan"):
+            if np.shape(state[name]) != (ne,) + self.shape:
+                raise ValueError(f"extremes_restore: expected {name} of shape {(ne,) + self.shape}, got {np.shape(state[name])}")
+        if np.shape(state["thr"]) != (nt,) + self.shape + (4,):
+            raise ValueError(f"extremes_restore: expected thr of shape {(nt,) + self.shape + (4,)}, got {np.shape(state['thr'])}")
+        if [np.shape(h) for h in state["hist"]] != [(nlat, nb + 3) for nb in nbs]:
+            raise ValueError("extremes_restore: the histogram tables do not have the configured shapes")
+        values = np.stack([np.asarray(state["vmax"], dtype=np.float64), np.asarray(state["vmin"], dtype=np.float64)])
+        counts = np.stack([np.asarray(state[k], dtype=np.int32) for k in ("tmax", "tmin", "nan")])
+        thr = np.ascontiguousarray(state["thr"], dtype=np.uint32).view(np.int32)
+        hist = np.concatenate([np.asarray(h, dtype=np.int64).reshape(-1) for h in state["hist"]]) if nbs else None
+        self.call("qd_extremes_restore", values, counts, thr if nt else None, hist, int(state["n"]))
+
+    def extremes_reset(self):
+        self.call("qd_extremes_reset")
 
     # ---- per-step series (qd_series.hip)
     def series_configure(self, entries, zonal, w_row):
@@ -901,7 +966,7 @@ class Device:
     def digest(self, names):
         """The 64-bit digests of resident planes (include/qingdai_hip.h: qd_state_digest), one launch per 64 of them -> np.uint64[n].
         names: what _lib.state_ref takes -- field names, LAND_MASK, ICE_MASK, ROUTE_BUFFER, ROUTE_FLOW, ROUTE_LAKES, ECO_LAI_STACK,
-        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, FLOW_SUMS, SPHARM_SUMS, EDDY_SUMS, EDDY_ANCHORS, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
+        INDIV_E_DAY, INDIV_STRESS, SPECTRA_SUMS, FLOW_SUMS, SPHARM_SUMS, EDDY_SUMS, EDDY_ANCHORS, EXTREMES_VALUES, EXTREMES_COUNTS, EXTREMES_HIST, "PHYTO_TRACER:s", "HISTORY_SUM:k".  A plane whose subsystem is not configured raises."""
         self.flush()
         refs = [_lib.state_ref(n) for n in names]
         out = np.zeros(len(refs), dtype=np.uint64)

@@ -186,6 +186,16 @@ qd_eddy_*; one launch per sampled step, behind the step's last).  A chunk ends w
 <QD_OUTPUT_DIR>/eddy/eddy_day_{a}_{b}.nc (per pair the zonal-mean total, mean meridional, stationary and transient parts over lat,
 with QD_EDDY_MAPS=1 the transient covariance and the time means as maps) is written and one [Eddy] line printed.  The normal end of
 main writes the open window with complete = 0; under QD_CHECKPOINT=1 the checkpoint carries it instead.
+Extremes, spells and distributions (QD_EXTREMES=1, default 0; nothing the reference has): on every QD_EXTREMES_SAMPLE_EVERY-th
+(default 4) step of a window of QD_EXTREMES_EVERY_DAYS (default 10) planet-days -- history's window clock -- the entries of
+QD_EXTREMES_FIELDS (default TS,PRECIP,WIND_SPEED,H, plus SST with the ocean; history's parser) update, per cell, their maximum and
+minimum with the sample they occurred in and a NaN count; the thresholds of QD_EXTREMES_THRESHOLDS (default
+TS<273.15,PRECIP>1.1574e-5, i.e. freezing and 1 mm/day) their hit count, spell count and longest spell; the binned entries of
+QD_EXTREMES_BINS (default PRECIP:log:1e-8:1e-2:60,TS:lin:150:350:100,WIND_SPEED:lin:0:100:100) a histogram per latitude row -- a
+thirteenth span lane (qingdai_amd/extremes.py, qd_extremes_*; at most two launches per sampled step, at history's two sampling
+places).  A chunk ends with a window's last step, behind which <QD_OUTPUT_DIR>/extremes/extremes_day_{a}_{b}.nc is written and one
+[Extremes] line printed.  The default ranges, thresholds and cadence are guesses (the file carries the under and over shares of every
+histogram).  The normal end of main writes the open window with complete = 0; under QD_CHECKPOINT=1 the checkpoint carries it.
 
 Per iteration (run_simulation.py:1760-2340), all on the device through one qd_step_n call per chunk:
   hybrid precipitation -> clouds -> cloud tracer -> insolation -> P019 lapse/snow -> albedo -> Teq ->
@@ -292,6 +302,7 @@ class Simulation:
     flow = None                            # enable_flow (QD_FLOW=1)
     spharm = None                          # enable_spharm (QD_SPHARM=1)
     eddy = None                            # enable_eddy (QD_EDDY=1)
+    extremes = None                        # enable_extremes (QD_EXTREMES=1)
     truecolor = stateframe = figures = None
     plot_every = None                      # the plot interval in steps, shared by the three outputs above (run_simulation.py:1649-1651)
     _failed = frozenset()                  # the non-fatal outputs whose failure has been reported
@@ -884,6 +895,7 @@ class Simulation:
         hist, ser, spc = self.history, self.series, getattr(self, "spectra", None)
         dri, flw = getattr(self, "drifters", None), getattr(self, "flow", None)
         sph, edd = getattr(self, "spharm", None), getattr(self, "eddy", None)
+        ext = getattr(self, "extremes", None)
         while n > 0:
             k = n if hist is None else min(n, hist.steps_to_window_end())
             if ser is not None:
@@ -898,6 +910,8 @@ class Simulation:
                 k = min(k, sph.steps_to_window_end())
             if edd is not None:
                 k = min(k, edd.steps_to_window_end())
+            if ext is not None:
+                k = min(k, ext.steps_to_window_end())
             self._run_lanes(k, energy_diag)
             n -= k
             if flw is not None and flw.window_closed():
@@ -906,6 +920,8 @@ class Simulation:
                 self.flush_spharm()
             if edd is not None and edd.window_closed():
                 self.flush_eddy()
+            if ext is not None and ext.window_closed():
+                self.flush_extremes()
             if hist is not None and hist.window_closed():
                 self.flush_history()
             if ser is not None and ser.window_closed():
@@ -950,6 +966,11 @@ class Simulation:
         dropped (the next one starts from zero): output never stops the run."""
         return self._nonfatal(lambda: self.eddy.flush(complete=complete), "[Eddy] window skipped: {}", cleanup=self.eddy.drop)
 
+    def flush_extremes(self, complete=1):
+        """Write the extremes window that stands in the device's planes -> the path or None.  A failure is reported and the window
+        is dropped (the next one starts from its start values): output never stops the run."""
+        return self._nonfatal(lambda: self.extremes.flush(complete=complete), "[Extremes] window skipped: {}", cleanup=self.extremes.drop)
+
     def _run_lanes(self, n, energy_diag=False):
         """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
         individuals')."""
@@ -963,7 +984,8 @@ class Simulation:
                                    ("eco_daily", eco_daily), ("history", self.history), ("series", self.series),
                                    ("spectra", getattr(self, "spectra", None)),
                                    ("drifters", getattr(self, "drifters", None)), ("flow", getattr(self, "flow", None)),
-                                   ("spharm", getattr(self, "spharm", None)), ("eddy", getattr(self, "eddy", None))) if p is not None}
+                                   ("spharm", getattr(self, "spharm", None)), ("eddy", getattr(self, "eddy", None)),
+                                   ("extremes", getattr(self, "extremes", None))) if p is not None}
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
         # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
@@ -1054,6 +1076,15 @@ class Simulation:
         self.spharm = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
                                dt=float(self.dt), day=self.day_seconds)
         return self.spharm
+
+    def enable_extremes(self, env=None):
+        """QD_EXTREMES=1: per-cell extremes with their times, threshold frequencies and spells, and per-row histograms of the
+        selected entries, kept by a device lane and written per window to <QD_OUTPUT_DIR>/extremes/ (qingdai_amd/extremes.py) -> the
+        Extremes or None.  The run-local step index the windows count on starts where this is called."""
+        from .extremes import from_env
+        self.extremes = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
+                                 dt=float(self.dt), day=self.day_seconds)
+        return self.extremes
 
     def enable_eddy(self, env=None):
         """QD_EDDY=1: covariances and transports of the selected pairs of fields, accumulated by a device lane and written per
@@ -1347,6 +1378,8 @@ def main(argv=None):
         sim.enable_spharm(env)
     if getattr(sim, "enable_eddy", None) is not None:          # (likewise)
         sim.enable_eddy(env)
+    if getattr(sim, "enable_extremes", None) is not None:      # (likewise)
+        sim.enable_extremes(env)
     if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
         try:
             sim.load_checkpoint(ck_file, env)
@@ -1442,6 +1475,8 @@ def main(argv=None):
         sim.flush_spharm(complete=0)                           # and the open spherical-harmonic window
     if getattr(sim, "eddy", None) is not None and not (ck["enabled"] and autosave_on):
         sim.flush_eddy(complete=0)                             # and the open eddy window
+    if getattr(sim, "extremes", None) is not None and not (ck["enabled"] and autosave_on):
+        sim.flush_extremes(complete=0)                         # and the open extremes window
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")
