@@ -48,6 +48,9 @@ import numpy as np
 
 from . import _lib, ncio
 from ._lib import FIELDS
+from .window_lane import env_int as _int, i8_code as _i8
+
+KEYED_LANES = ("series", "spectra", "flow", "spharm", "eddy", "extremes", "drifters")     # the order check_subsystems tests them in
 
 ABI_VERSION = 1                      # QD_ABI_VERSION as of this module (tests/test_state_digest_cpu.py holds it to the header); a handle's
                                      # own library is asked where there is one (abi_version)
@@ -89,13 +92,6 @@ def span_consistent(sim):
 
 
 # ------------------------------------------------------------------------------------- environment
-def _int(env, name, default):
-    try:
-        return int(env.get(name, str(default)))
-    except (TypeError, ValueError):
-        return default
-
-
 def read_env(env=None, data_dir=None):
     """QD_CHECKPOINT (default 0), QD_CHECKPOINT_PATH (default <QD_DATA_DIR>/checkpoint.nc), QD_CHECKPOINT_STRICT (default 1)."""
     env = os.environ if env is None else env
@@ -158,36 +154,22 @@ def _eco_f32(sim):
 
 
 def subsystems(sim):
-    """The subsystem set a file must share with the run that loads it, as one string per item.  The series lane's key is there only
-    when the lane is on: a file without it says "off", as every file written before the lane existed does."""
+    """The subsystem set a file must share with the run that loads it, as one string per item.  A keyed lane's item (its key()) is
+    there only when the lane is on: a file without it says "off", as every file written before the lane existed does.  The history
+    item is older than the keys: it is always there, "-" when the lane is off."""
     pop = sim.eco.pop if sim.eco is not None else None
-    ser = getattr(sim, "series", None)
-    extra = {"series": f"{','.join(ser.names)}|zonal={int(ser.zonal)}|every={int(ser.every)}"} if ser is not None else {}
-    spc = getattr(sim, "spectra", None)
-    if spc is not None:                 # likewise the spectra lane's
-        extra["spectra"] = f"{','.join(spc.names)}|every={int(spc.every)}|lat={int(spc.lat_resolved)}"
-    dri = getattr(sim, "drifters", None)
-    if dri is not None:                 # and the drifters'
-        extra["drifters"] = dri.key()
-    flw = getattr(sim, "flow", None)
-    if flw is not None:                 # and the flow lane's
-        extra["flow"] = f"every={int(flw.every)}"
-    sph = getattr(sim, "spharm", None)
-    if sph is not None:                 # and the spherical-harmonic lane's
-        extra["spharm"] = sph.key()
-    edd = getattr(sim, "eddy", None)
-    if edd is not None:                 # and the eddy lane's
-        extra["eddy"] = edd.key()
-    ext = getattr(sim, "extremes", None)
-    if ext is not None:                 # and the extremes lane's
-        extra["extremes"] = ext.key()
-    return {**{"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
-            "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
-            "phyto_daily": str(int(sim.phyto_daily is not None)),
-            "ecology": str(int(sim.eco is not None)), "population": str(int(pop is not None)), "eco_f32": str(int(_eco_f32(sim))),
-            "eco_daily": str(int(sim.eco_daily is not None)), "individuals": str(int(sim.indiv is not None)),
-            "indiv_daily": str(int(sim.indiv_daily is not None)),
-            "history": ",".join(sim.history.names) if sim.history is not None else "-"}, **extra}
+    items = {"ocean": str(int(sim.ocean is not None)), "routing": str(int(sim.routing is not None)),
+             "phyto": str(int(sim.phyto is not None)), "phyto_transport": str(int(bool(getattr(sim, "phyto_transport", False)))),
+             "phyto_daily": str(int(sim.phyto_daily is not None)),
+             "ecology": str(int(sim.eco is not None)), "population": str(int(pop is not None)), "eco_f32": str(int(_eco_f32(sim))),
+             "eco_daily": str(int(sim.eco_daily is not None)), "individuals": str(int(sim.indiv is not None)),
+             "indiv_daily": str(int(sim.indiv_daily is not None)),
+             "history": ",".join(sim.history.names) if sim.history is not None else "-"}
+    for name in ("series", "spectra", "drifters", "flow", "spharm", "eddy", "extremes"):      # (the order the files have held them in)
+        lane = getattr(sim, name, None)
+        if lane is not None:
+            items[name] = lane.key()
+    return items
 
 
 def plane_names(sim):
@@ -229,11 +211,6 @@ def simulation_digest(sim):
 
 def _attr_key(name):
     return "digest_" + name.replace(":", "_")
-
-
-def _i8():
-    """Classic NetCDF (the scipy back end) has no 64-bit integer: the counts, all far below 2^53, are then written as f8."""
-    return "i8" if ncio.backend() == "netCDF4" else "f8"
 
 
 def _code_hash():
@@ -304,52 +281,25 @@ def collect(sim):
         v["hist_sums"] = ("f8", ("hist", "lat", "lon"), sums)
         v["hist_clock"] = ("f8", ("five",), np.array([float(h.i), _nan(h.t_first), _nan(h.t_last), float(h.n_open), float(count)]))
     ser = getattr(sim, "series", None)
-    if ser is not None:
-        recs, times, steps = ser.window()                      # (a span boundary: every record of the log has been delivered)
-        n = int(len(recs))
-        pad = max(n, 1)                                        # classic NetCDF reads a dimension of size 0 as the unlimited one
-        dims["series_time"], dims["series_width"] = pad, int(ser.width)
-        v["series_records"] = ("f8", ("series_time", "series_width"), np.concatenate([recs, np.zeros((pad - n, ser.width))]))
-        v["series_times"] = ("f8", ("series_time",), np.concatenate([times, np.zeros(pad - n)]))
-        v["series_steps"] = ("f8", ("series_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
-        v["series_clock"] = ("f8", ("two",), np.array([float(ser.i), float(n)]))
+    if ser is not None:                                        # (a span boundary: every record of the log has been delivered)
+        _save_log_window(dims, v, ser, "series")
     spc = getattr(sim, "spectra", None)
     if spc is not None:
-        recs, times, steps = spc.window()
-        n = int(len(recs))
-        pad = max(n, 1)
-        dims["spectra_time"], dims["spectra_width"] = pad, int(spc.width)
-        v["spectra_records"] = ("f8", ("spectra_time", "spectra_width"), np.concatenate([recs, np.zeros((pad - n, spc.width))]))
-        v["spectra_times"] = ("f8", ("spectra_time",), np.concatenate([times, np.zeros(pad - n)]))
-        v["spectra_steps"] = ("f8", ("spectra_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
         sums, count = spc.sums()
-        v["spectra_clock"] = ("f8", ("three",), np.array([float(spc.i), float(n), float(count)]))
+        _save_log_window(dims, v, spc, "spectra", count)
         if sums is not None:
             dims["spectra_entry"], dims["spectra_k"] = int(sums.shape[0]), int(sums.shape[2])
             v["spectra_sums"] = ("f8", ("spectra_entry", "lat", "spectra_k"), sums)
     flw = getattr(sim, "flow", None)
     if flw is not None:
-        recs, times, steps = flw.window()
-        n = int(len(recs))
-        pad = max(n, 1)
         sums, count = flw.sums()
-        dims["flow_time"], dims["flow_width"], dims["flow_plane"] = pad, int(flw.width), int(sums.shape[0])
-        v["flow_records"] = ("f8", ("flow_time", "flow_width"), np.concatenate([recs, np.zeros((pad - n, flw.width))]))
-        v["flow_times"] = ("f8", ("flow_time",), np.concatenate([times, np.zeros(pad - n)]))
-        v["flow_steps"] = ("f8", ("flow_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
-        v["flow_clock"] = ("f8", ("three",), np.array([float(flw.i), float(n), float(count)]))
+        _save_log_window(dims, v, flw, "flow", count)
+        dims["flow_plane"] = int(sums.shape[0])
         v["flow_sums"] = ("f8", ("flow_plane", "lat", "lon"), sums)
     sph = getattr(sim, "spharm", None)
     if sph is not None:
-        recs, times, steps = sph.window()
-        n = int(len(recs))
-        pad = max(n, 1)
-        dims["spharm_time"], dims["spharm_width"] = pad, int(sph.width)
-        v["spharm_records"] = ("f8", ("spharm_time", "spharm_width"), np.concatenate([recs, np.zeros((pad - n, sph.width))]))
-        v["spharm_times"] = ("f8", ("spharm_time",), np.concatenate([times, np.zeros(pad - n)]))
-        v["spharm_steps"] = ("f8", ("spharm_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
         sums, count = sph.sums()
-        v["spharm_clock"] = ("f8", ("three",), np.array([float(sph.i), float(n), float(count)]))
+        _save_log_window(dims, v, sph, "spharm", count)
         if sums is not None:
             dims["spharm_entry"], dims["spharm_degree"] = int(sums.shape[0]), int(sums.shape[1])
             v["spharm_sums"] = ("f8", ("spharm_entry", "spharm_degree", "spharm_degree"), sums)
@@ -375,14 +325,7 @@ def collect(sim):
         v["extremes_clock"] = ("f8", ("five",), np.array([float(ext.i), _nan(ext.t_first), _nan(ext.t_last), float(ext.n_open), float(st["n"])]))
     dri = getattr(sim, "drifters", None)
     if dri is not None:                                        # the particles as they stand, and the open window's records so far
-        recs, times, steps = dri.window()
-        n = int(len(recs))
-        pad = max(n, 1)
-        dims["drift_time"], dims["drift_width"] = pad, max(1, int(dri.width))
-        v["drift_records"] = ("f8", ("drift_time", "drift_width"), np.concatenate([recs, np.zeros((pad - n, dri.width))]).reshape(pad, -1))
-        v["drift_times"] = ("f8", ("drift_time",), np.concatenate([times, np.zeros(pad - n)]))
-        v["drift_steps"] = ("f8", ("drift_time",), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
-        v["drift_clock"] = ("f8", ("two",), np.array([float(dri.i), float(n)]))
+        _save_log_window(dims, v, dri, "drift")
         for pop, state in dri.state().items():
             if state.shape[1]:
                 dims[f"drift_{pop}_rows"], dims[f"drift_{pop}_n"] = int(state.shape[0]), int(state.shape[1])
@@ -400,6 +343,29 @@ def collect(sim):
     for name, d in digests.items():
         attrs["run_digest" if name == "run" else _attr_key(name)] = f"0x{d:016x}"
     return dims, v, attrs
+
+
+def _save_log_window(dims, v, lane, prefix, count=None):
+    """A LogWindowLane's open window as <prefix>_records / _times / _steps, padded to one row where it is empty (classic NetCDF
+    reads a dimension of size 0 as the unlimited one), and <prefix>_clock {i, records[, count: the sample count of the lane's sums]}."""
+    recs, times, steps = lane.window()
+    n = int(len(recs))
+    pad = max(n, 1)
+    t, w = prefix + "_time", prefix + "_width"
+    dims[t], dims[w] = pad, max(1, int(lane.width))
+    v[prefix + "_records"] = ("f8", (t, w), np.concatenate([recs, np.zeros((pad - n, lane.width))]).reshape(pad, -1))
+    v[prefix + "_times"] = ("f8", (t,), np.concatenate([times, np.zeros(pad - n)]))
+    v[prefix + "_steps"] = ("f8", (t,), np.concatenate([np.asarray(steps, dtype=np.float64), np.zeros(pad - n)]))
+    clock = [float(lane.i), float(n)] + ([] if count is None else [float(count)])
+    v[prefix + "_clock"] = ("f8", ("two" if count is None else "three",), np.array(clock))
+
+
+def _restore_log_window(v, lane, prefix, **sums):
+    """The inverse of _save_log_window, through the lane's restore_window (which takes `sums`, where the lane has some)."""
+    clock = np.asarray(v[prefix + "_clock"], dtype=np.float64)
+    n = int(clock[1])
+    lane.restore_window(np.asarray(v[prefix + "_records"], dtype=np.float64)[:n], np.asarray(v[prefix + "_times"])[:n],
+                        np.asarray(v[prefix + "_steps"])[:n], int(clock[0]), **sums)
 
 
 def write_atomic(path, dims, variables, attrs):
@@ -517,27 +483,10 @@ def check_grid_and_abi(f, shape, dev=None):
 def check_subsystems(f, sim):
     want, got = subsystems(sim), f.subsystems()
     onoff = lambda s: {"0": "off", "1": "on"}.get(s, f"'{s}'")
-    if got.get("series", "-") != want.get("series", "-"):
-        raise CheckpointRefused(f"the subsystem set differs: the series lane is '{got.get('series', '-')}' in the file and "
-                                f"'{want.get('series', '-')}' in this run")
-    if got.get("spectra", "-") != want.get("spectra", "-"):
-        raise CheckpointRefused(f"the subsystem set differs: the spectra lane is '{got.get('spectra', '-')}' in the file and "
-                                f"'{want.get('spectra', '-')}' in this run")
-    if got.get("flow", "-") != want.get("flow", "-"):
-        raise CheckpointRefused(f"the subsystem set differs: the flow lane is '{got.get('flow', '-')}' in the file and "
-                                f"'{want.get('flow', '-')}' in this run")
-    if got.get("spharm", "-") != want.get("spharm", "-"):
-        raise CheckpointRefused(f"the subsystem set differs: the spharm lane is '{got.get('spharm', '-')}' in the file and "
-                                f"'{want.get('spharm', '-')}' in this run")
-    if got.get("eddy", "-") != want.get("eddy", "-"):
-        raise CheckpointRefused(f"the subsystem set differs: the eddy lane is '{got.get('eddy', '-')}' in the file and "
-                                f"'{want.get('eddy', '-')}' in this run")
-    if got.get("extremes", "-") != want.get("extremes", "-"):
-        raise CheckpointRefused(f"the subsystem set differs: the extremes lane is '{got.get('extremes', '-')}' in the file and "
-                                f"'{want.get('extremes', '-')}' in this run")
-    if got.get("drifters", "-") != want.get("drifters", "-"):
-        raise CheckpointRefused(f"the subsystem set differs: the drifters lane is '{got.get('drifters', '-')}' in the file and "
-                                f"'{want.get('drifters', '-')}' in this run")
+    for name in KEYED_LANES:
+        if got.get(name, "-") != want.get(name, "-"):
+            raise CheckpointRefused(f"the subsystem set differs: the {name} lane is '{got.get(name, '-')}' in the file and "
+                                    f"'{want.get(name, '-')}' in this run")
     for k in want:
         if got.get(k) != want[k]:
             if k == "history":
@@ -668,29 +617,16 @@ def load(sim, path, env=None, out=print):
         dev.history_restore(np.asarray(v["hist_sums"], dtype=np.float64), int(clock[4]))
         h.i, h.t_first, h.t_last, h.n_open = int(clock[0]), _none(clock[1]), _none(clock[2]), int(clock[3])
     if getattr(sim, "series", None) is not None:
-        clock = np.asarray(v["series_clock"], dtype=np.float64)
-        n = int(clock[1])
-        sim.series.restore_window(np.asarray(v["series_records"], dtype=np.float64)[:n], np.asarray(v["series_times"])[:n],
-                                  np.asarray(v["series_steps"])[:n], int(clock[0]))
+        _restore_log_window(v, sim.series, "series")
         dev.series_reset()
     if getattr(sim, "spectra", None) is not None:
-        clock = np.asarray(v["spectra_clock"], dtype=np.float64)
-        n = int(clock[1])
-        sim.spectra.restore_window(np.asarray(v["spectra_records"], dtype=np.float64)[:n], np.asarray(v["spectra_times"])[:n],
-                                   np.asarray(v["spectra_steps"])[:n], int(clock[0]),
-                                   sums=np.asarray(v["spectra_sums"], dtype=np.float64) if "spectra_sums" in v else None, count=int(clock[2]))
+        _restore_log_window(v, sim.spectra, "spectra", sums=np.asarray(v["spectra_sums"], dtype=np.float64) if "spectra_sums" in v else None,
+                            count=int(v["spectra_clock"][2]))
     if getattr(sim, "flow", None) is not None:
-        clock = np.asarray(v["flow_clock"], dtype=np.float64)
-        n = int(clock[1])
-        sim.flow.restore_window(np.asarray(v["flow_records"], dtype=np.float64)[:n], np.asarray(v["flow_times"])[:n],
-                                np.asarray(v["flow_steps"])[:n], int(clock[0]),
-                                sums=np.asarray(v["flow_sums"], dtype=np.float64), count=int(clock[2]))
+        _restore_log_window(v, sim.flow, "flow", sums=np.asarray(v["flow_sums"], dtype=np.float64), count=int(v["flow_clock"][2]))
     if getattr(sim, "spharm", None) is not None:
-        clock = np.asarray(v["spharm_clock"], dtype=np.float64)
-        n = int(clock[1])
-        sim.spharm.restore_window(np.asarray(v["spharm_records"], dtype=np.float64)[:n], np.asarray(v["spharm_times"])[:n],
-                                  np.asarray(v["spharm_steps"])[:n], int(clock[0]),
-                                  sums=np.asarray(v["spharm_sums"], dtype=np.float64) if "spharm_sums" in v else None, count=int(clock[2]))
+        _restore_log_window(v, sim.spharm, "spharm", sums=np.asarray(v["spharm_sums"], dtype=np.float64) if "spharm_sums" in v else None,
+                            count=int(v["spharm_clock"][2]))
     if getattr(sim, "eddy", None) is not None:
         e, clock = sim.eddy, np.asarray(v["eddy_clock"], dtype=np.float64)
         dev.eddy_restore(np.asarray(v["eddy_anchors"], dtype=np.float64), np.asarray(v["eddy_sums"], dtype=np.float64),
@@ -710,10 +646,7 @@ def load(sim, path, env=None, out=print):
         x.i, x.t_first, x.t_last, x.n_open = int(clock[0]), _none(clock[1]), _none(clock[2]), int(clock[3])
     dri = getattr(sim, "drifters", None)
     if dri is not None:
-        clock = np.asarray(v["drift_clock"], dtype=np.float64)
-        n = int(clock[1])
-        dri.restore_window(np.asarray(v["drift_records"], dtype=np.float64)[:n], np.asarray(v["drift_times"])[:n],
-                           np.asarray(v["drift_steps"])[:n], int(clock[0]))
+        _restore_log_window(v, dri, "drift")
         dri.restore_state(np.asarray(v["drift_atm"], dtype=np.float64) if "drift_atm" in v else np.empty((3, 0)),
                           np.asarray(v["drift_ocn"], dtype=np.float64) if "drift_ocn" in v else np.empty((4, 0)))
         dev.drift_reset()

@@ -18,12 +18,12 @@ of the step outside the .hip.  Nothing here touches the device at import.
 from __future__ import annotations
 
 import math
-import os
 
 import numpy as np
 
-from . import history, ncio
+from . import history
 from ._lib import DRIFT_MAX, DRIFT_MAX_SAMPLES
+from .window_lane import LogWindowLane, env_days, env_every, env_int, i8_code, window_file_name
 
 SAMPLE_VARS = ("QD_DRIFT_SAMPLE_ATM", "QD_DRIFT_SAMPLE_OCN")
 N_ATM, N_OCN, EVERY, EVERY_DAYS = 4096, 4096, 24, 10.0
@@ -173,13 +173,6 @@ def seed_fibonacci(n, grid, land_mask=None):
 
 
 # ------------------------------------------------------------------------------------- environment
-def _int(env, name, default):
-    try:
-        return int(env.get(name, str(default)))
-    except (TypeError, ValueError):
-        return default
-
-
 def parse_samples(text, var):
     """A sample list through history's parser: f64 planes only (no derived speed), at most 4, never PRECIP."""
     names = history.parse_fields(text, var=var)
@@ -200,19 +193,10 @@ def read_env(env):
     (QD_DRIFT_EVERY_DAYS, default 10; unparsable or <= 0 -> 10), sample_atm / sample_ocn (QD_DRIFT_SAMPLE_ATM, default TS,H;
     QD_DRIFT_SAMPLE_OCN, default SST; an empty value samples nothing), log_cap (QD_DRIFT_LOG_CAP: fewer records per chunk than the
     device log holds, for tests; None = the device's)."""
-    enabled = _int(env, "QD_DRIFTERS", 0) == 1
-    every = _int(env, "QD_DRIFT_EVERY", EVERY)
-    if every < 1:
-        every = EVERY
-    try:
-        days = float(env.get("QD_DRIFT_EVERY_DAYS", str(EVERY_DAYS)))
-    except (TypeError, ValueError):
-        days = EVERY_DAYS
-    if not (days > 0.0) or not math.isfinite(days):
-        days = EVERY_DAYS
+    enabled = env_int(env, "QD_DRIFTERS", 0) == 1
     counts = []
     for name, default in (("QD_DRIFT_N_ATM", N_ATM), ("QD_DRIFT_N_OCN", N_OCN)):
-        k = _int(env, name, default)
+        k = env_int(env, name, default)
         if enabled and not 0 <= k <= DRIFT_MAX:
             raise ValueError(f"{name}: {k} particles, a population holds 0 to {DRIFT_MAX}")
         counts.append(k)
@@ -220,8 +204,9 @@ def read_env(env):
     for var, default in zip(SAMPLE_VARS, DEFAULT_SAMPLES):
         text = env.get(var)
         samples.append(list(default) if text is None else (parse_samples(text, var) if enabled else []))
-    cap = _int(env, "QD_DRIFT_LOG_CAP", 0)
-    return {"enabled": enabled, "n_atm": counts[0], "n_ocn": counts[1], "every": every, "every_days": days,
+    cap = env_int(env, "QD_DRIFT_LOG_CAP", 0)
+    return {"enabled": enabled, "n_atm": counts[0], "n_ocn": counts[1], "every": env_every(env, "QD_DRIFT_EVERY", EVERY),
+            "every_days": env_days(env, "QD_DRIFT_EVERY_DAYS", EVERY_DAYS),
             "sample_atm": samples[0], "sample_ocn": samples[1], "log_cap": cap if cap >= 1 else None}
 
 
@@ -256,12 +241,7 @@ def split_records(recs, n_atm, ns_atm, n_ocn, ns_ocn):
 
 
 def file_name(a_days, b_days, decimals=1):
-    w = decimals + 3
-    return f"drifters_day_{a_days:0{w}.{decimals}f}_{b_days:0{w}.{decimals}f}.nc"
-
-
-def _i8():
-    return "i8" if ncio.backend() == "netCDF4" else "f8"
+    return window_file_name("drifters", a_days, b_days, decimals)
 
 
 def window_variables(parts, samples, times, steps, shape, dt, every, complete):
@@ -270,7 +250,7 @@ def window_variables(parts, samples, times, steps, shape, dt, every, complete):
     n = int(len(times))
     dims = {"time": n}
     v = {"time_seconds": ("f8", ("time",), np.asarray(times, dtype=np.float64).reshape(n)),
-         "step": (_i8(), ("time",), np.asarray(steps, dtype=np.int64).reshape(n))}
+         "step": (i8_code(), ("time",), np.asarray(steps, dtype=np.int64).reshape(n))}
     for pop in POPS:
         b = parts[pop]
         if b.shape[2] == 0:
@@ -291,19 +271,18 @@ def window_variables(parts, samples, times, steps, shape, dt, every, complete):
     return dims, v
 
 
-class Drifters:
-    """The lane's participant in Device.step_n: the run-local step index is its clock, span_schedule uploads the span's record
-    flags (every step of the span advances), span_deliver drains the span's records into the open window, flush() writes the
-    window's file.  `sim` gives dev, grid, ocean (None = off), dt, day_seconds and land_mask.  Seeds: atm=(lat, lon) and / or
-    ocn=(lat, lon) in degrees, the caller's own; with neither, cfg's counts of Fibonacci lattice points (ocn: those over ocean)."""
+class Drifters(LogWindowLane):
+    """The lane's participant in Device.step_n: the clock and the span protocol are window_lane's (the flags name the steps that
+    record; every step of the span advances), flush() writes the window's file.  drop() forgets the delivered records only: _pending
+    and the device log stay as they are.  `sim` gives dev, grid, ocean (None = off), dt, day_seconds and land_mask.  Seeds:
+    atm=(lat, lon) and / or ocn=(lat, lon) in degrees, the caller's own; with neither, cfg's counts of Fibonacci lattice points (ocn:
+    those over ocean)."""
+    NAME, TAG = "drifters", "Drifters"
 
     def __init__(self, sim, atm=None, ocn=None, cfg=None, out=print, output_dir=None):
         cfg = default_config() if cfg is None else dict(cfg)
         dev, grid = sim.dev, sim.grid
-        self.dev, self.grid, self.cfg, self.out = dev, grid, cfg, out
         self.with_ocean = getattr(sim, "ocean", None) is not None
-        self.dt = float(sim.dt)
-        self.day = float(sim.day_seconds)
         self.shape = (int(grid.n_lat), int(grid.n_lon))
         land = np.asarray(sim.land_mask)
         if atm is None and ocn is None:
@@ -322,15 +301,8 @@ class Drifters:
             for name in self.samples[p]:
                 if name in history.OCEAN_ONLY and not self.with_ocean:
                     raise ValueError(f"{var}: field '{name}' needs the ocean, which is off in this run (QD_USE_OCEAN)")
-        self.S = history.steps_per_window(cfg["every_days"], self.day, self.dt)
-        self.every = int(cfg["every"])
-        self.decimals = history.label_decimals(self.S * self.dt / self.day)
-        self.output_dir = output_dir
-        self.width = record_width(self.n["atm"], len(self.samples["atm"]), self.n["ocn"], len(self.samples["ocn"]))
-        self.i = 0                                   # run-local index of the next step
-        self._pending = []                           # (times, steps) of spans that ran and whose records are still in the device log
-        self.drop()
-        self.files = []
+        width = record_width(self.n["atm"], len(self.samples["atm"]), self.n["ocn"], len(self.samples["ocn"]))
+        super().__init__(dev, grid, cfg, out, sim.dt, sim.day_seconds, cfg["every_days"], cfg["every"], width, output_dir)
         self.device_cap = dev.drift_configure(seeds["atm"], seeds["ocn"], self.samples["atm"], self.samples["ocn"],
                                               sec_table(grid.lat))
         self.cap = self.device_cap if cfg.get("log_cap") is None else max(1, min(self.device_cap, int(cfg["log_cap"])))
@@ -339,48 +311,12 @@ class Drifters:
         """The lane's place in a checkpoint's subsystem set."""
         return "|".join(f"{p}={self.n[p]}:{','.join(self.samples[p])}" for p in POPS) + f"|every={self.every}"
 
-    # -- the span protocol of Device.step_n
-    def span_clock(self):
-        return (self.i, len(self._pending))
+    def _upload(self, flags):
+        self.dev.drift_schedule(flags)
 
-    def span_restore(self, clock):
-        self.i = clock[0]
-        del self._pending[clock[1]:]
+    def _drain(self, want):
+        return self.dev.drift_log(want)
 
-    def span_schedule(self, t0, dt, n):
-        flags = history.schedule(self.i, n, self.S, self.every)
-        self.dev.drift_schedule(flags)               # (more records than the log holds between two drains: qd_step_n refuses the span)
-        if t0 is None:
-            times = (self.i + np.arange(int(n))) * float(dt)
-        elif np.ndim(t0) == 0:
-            times = float(t0) + float(dt) * np.arange(int(n))
-        else:
-            times = np.asarray(t0, dtype=np.float64)
-        hit = np.flatnonzero(flags)
-        return (int(n), np.asarray(times, dtype=np.float64)[hit].copy(), (self.i + hit).astype(np.int64))
-
-    def _fired(self, k):
-        n, times, steps = k
-        self.i += n
-        if len(times):
-            self._pending.append((times, steps))
-
-    def span_deliver(self, dt):
-        """Drain the device log into the open window -> the records [n][width] that came."""
-        want = sum(len(t) for t, _ in self._pending)
-        if want == 0:
-            return np.empty((0, self.width))
-        recs = self.dev.drift_log(want)
-        if len(recs) != want:
-            raise RuntimeError(f"Drifters: the device log held {len(recs)} records where the schedule says {want}")
-        self.recs.append(recs)
-        for t, s in self._pending:
-            self.times.append(t)
-            self.steps.append(s)
-        self._pending = []
-        return recs
-
-    # -- windows
     def steps_to_window_end(self, i=None):
         """Steps from step i (default: the next step) up to and including the earlier of its window's last step and the step whose
         record fills the device log (self.cap records since the last drain, and every span is drained)."""
@@ -389,24 +325,6 @@ class Drifters:
         first = -(-pos // self.every) * self.every                 # the next recording position of the window
         room = first + (self.cap - 1) * self.every - pos + 1       # steps up to and including the cap-th record from here
         return min(self.S - pos, room)
-
-    def window_closed(self):
-        return self.i > 0 and self.i % self.S == 0
-
-    def window(self):
-        """The open window as delivered so far -> (recs [n][width], times [n], steps [n])."""
-        if not self.recs:
-            return np.empty((0, self.width)), np.empty(0), np.empty(0, dtype=np.int64)
-        return np.concatenate(self.recs), np.concatenate(self.times), np.concatenate(self.steps)
-
-    def restore_window(self, recs, times, steps, i):
-        """The inverse of window() and the clock, for an exact resume (checkpoint.py)."""
-        self.drop()
-        recs = np.asarray(recs, dtype=np.float64).reshape(-1, self.width)
-        if len(recs):
-            self.recs, self.times = [recs.copy()], [np.asarray(times, dtype=np.float64).reshape(-1).copy()]
-            self.steps = [np.asarray(steps).reshape(-1).astype(np.int64)]
-        self.i = int(i)
 
     def split(self, recs):
         return split_records(recs, self.n["atm"], len(self.samples["atm"]), self.n["ocn"], len(self.samples["ocn"]))
@@ -419,38 +337,18 @@ class Drifters:
     def restore_state(self, atm, ocn):
         self.dev.drift_state_set(atm, ocn)
 
-    def path(self, a_days, b_days):
-        out = self.output_dir if self.output_dir is not None else os.environ.get("QD_OUTPUT_DIR", "output")
-        return os.path.join(out, "drifters", file_name(a_days, b_days, self.decimals))
-
-    def flush(self, complete=1):
-        """Write the open window's file, print one line, start the next window -> the path, or None when it holds no record."""
+    def _window_file(self, complete):
         recs, times, steps = self.window()
         if len(recs) == 0:
             return None
         a, b = float(times[0]) / self.day, float(times[-1]) / self.day
-        path = self.path(a, b)
         parts = self.split(recs)
         dims, variables = window_variables(parts, self.samples, times, steps, self.shape, self.dt, self.every, complete)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        tmp = path + ".part"
-        try:
-            ncio.write_nc(tmp, dims, variables)
-            os.replace(tmp, path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
         d = self.decimals
         dead = {p: int(parts[p][-1, 2, :].sum()) for p in POPS}
-        self.out(f"[Drifters] day {a:.{d}f}–{b:.{d}f}: {len(recs)} records | atm {self.n['atm'] - dead['atm']}/{dead['atm']} | "
-                 f"ocn {self.n['ocn'] - dead['ocn']}/{dead['ocn']}/{int(parts['ocn'][-1, 3, :].sum()) if self.n['ocn'] else 0}")
-        self.drop()
-        self.files.append(path)
-        return path
-
-    def drop(self):
-        """Forget the open window's delivered records; the next record starts the next file."""
-        self.recs, self.times, self.steps = [], [], []
+        line = (f"[Drifters] day {a:.{d}f}–{b:.{d}f}: {len(recs)} records | atm {self.n['atm'] - dead['atm']}/{dead['atm']} | "
+                f"ocn {self.n['ocn'] - dead['ocn']}/{dead['ocn']}/{int(parts['ocn'][-1, 3, :].sum()) if self.n['ocn'] else 0}")
+        return a, b, dims, variables, line
 
 
 def from_env(sim, env, out=print):

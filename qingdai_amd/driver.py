@@ -205,6 +205,7 @@ Per iteration (run_simulation.py:1760-2340), all on the device through one qd_st
 from __future__ import annotations
 
 import atexit
+import importlib
 import os
 import signal
 import sys
@@ -217,6 +218,12 @@ from . import topography as topo
 from .truecolor import plot_interval_steps, firing_steps      # the plot clock of the state frame, the true-colour frame and the figures
 
 PLANET_OMEGA = 8.726646259971648e-5
+# The windowed diagnostics (qingdai_amd/window_lane.py) by their NAME, which is also the Simulation attribute, the module and the
+# keyword of Device.step_n.  The order of the printed lines is behaviour: WINDOW_LANES is the order in which main enables them, a
+# span delivers to them and the end of a run writes their open windows; MID_RUN_FLUSH_ORDER the order in which windows that close
+# on the same step are written inside a run.
+WINDOW_LANES = ("history", "series", "spectra", "drifters", "flow", "spharm", "eddy", "extremes")
+MID_RUN_FLUSH_ORDER = ("flow", "spharm", "eddy", "extremes", "history", "series", "spectra", "drifters")
 
 RESTART_VARS = {  # restart name -> device field (run_simulation.py:63-124)
     "u": "U", "v": "V", "h": "H", "T_s": "TS", "cloud_cover": "CLOUD", "q": "Q", "h_ice": "HICE",
@@ -890,86 +897,51 @@ class Simulation:
             self._run_cut(n, energy_diag)
 
     def _run_cut(self, n, energy_diag=False):
-        """n steps through _run_lanes; under QD_HISTORY=1 cut so that a chunk ends with a window's last step, behind which the
-        window's file is written (the sums then start the next window from zero); under QD_SERIES=1 likewise with its windows."""
-        hist, ser, spc = self.history, self.series, getattr(self, "spectra", None)
-        dri, flw = getattr(self, "drifters", None), getattr(self, "flow", None)
-        sph, edd = getattr(self, "spharm", None), getattr(self, "eddy", None)
-        ext = getattr(self, "extremes", None)
+        """n steps through _run_lanes, cut so that a chunk ends with the last step of a window of every windowed lane that is on,
+        behind which the window's file is written (and the next window starts from zero)."""
+        on = self._window_lanes()
         while n > 0:
-            k = n if hist is None else min(n, hist.steps_to_window_end())
-            if ser is not None:
-                k = min(k, ser.steps_to_window_end())
-            if spc is not None:
-                k = min(k, spc.steps_to_window_end())
-            if dri is not None:
-                k = min(k, dri.steps_to_window_end())              # (its window's end, or the step that fills its device log)
-            if flw is not None:
-                k = min(k, flw.steps_to_window_end())
-            if sph is not None:
-                k = min(k, sph.steps_to_window_end())
-            if edd is not None:
-                k = min(k, edd.steps_to_window_end())
-            if ext is not None:
-                k = min(k, ext.steps_to_window_end())
+            k = min([n] + [lane.steps_to_window_end() for lane in on.values()])      # (the drifters': or the step that fills their log)
             self._run_lanes(k, energy_diag)
             n -= k
-            if flw is not None and flw.window_closed():
-                self.flush_flow()
-            if sph is not None and sph.window_closed():
-                self.flush_spharm()
-            if edd is not None and edd.window_closed():
-                self.flush_eddy()
-            if ext is not None and ext.window_closed():
-                self.flush_extremes()
-            if hist is not None and hist.window_closed():
-                self.flush_history()
-            if ser is not None and ser.window_closed():
-                self.flush_series()
-            if spc is not None and spc.window_closed():
-                self.flush_spectra()
-            if dri is not None and dri.window_closed():
-                self.flush_drifters()
+            for name in MID_RUN_FLUSH_ORDER:
+                if name in on and on[name].window_closed():
+                    getattr(self, "flush_" + name)()
+
+    def _window_lanes(self):
+        """{name: lane} of the windowed lanes that are on, in WINDOW_LANES' order."""
+        lanes = {name: getattr(self, name, None) for name in WINDOW_LANES}
+        return {name: lane for name, lane in lanes.items() if lane is not None}
+
+    def flush_window(self, name, complete=1):
+        """Write the open window of the lane `name` -> the path or None.  A failure is reported and the window is dropped (the next
+        one starts from zero): output never stops the run."""
+        lane = getattr(self, name)
+        return self._nonfatal(lambda: lane.flush(complete=complete), f"[{lane.TAG}] window skipped: {{}}", cleanup=lane.drop)
 
     def flush_history(self, complete=1):
-        """Write the history window that stands in the accumulators -> the path or None.  A failure is reported and the window is
-        dropped (the next one starts from zero): output never stops the run."""
-        return self._nonfatal(lambda: self.history.flush(complete=complete), "[History] window skipped: {}", cleanup=self.history.drop)
+        return self.flush_window("history", complete)
 
     def flush_series(self, complete=1):
-        """Write the series window that stands on the host -> the path or None.  A failure is reported and the window is dropped:
-        output never stops the run."""
-        return self._nonfatal(lambda: self.series.flush(complete=complete), "[Series] window skipped: {}", cleanup=self.series.drop)
+        return self.flush_window("series", complete)
 
     def flush_spectra(self, complete=1):
-        """Write the spectra window that stands on the host (and in the device's sum planes) -> the path or None.  A failure is
-        reported and the window is dropped: output never stops the run."""
-        return self._nonfatal(lambda: self.spectra.flush(complete=complete), "[Spectra] window skipped: {}", cleanup=self.spectra.drop)
+        return self.flush_window("spectra", complete)
 
     def flush_drifters(self, complete=1):
-        """Write the drifter window that stands on the host -> the path or None.  A failure is reported and the window is dropped:
-        output never stops the run."""
-        return self._nonfatal(lambda: self.drifters.flush(complete=complete), "[Drifters] window skipped: {}", cleanup=self.drifters.drop)
+        return self.flush_window("drifters", complete)
 
     def flush_flow(self, complete=1):
-        """Write the flow window that stands on the host (and in the device's sum planes) -> the path or None.  A failure is
-        reported and the window is dropped: output never stops the run."""
-        return self._nonfatal(lambda: self.flow.flush(complete=complete), "[Flow] window skipped: {}", cleanup=self.flow.drop)
+        return self.flush_window("flow", complete)
 
     def flush_spharm(self, complete=1):
-        """Write the spherical-harmonic window that stands on the host (and in the device's sum planes) -> the path or None.  A
-        failure is reported and the window is dropped: output never stops the run."""
-        return self._nonfatal(lambda: self.spharm.flush(complete=complete), "[SphSpec] window skipped: {}", cleanup=self.spharm.drop)
+        return self.flush_window("spharm", complete)
 
     def flush_eddy(self, complete=1):
-        """Write the eddy window that stands in the device's planes -> the path or None.  A failure is reported and the window is
-        dropped (the next one starts from zero): output never stops the run."""
-        return self._nonfatal(lambda: self.eddy.flush(complete=complete), "[Eddy] window skipped: {}", cleanup=self.eddy.drop)
+        return self.flush_window("eddy", complete)
 
     def flush_extremes(self, complete=1):
-        """Write the extremes window that stands in the device's planes -> the path or None.  A failure is reported and the window
-        is dropped (the next one starts from its start values): output never stops the run."""
-        return self._nonfatal(lambda: self.extremes.flush(complete=complete), "[Extremes] window skipped: {}", cleanup=self.extremes.drop)
+        return self.flush_window("extremes", complete)
 
     def _run_lanes(self, n, energy_diag=False):
         """One span: the lanes that are on, qd_step_n, the clock, each lane's lines (phyto, routing, budget, eco daily with the
@@ -981,11 +953,8 @@ class Simulation:
         if self.budget is not None:
             self.budget.routed = self.routing is not None
         lanes = {k: p for k, p in (("phyto_daily", self.phyto_daily), ("routing", self.routing), ("budget", self.budget),
-                                   ("eco_daily", eco_daily), ("history", self.history), ("series", self.series),
-                                   ("spectra", getattr(self, "spectra", None)),
-                                   ("drifters", getattr(self, "drifters", None)), ("flow", getattr(self, "flow", None)),
-                                   ("spharm", getattr(self, "spharm", None)), ("eddy", getattr(self, "eddy", None)),
-                                   ("extremes", getattr(self, "extremes", None))) if p is not None}
+                                   ("eco_daily", eco_daily)) if p is not None}
+        lanes.update(self._window_lanes())
         eco_clock = eco_daily.span_clock() if eco_daily is not None else None
         # from here to the end of the bookkeeping the device and the host clocks disagree: what interrupts in between (a signal
         # handler runs right behind the device call) must not take the state for a span boundary (checkpoint.span_consistent)
@@ -1033,75 +1002,51 @@ class Simulation:
                                routed=self.routing is not None)
         return self.budget
 
+    def _enable_window(self, name, env=None):
+        """QD_<NAME>=1: the windowed lane `name` (qingdai_amd/<name>.py), kept by a device lane and written per window to
+        <QD_OUTPUT_DIR>/<name>/ -> the lane or None.  The run-local step index the windows count on starts where this is called.
+        An unknown field name raises here, before the loop."""
+        env = os.environ if env is None else env
+        from_env = importlib.import_module("." + name, __package__).from_env
+        if name == "drifters":
+            lane = from_env(self, env)
+        else:
+            kw = {} if name == "flow" else {"with_ocean": self.ocean is not None}
+            lane = from_env(self.dev, self.grid, env, dt=float(self.dt), day=self.day_seconds, **kw)
+        setattr(self, name, lane)
+        return lane
+
     def enable_history(self, env=None):
-        """QD_HISTORY=1: time means of the selected fields over windows of QD_HISTORY_EVERY_DAYS planet-days, accumulated by a device
-        lane and written to <QD_OUTPUT_DIR>/history/ (qingdai_amd/history.py) -> the History or None.  The run-local step index the
-        windows count on starts where this is called.  An unknown field name raises here, before the loop."""
-        from .history import from_env
-        self.history = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
-                                dt=float(self.dt), day=self.day_seconds)
-        return self.history
+        """QD_HISTORY=1: time means of the selected fields."""
+        return self._enable_window("history", env)
 
     def enable_series(self, env=None):
-        """QD_SERIES=1: per-step global means, extrema, NaN counts and zonal means of the selected fields, reduced by a device lane
-        and written per window to <QD_OUTPUT_DIR>/series/ (qingdai_amd/series.py) -> the Series or None.  The run-local step index
-        the windows count on starts where this is called.  An unknown field name raises here, before the loop."""
-        from .series import from_env
-        self.series = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
-                               dt=float(self.dt), day=self.day_seconds)
-        return self.series
+        """QD_SERIES=1: per-step global means, extrema, NaN counts and zonal means."""
+        return self._enable_window("series", env)
 
     def enable_spectra(self, env=None):
-        """QD_SPECTRA=1: zonal wavenumber spectra of the selected fields, transformed by a device lane and written per window to
-        <QD_OUTPUT_DIR>/spectra/ (qingdai_amd/spectra.py) -> the Spectra or None.  The run-local step index the windows count on
-        starts where this is called.  An unknown field name raises here, before the loop."""
-        from .spectra import from_env
-        self.spectra = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
-                                dt=float(self.dt), day=self.day_seconds)
-        return self.spectra
+        """QD_SPECTRA=1: zonal wavenumber spectra."""
+        return self._enable_window("spectra", env)
 
     def enable_flow(self, env=None):
-        """QD_FLOW=1: vorticity, divergence, streamfunction and velocity potential of the winds, solved by a device lane and written
-        per window to <QD_OUTPUT_DIR>/flow/ (qingdai_amd/flow.py) -> the Flow or None.  The run-local step index the windows count
-        on starts where this is called."""
-        from .flow import from_env
-        self.flow = from_env(self.dev, self.grid, os.environ if env is None else env, dt=float(self.dt), day=self.day_seconds)
-        return self.flow
+        """QD_FLOW=1: vorticity, divergence, streamfunction and velocity potential of the winds."""
+        return self._enable_window("flow", env)
 
     def enable_spharm(self, env=None):
-        """QD_SPHARM=1: spherical-harmonic power spectra of the selected fields, analysed by a device lane and written per window to
-        <QD_OUTPUT_DIR>/spharm/ (qingdai_amd/spharm.py) -> the Spharm or None.  The run-local step index the windows count on
-        starts where this is called."""
-        from .spharm import from_env
-        self.spharm = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
-                               dt=float(self.dt), day=self.day_seconds)
-        return self.spharm
+        """QD_SPHARM=1: spherical-harmonic power spectra."""
+        return self._enable_window("spharm", env)
 
     def enable_extremes(self, env=None):
-        """QD_EXTREMES=1: per-cell extremes with their times, threshold frequencies and spells, and per-row histograms of the
-        selected entries, kept by a device lane and written per window to <QD_OUTPUT_DIR>/extremes/ (qingdai_amd/extremes.py) -> the
-        Extremes or None.  The run-local step index the windows count on starts where this is called."""
-        from .extremes import from_env
-        self.extremes = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
-                                 dt=float(self.dt), day=self.day_seconds)
-        return self.extremes
+        """QD_EXTREMES=1: per-cell extremes, threshold frequencies and spells, per-row histograms."""
+        return self._enable_window("extremes", env)
 
     def enable_eddy(self, env=None):
-        """QD_EDDY=1: covariances and transports of the selected pairs of fields, accumulated by a device lane and written per
-        window to <QD_OUTPUT_DIR>/eddy/ (qingdai_amd/eddy.py) -> the Eddy or None.  The run-local step index the windows count on
-        starts where this is called."""
-        from .eddy import from_env
-        self.eddy = from_env(self.dev, self.grid, os.environ if env is None else env, with_ocean=self.ocean is not None,
-                             dt=float(self.dt), day=self.day_seconds)
-        return self.eddy
+        """QD_EDDY=1: covariances and transports of the selected pairs of fields."""
+        return self._enable_window("eddy", env)
 
     def enable_drifters(self, env=None):
-        """QD_DRIFTERS=1: Lagrangian drifters on the winds and the currents, advanced by a device lane on every step and written per
-        window to <QD_OUTPUT_DIR>/drifters/ (qingdai_amd/drifters.py) -> the Drifters or None.  The run-local step index the
-        windows count on starts where this is called.  An unknown sampled field raises here, before the loop."""
-        from .drifters import from_env
-        self.drifters = from_env(self, os.environ if env is None else env)
-        return self.drifters
+        """QD_DRIFTERS=1: Lagrangian drifters on the winds and the currents."""
+        return self._enable_window("drifters", env)
 
     def enable_routing(self, env=None):
         """run_simulation.py:1294-1321 with the reference's QD_HYDRO_* defaults and messages -> the RiverRouting or None."""
@@ -1365,21 +1310,10 @@ def main(argv=None):
         _legacy_load()
     sim.enable_routing(env)
     sim.enable_budget_diag(env)
-    sim.enable_history(env)
-    if getattr(sim, "enable_series", None) is not None:        # (a stand-in Simulation from before the series lane has none)
-        sim.enable_series(env)
-    if getattr(sim, "enable_spectra", None) is not None:       # (likewise)
-        sim.enable_spectra(env)
-    if getattr(sim, "enable_drifters", None) is not None:      # (likewise)
-        sim.enable_drifters(env)
-    if getattr(sim, "enable_flow", None) is not None:          # (likewise)
-        sim.enable_flow(env)
-    if getattr(sim, "enable_spharm", None) is not None:        # (likewise)
-        sim.enable_spharm(env)
-    if getattr(sim, "enable_eddy", None) is not None:          # (likewise)
-        sim.enable_eddy(env)
-    if getattr(sim, "enable_extremes", None) is not None:      # (likewise)
-        sim.enable_extremes(env)
+    for name in WINDOW_LANES:
+        enable = getattr(sim, "enable_" + name, None)          # (a stand-in Simulation from before a lane has none)
+        if enable is not None:
+            enable(env)
     if ck_file is not None:                                    # behind the lanes: their buffers and clocks come from the file
         try:
             sim.load_checkpoint(ck_file, env)
@@ -1459,24 +1393,12 @@ def main(argv=None):
                 next_autosave_t += autosave_dt
         return next_autosave_t
     sim.run_loop(n_total, next_autosave_t if autosave_on else None, _after_chunk)
-    if sim.history is not None and not (ck["enabled"] and autosave_on):
-        # the open window, marked incomplete (the signal path does not get here); under QD_CHECKPOINT=1 the final checkpoint carries
-        # it instead, and the run that resumes writes it when it is complete
-        sim.flush_history(complete=0)
-    if getattr(sim, "series", None) is not None and not (ck["enabled"] and autosave_on):
-        sim.flush_series(complete=0)                           # likewise the open series window
-    if getattr(sim, "spectra", None) is not None and not (ck["enabled"] and autosave_on):
-        sim.flush_spectra(complete=0)                          # and the open spectra window
-    if getattr(sim, "drifters", None) is not None and not (ck["enabled"] and autosave_on):
-        sim.flush_drifters(complete=0)                         # and the open drifter window
-    if getattr(sim, "flow", None) is not None and not (ck["enabled"] and autosave_on):
-        sim.flush_flow(complete=0)                             # and the open flow window
-    if getattr(sim, "spharm", None) is not None and not (ck["enabled"] and autosave_on):
-        sim.flush_spharm(complete=0)                           # and the open spherical-harmonic window
-    if getattr(sim, "eddy", None) is not None and not (ck["enabled"] and autosave_on):
-        sim.flush_eddy(complete=0)                             # and the open eddy window
-    if getattr(sim, "extremes", None) is not None and not (ck["enabled"] and autosave_on):
-        sim.flush_extremes(complete=0)                         # and the open extremes window
+    if not (ck["enabled"] and autosave_on):
+        # the open windows, marked incomplete (the signal path does not get here); under QD_CHECKPOINT=1 the final checkpoint carries
+        # them instead, and the run that resumes writes each when it is complete
+        for name in WINDOW_LANES:
+            if getattr(sim, name, None) is not None:
+                getattr(sim, "flush_" + name)(complete=0)
     if env.get("QD_RESTART_OUT"):
         sim.save(env["QD_RESTART_OUT"])
         print(f"[Restart] wrote {env['QD_RESTART_OUT']}")

@@ -34,14 +34,11 @@ Nothing here touches the device at import; the parser, the clock, the arithmetic
 """
 from __future__ import annotations
 
-import math
-import os
-
 import numpy as np
 
-from . import history, ncio
+from . import history, order
 from ._lib import C as _C, FIELDS
-from .series import _lanes, _wave
+from .window_lane import SumWindowLane, env_days, env_dt, env_every, env_int, window_file_name
 
 PAIRS_VAR = "QD_EDDY_PAIRS"
 DEFAULT_PAIRS = "U*V,V*TS,V*Q,V*H,U*U,V*V,H*H,TS*TS"
@@ -90,37 +87,21 @@ def parse_pairs(text, var=PAIRS_VAR):
     return fields, pairs, labels
 
 
-def _int(env, name, default):
-    try:
-        return int(env.get(name, str(default)))
-    except (TypeError, ValueError):
-        return default
-
-
 def read_env(env):
     """-> dict: enabled (QD_EDDY, default 0), pairs (QD_EDDY_PAIRS as text, upper-cased; the default list when unset or empty;
     parsed -- and refused -- only when the lane is on), sample_every (QD_EDDY_SAMPLE_EVERY, default 4; unparsable or < 1 -> 4),
     every_days (QD_EDDY_EVERY_DAYS, default 10; unparsable or <= 0 -> 10), maps (QD_EDDY_MAPS, default 1)."""
-    enabled = _int(env, "QD_EDDY", 0) == 1
-    k = _int(env, "QD_EDDY_SAMPLE_EVERY", SAMPLE_EVERY)
-    if k < 1:
-        k = SAMPLE_EVERY
-    try:
-        days = float(env.get("QD_EDDY_EVERY_DAYS", str(EVERY_DAYS)))
-    except (TypeError, ValueError):
-        days = EVERY_DAYS
-    if not (days > 0.0) or not math.isfinite(days):
-        days = EVERY_DAYS
+    enabled = env_int(env, "QD_EDDY", 0) == 1
     text = env.get(PAIRS_VAR)
     text = DEFAULT_PAIRS if text is None or not str(text).strip() else ",".join(s.strip().upper() for s in str(text).split(",") if s.strip())
     if enabled:
         parse_pairs(text)
-    return {"enabled": enabled, "pairs": text, "sample_every": k, "every_days": days, "maps": _int(env, "QD_EDDY_MAPS", MAPS) != 0}
+    return {"enabled": enabled, "pairs": text, "sample_every": env_every(env, "QD_EDDY_SAMPLE_EVERY", SAMPLE_EVERY),
+            "every_days": env_days(env, "QD_EDDY_EVERY_DAYS", EVERY_DAYS), "maps": env_int(env, "QD_EDDY_MAPS", MAPS) != 0}
 
 
 def file_name(a_days, b_days, decimals=1):
-    w = decimals + 3
-    return f"eddy_day_{a_days:0{w}.{decimals}f}_{b_days:0{w}.{decimals}f}.nc"
+    return window_file_name("eddy", a_days, b_days, decimals)
 
 
 # ------------------------------------------------------------------------------------- the definition, in NumPy
@@ -154,13 +135,13 @@ def _row_sums(x):
     128 m + 2 l and 128 m + 2 l + 1 and adds them in ascending order into one accumulator that starts at +0.0; then the five
     halvings.  (A cell past the row's end is no add on the device and an add of +0.0 here, which changes no bit.)"""
     x = np.ascontiguousarray(x, dtype=np.float64)
-    cells = _lanes(x, 128, 0.0)
+    cells = order.lanes(x, 128, 0.0)
     cells = cells.reshape(x.shape[:-1] + (cells.shape[-2], 64, 2))
     acc = np.zeros(x.shape[:-1] + (64,))
     for m in range(cells.shape[-3]):
         acc = acc + cells[..., m, :, 0]
         acc = acc + cells[..., m, :, 1]
-    return _wave(acc, np.add)
+    return order.wave(acc, np.add)
 
 
 def zonal_reference(S, Cs, pairs):
@@ -207,85 +188,33 @@ def covariance_maps(sums, pair_sums, pairs, count):
 
 
 # ------------------------------------------------------------------------------------- the lane
-class Eddy:
-    """The lane's participant in Device.step_n, with history's clock: the run-local step index names the sampled steps,
-    span_schedule uploads the span's sample flags, flush() turns the resident sums into one file."""
+class Eddy(SumWindowLane):
+    """The lane's participant in Device.step_n: the clock and the span protocol are window_lane's, flush() turns the resident sums
+    into one file.  drop() zeroes the device's planes and count and forgets the labels."""
+    NAME, TAG = "eddy", "Eddy"
 
     def __init__(self, dev, grid, cfg, with_ocean=True, dt=300.0, day=None, out=print, output_dir=None):
-        self.dev, self.grid, self.cfg, self.out = dev, grid, dict(cfg), out
-        self.dt = float(dt)
-        self.day = float(2.0 * np.pi / dev.params.omega) if day is None else float(day)
+        super().__init__(dev, grid, cfg, out, dt, day, cfg["every_days"], cfg["sample_every"], output_dir)
         self.text = str(cfg.get("pairs") or DEFAULT_PAIRS)
         self.fields, self.pairs, self.labels = parse_pairs(self.text)
         history.resolve_fields(self.fields, with_ocean, var=PAIRS_VAR)     # a field of a subsystem that is off is refused
         self.maps = bool(cfg.get("maps", True))
-        self.S = history.steps_per_window(cfg["every_days"], self.day, self.dt)
-        self.sample_every = int(cfg["sample_every"])
-        self.decimals = history.label_decimals(self.S * self.dt / self.day)
-        self.output_dir = output_dir
-        self.i = 0                                   # run-local index of the next step
-        self.t_first = self.t_last = None            # start times (s) of the open window's first and last sampled step
-        self.n_open = 0                              # samples the host has scheduled into the open window
-        self.files = []
         dev.eddy_configure(self.fields, self.pairs)
 
     def key(self):
         """The lane's part of a checkpoint's subsystem set."""
         return f"{self.text}|every={self.sample_every}|maps={int(self.maps)}"
 
-    # -- the span protocol of Device.step_n
-    def span_clock(self):
-        return (self.i, self.t_first, self.t_last, self.n_open)
-
-    def span_restore(self, clock):
-        self.i, self.t_first, self.t_last, self.n_open = clock
-
-    def span_schedule(self, t0, dt, n):
-        flags = history.schedule(self.i, n, self.S, self.sample_every)
+    def _upload(self, flags):
         self.dev.eddy_schedule(flags)
-        if t0 is None:
-            times = (self.i + np.arange(int(n))) * float(dt)
-        elif np.ndim(t0) == 0:
-            times = float(t0) + float(dt) * np.arange(int(n))
-        else:
-            times = np.asarray(t0, dtype=np.float64)
-        hit = np.flatnonzero(flags)
-        return (int(n), (float(times[hit[0]]), float(times[hit[-1]])) if hit.size else None, int(hit.size))
 
-    def _fired(self, k):
-        n, span, count = k
-        self.i += n
-        if span is not None:
-            if self.t_first is None:
-                self.t_first = span[0]
-            self.t_last = span[1]
-            self.n_open += count
-
-    def span_deliver(self, dt):
-        pass                                         # the samples went into the resident sums: nothing to drain behind a span
-
-    # -- windows
-    def steps_to_window_end(self, i=None):
-        """Steps from step i (default: the next step) up to and including its window's last step."""
-        i = self.i if i is None else int(i)
-        return self.S - (i % self.S)
-
-    def window_closed(self):
-        """The last step that ran was a window's last step."""
-        return self.i > 0 and self.i % self.S == 0
-
-    def path(self, a_days, b_days):
-        out = self.output_dir if self.output_dir is not None else os.environ.get("QD_OUTPUT_DIR", "output")
-        return os.path.join(out, "eddy", file_name(a_days, b_days, self.decimals))
-
-    def flush(self, complete=1):
-        """Reduce the rows on the device, read the planes, decompose, write the file, print one line, reset -> the path, or None
-        when the window holds no sample."""
+    def _window_file(self, complete):
+        """Reduce the rows on the device, read the planes, decompose -> the window's file, or None when it holds no sample."""
         anchors, sums, pair_sums, count = self.dev.eddy_read()
         if count <= 0:
             return None
         zonal = self.dev.eddy_zonal()
-        t0s, t1s = (0.0 if self.t_first is None else float(self.t_first)), (0.0 if self.t_last is None else float(self.t_last))
+        t0s, t1s = self.window_labels()
         a, b = t0s / self.day, t1s / self.day
         abar = time_means(anchors, sums, count)
         parts = decompose(zonal, count, abar, self.pairs)
@@ -302,15 +231,6 @@ class Eddy:
         variables.update(n_samples=("i4", (), int(count)), t_start_seconds=("f8", (), t0s), t_end_seconds=("f8", (), t1s),
                          dt_seconds=("f8", (), self.dt), sample_every=("i4", (), self.sample_every), maps=("i4", (), int(self.maps)),
                          complete=("i4", (), 1 if complete else 0))
-        path = self.path(a, b)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        tmp = path + ".part"
-        try:
-            ncio.write_nc(tmp, {"lat": int(self.grid.n_lat), "lon": int(self.grid.n_lon)}, variables)
-            os.replace(tmp, path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
         tr = parts["transient"][0]
         if np.isnan(tr).all():
             where, value = float("nan"), float("nan")
@@ -318,17 +238,13 @@ class Eddy:
             j = int(np.nanargmax(np.abs(tr)))
             where, value = float(lat[j]), float(tr[j])
         d = self.decimals
-        self.out(f"[Eddy] day {a:.{d}f}–{b:.{d}f}: {count} samples | {self.labels[0][0]}*{self.labels[0][1]} transient "
-                 f"max |.| at lat {where:.2f}: {value:.6g}")
-        self.drop()
-        self.files.append(path)
-        return path
+        line = (f"[Eddy] day {a:.{d}f}–{b:.{d}f}: {count} samples | {self.labels[0][0]}*{self.labels[0][1]} transient "
+                f"max |.| at lat {where:.2f}: {value:.6g}")
+        return a, b, {"lat": int(self.grid.n_lat), "lon": int(self.grid.n_lon)}, variables, line
 
     def drop(self):
-        """Forget the open window: sums and count to zero, the labels start with the next sample."""
         self.dev.eddy_reset()
-        self.t_first = self.t_last = None
-        self.n_open = 0
+        super().drop()
 
 
 def from_env(dev, grid, env, with_ocean=True, dt=None, day=None, out=print):
@@ -336,6 +252,4 @@ def from_env(dev, grid, env, with_ocean=True, dt=None, day=None, out=print):
     cfg = read_env(env)
     if not cfg["enabled"]:
         return None
-    if dt is None:
-        dt = float(env.get("QD_DT_SECONDS", "300"))
-    return Eddy(dev, grid, cfg, with_ocean=with_ocean, dt=dt, day=day, out=out)
+    return Eddy(dev, grid, cfg, with_ocean=with_ocean, dt=env_dt(env, dt), day=day, out=out)

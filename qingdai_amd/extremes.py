@@ -24,13 +24,13 @@ Nothing here touches the device at import; the parsers, the clock, the arithmeti
 from __future__ import annotations
 
 import math
-import os
 import zlib
 
 import numpy as np
 
-from . import history, ncio
+from . import history
 from ._lib import C as _C
+from .window_lane import SumWindowLane, env_days, env_dt, env_every, env_int, i8_code, window_file_name
 
 FIELDS_VAR, THRESHOLDS_VAR, BINS_VAR = "QD_EXTREMES_FIELDS", "QD_EXTREMES_THRESHOLDS", "QD_EXTREMES_BINS"
 DEFAULT_FIELDS = ("TS", "PRECIP", "WIND_SPEED", "H")
@@ -151,34 +151,19 @@ def threshold_label(name, cmp, value):
     return f"{name}_{'lt' if cmp == '<' else 'gt'}_{text}"
 
 
-def _int(env, name, default):
-    try:
-        return int(env.get(name, str(default)))
-    except (TypeError, ValueError):
-        return default
-
-
 def read_env(env):
     """-> dict: enabled (QD_EXTREMES, default 0), fields (QD_EXTREMES_FIELDS parsed, or None = the default list), thresholds and bins
     (the texts of QD_EXTREMES_THRESHOLDS and QD_EXTREMES_BINS, or None = the defaults that name a field of the run), sample_every
     (QD_EXTREMES_SAMPLE_EVERY, default 4; unparsable or < 1 -> 4), every_days (QD_EXTREMES_EVERY_DAYS, default 10; unparsable or
     <= 0 -> 10).  The lists are parsed -- and refused -- only when the lane is on."""
-    enabled = _int(env, "QD_EXTREMES", 0) == 1
-    k = _int(env, "QD_EXTREMES_SAMPLE_EVERY", SAMPLE_EVERY)
-    if k < 1:
-        k = SAMPLE_EVERY
-    try:
-        days = float(env.get("QD_EXTREMES_EVERY_DAYS", str(EVERY_DAYS)))
-    except (TypeError, ValueError):
-        days = EVERY_DAYS
-    if not (days > 0.0) or not math.isfinite(days):
-        days = EVERY_DAYS
+    enabled = env_int(env, "QD_EXTREMES", 0) == 1
 
     def text(var):
         t = env.get(var)
         return None if t is None or not str(t).strip() else str(t)
     fields = text(FIELDS_VAR)
-    cfg = {"enabled": enabled, "fields": None, "thresholds": text(THRESHOLDS_VAR), "bins": text(BINS_VAR), "sample_every": k, "every_days": days}
+    cfg = {"enabled": enabled, "fields": None, "thresholds": text(THRESHOLDS_VAR), "bins": text(BINS_VAR),
+           "sample_every": env_every(env, "QD_EXTREMES_SAMPLE_EVERY", SAMPLE_EVERY), "every_days": env_days(env, "QD_EXTREMES_EVERY_DAYS", EVERY_DAYS)}
     if enabled:
         cfg["fields"] = parse_fields(fields) if fields is not None else None
         names = cfg["fields"] if cfg["fields"] is not None else list(DEFAULT_FIELDS + DEFAULT_OCEAN_FIELDS)
@@ -198,8 +183,7 @@ def resolve_fields(fields, with_ocean, var=FIELDS_VAR):
 
 
 def file_name(a_days, b_days, decimals=1):
-    w = decimals + 3
-    return f"extremes_day_{a_days:0{w}.{decimals}f}_{b_days:0{w}.{decimals}f}.nc"
+    return window_file_name("extremes", a_days, b_days, decimals)
 
 
 # ------------------------------------------------------------------------------------- the definition, in NumPy
@@ -318,11 +302,6 @@ def threshold_summary(thr, n, step_seconds):
             "freq": count / np.float64(n), "longest_seconds": longest * float(step_seconds), "mean_spell_seconds": mean}
 
 
-def _i8():
-    """Classic NetCDF (the scipy back end) has no 64-bit integer: the counts, all far below 2^53, are then written as f8."""
-    return "i8" if ncio.backend() == "netCDF4" else "f8"
-
-
 def window_variables(state, names, thresholds, hists, lat, lon, t_first, step_seconds):
     """The state of a window -> (dims, variables) of its file, without the scalars.  thresholds: [(name, cmp, value)]; hists:
     [(name, edges)]; t_first: the start time (s) of sample 0; step_seconds: sample_every * dt."""
@@ -348,7 +327,7 @@ def window_variables(state, names, thresholds, hists, lat, lon, t_first, step_se
         dims[f"{n}_edge"], dims[f"{n}_bin"], dims[f"{n}_col"] = nb + 1, nb, nb + 3
         s = hist_summary(state["hist"][h], edges, lat)
         v[f"{n}_edges"] = ("f8", (f"{n}_edge",), np.asarray(edges, dtype=np.float64))
-        v[f"{n}_hist"] = (_i8(), ("lat", f"{n}_col"), np.asarray(state["hist"][h], dtype=np.int64))
+        v[f"{n}_hist"] = (i8_code(), ("lat", f"{n}_col"), np.asarray(state["hist"][h], dtype=np.int64))
         v[f"{n}_pdf"] = ("f8", (f"{n}_bin",), s["pdf"])
         for key in ("under_frac", "over_frac", "nan_frac"):
             v[f"{n}_{key}"] = ("f8", (), float(s[key]))
@@ -357,14 +336,16 @@ def window_variables(state, names, thresholds, hists, lat, lon, t_first, step_se
 
 
 # ------------------------------------------------------------------------------------- the lane
-class Extremes:
-    """The lane's participant in Device.step_n, with history's clock: the run-local step index names the sampled steps,
-    span_schedule uploads the span's sample flags, flush() turns the resident state into one file.
+class Extremes(SumWindowLane):
+    """The lane's participant in Device.step_n: the clock and the span protocol are window_lane's, flush() turns the resident state
+    into one file.  drop() puts the device's state back to its start values, the count to zero, and forgets the labels.
 
     Extremes(sim, fields=..., thresholds=..., bins={name: edges}) configures it on a driver.Simulation with the caller's own lists:
     fields a list of names or a comma-separated text, thresholds a text like QD_EXTREMES_THRESHOLDS or [(name, cmp, value)], bins a
     text like QD_EXTREMES_BINS or {name: edges} with the edges as they are to be used.  Extremes(dev, grid, cfg, ...) is what
     from_env builds.  What is None comes from cfg, and then from the defaults that name a field of the run."""
+
+    NAME, TAG = "extremes", "Extremes"
 
     def __init__(self, dev, grid=None, cfg=None, with_ocean=None, dt=None, day=None, out=print, output_dir=None,
                  fields=None, thresholds=None, bins=None):
@@ -375,9 +356,8 @@ class Extremes:
             dt = float(sim.dt) if dt is None else dt
             day = getattr(sim, "day_seconds", None) if day is None else day
         cfg = dict(cfg or {})
-        self.dev, self.grid, self.cfg, self.out = dev, grid, cfg, out
-        self.dt = float(300.0 if dt is None else dt)
-        self.day = float(2.0 * np.pi / dev.params.omega) if day is None else float(day)
+        super().__init__(dev, grid, cfg, out, 300.0 if dt is None else dt, day, cfg.get("every_days", EVERY_DAYS),
+                         cfg.get("sample_every", SAMPLE_EVERY), output_dir)
         with_ocean = True if with_ocean is None else bool(with_ocean)
         fields = cfg.get("fields") if fields is None else fields
         if isinstance(fields, str):
@@ -404,14 +384,6 @@ class Extremes:
                 self.hists.append((n, check_edges(e, f"{BINS_VAR}: '{n}'")))
             if len(self.hists) > MAX_HISTS:
                 raise ValueError(f"{BINS_VAR}: {len(self.hists)} histograms, at most {MAX_HISTS}")
-        self.S = history.steps_per_window(cfg.get("every_days", EVERY_DAYS), self.day, self.dt)
-        self.sample_every = int(cfg.get("sample_every", SAMPLE_EVERY))
-        self.decimals = history.label_decimals(self.S * self.dt / self.day)
-        self.output_dir = output_dir
-        self.i = 0                                   # run-local index of the next step
-        self.t_first = self.t_last = None            # start times (s) of the open window's first and last sampled step
-        self.n_open = 0                              # samples the host has scheduled into the open window
-        self.files = []
         dev.extremes_configure(history.entries_for(self.names), [(self.names.index(n), c, x) for n, c, x in self.thresholds],
                                [(self.names.index(n), e) for n, e in self.hists])
 
@@ -421,58 +393,15 @@ class Extremes:
         bins = ",".join(f"{n}:{e.size - 1}:{float(e[0])!r}:{float(e[-1])!r}:{zlib.crc32(e.tobytes()):08x}" for n, e in self.hists)
         return f"{','.join(self.names)}|{thr}|{bins}|every={self.sample_every}"
 
-    # -- the span protocol of Device.step_n
-    def span_clock(self):
-        return (self.i, self.t_first, self.t_last, self.n_open)
-
-    def span_restore(self, clock):
-        self.i, self.t_first, self.t_last, self.n_open = clock
-
-    def span_schedule(self, t0, dt, n):
-        flags = history.schedule(self.i, n, self.S, self.sample_every)
+    def _upload(self, flags):
         self.dev.extremes_schedule(flags)
-        if t0 is None:
-            times = (self.i + np.arange(int(n))) * float(dt)
-        elif np.ndim(t0) == 0:
-            times = float(t0) + float(dt) * np.arange(int(n))
-        else:
-            times = np.asarray(t0, dtype=np.float64)
-        hit = np.flatnonzero(flags)
-        return (int(n), (float(times[hit[0]]), float(times[hit[-1]])) if hit.size else None, int(hit.size))
 
-    def _fired(self, k):
-        n, span, count = k
-        self.i += n
-        if span is not None:
-            if self.t_first is None:
-                self.t_first = span[0]
-            self.t_last = span[1]
-            self.n_open += count
-
-    def span_deliver(self, dt):
-        pass                                         # the samples went into the resident state: nothing to drain behind a span
-
-    # -- windows
-    def steps_to_window_end(self, i=None):
-        """Steps from step i (default: the next step) up to and including its window's last step."""
-        i = self.i if i is None else int(i)
-        return self.S - (i % self.S)
-
-    def window_closed(self):
-        """The last step that ran was a window's last step."""
-        return self.i > 0 and self.i % self.S == 0
-
-    def path(self, a_days, b_days):
-        out = self.output_dir if self.output_dir is not None else os.environ.get("QD_OUTPUT_DIR", "output")
-        return os.path.join(out, "extremes", file_name(a_days, b_days, self.decimals))
-
-    def flush(self, complete=1):
-        """Read the state, write the file, print one line, reset -> the path, or None when the window holds no sample."""
+    def _window_file(self, complete):
         state = self.dev.extremes_read()
         count = state["n"]
         if count <= 0:
             return None
-        t0s, t1s = (0.0 if self.t_first is None else float(self.t_first)), (0.0 if self.t_last is None else float(self.t_last))
+        t0s, t1s = self.window_labels()
         a, b = t0s / self.day, t1s / self.day
         lat = np.asarray(self.grid.lat, dtype=np.float64)
         lon = np.asarray(self.grid.lon, dtype=np.float64)
@@ -480,15 +409,6 @@ class Extremes:
         variables.update(n_samples=("i4", (), int(count)), t_start_seconds=("f8", (), t0s), t_end_seconds=("f8", (), t1s),
                          dt_seconds=("f8", (), self.dt), sample_every=("i4", (), self.sample_every),
                          complete=("i4", (), 1 if complete else 0))
-        path = self.path(a, b)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        tmp = path + ".part"
-        try:
-            ncio.write_nc(tmp, dims, variables)
-            os.replace(tmp, path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
         d = self.decimals
         top = np.where(state["tmax"][0] >= 0, state["vmax"][0], -np.inf)
         j, i = np.unravel_index(int(np.argmax(top)), top.shape)
@@ -501,16 +421,11 @@ class Extremes:
             label = threshold_label(*self.thresholds[0])
             freq = variables[label.lower() + "_freq"][2]
             line += f"{' |' if not self.hists else ''} {label} freq={history.global_mean(freq, self.grid.lat_mesh):.6g}"
-        self.out(line)
-        self.drop()
-        self.files.append(path)
-        return path
+        return a, b, dims, variables, line
 
     def drop(self):
-        """Forget the open window: the state to its start values, the count to zero, the labels start with the next sample."""
         self.dev.extremes_reset()
-        self.t_first = self.t_last = None
-        self.n_open = 0
+        super().drop()
 
 
 def from_env(dev, grid, env, with_ocean=True, dt=None, day=None, out=print):
@@ -519,6 +434,4 @@ def from_env(dev, grid, env, with_ocean=True, dt=None, day=None, out=print):
     cfg = read_env(env)
     if not cfg["enabled"]:
         return None
-    if dt is None:
-        dt = float(env.get("QD_DT_SECONDS", "300"))
-    return Extremes(dev, grid, cfg, with_ocean=with_ocean, dt=dt, day=day, out=out)
+    return Extremes(dev, grid, cfg, with_ocean=with_ocean, dt=env_dt(env, dt), day=day, out=out)

@@ -39,14 +39,13 @@ touches the device at import.
 """
 from __future__ import annotations
 
-import math
-import os
 import types
 
 import numpy as np
 
-from . import history, ncio, series
+from . import order
 from ._lib import C
+from .window_lane import LogWindowLane, env_days, env_dt, env_every, env_int, i8_code, window_file_name
 
 EVERY_DAYS, EVERY = 10.0, 24
 REC = ("vort_global", "div_global", "vort_rms", "div_rms", "vort_maxabs", "div_maxabs", "psi_min", "psi_max", "chi_min", "chi_max",
@@ -85,22 +84,22 @@ def grid_tables(grid, radius):
 def _row_sums(x):
     """[..., n] -> [...]: the row stage of series.reduce_reference (lane l owns the cells 128 k + 2 l and 128 k + 2 l + 1)."""
     x = np.asarray(x, dtype=np.float64)
-    cells = series._lanes(x, 128, 0.0).reshape(x.shape[:-1] + (-1, 64, 2))
+    cells = order.lanes(x, 128, 0.0).reshape(x.shape[:-1] + (-1, 64, 2))
     acc = np.zeros(x.shape[:-1] + (64,))
     for k in range(cells.shape[-3]):
         acc = acc + cells[..., k, :, 0]
         acc = acc + cells[..., k, :, 1]
-    return series._wave(acc, np.add)
+    return order.wave(acc, np.add)
 
 
 def _cross_mean(S, w, n):
     """The second stage of series.reduce_reference with the weights w: lane l takes the rows l, l + 64, ..."""
-    rows_w, rows_p = series._lanes(w, 64, 0.0), series._lanes(w * S, 64, 0.0)
+    rows_w, rows_p = order.lanes(w, 64, 0.0), order.lanes(w * S, 64, 0.0)
     num, W = np.zeros(64), np.zeros(64)
     for k in range(rows_w.shape[0]):
         num = num + rows_p[k]
         W = W + rows_w[k]
-    return series._wave(num, np.add) / (np.float64(n) * series._wave(W, np.add))
+    return order.wave(num, np.add) / (np.float64(n) * order.wave(W, np.add))
 
 
 def vortdiv_reference(u, v, g):
@@ -291,31 +290,15 @@ def solve_grid(grid, radius, u, v, device=0):
 
 
 # ------------------------------------------------------------------------------------- environment
-def _int(env, name, default):
-    try:
-        return int(env.get(name, str(default)))
-    except (TypeError, ValueError):
-        return default
-
-
 def read_env(env):
     """-> dict: enabled (QD_FLOW, default 0), every (QD_FLOW_EVERY, default 24: ten samples per planet-day at the default 300 s step;
     unparsable or < 1 -> 24), every_days (QD_FLOW_EVERY_DAYS, default 10; unparsable or <= 0 -> 10)."""
-    every = _int(env, "QD_FLOW_EVERY", EVERY)
-    if every < 1:
-        every = EVERY
-    try:
-        days = float(env.get("QD_FLOW_EVERY_DAYS", str(EVERY_DAYS)))
-    except (TypeError, ValueError):
-        days = EVERY_DAYS
-    if not (days > 0.0) or not math.isfinite(days):
-        days = EVERY_DAYS
-    return {"enabled": _int(env, "QD_FLOW", 0) == 1, "every": every, "every_days": days}
+    return {"enabled": env_int(env, "QD_FLOW", 0) == 1, "every": env_every(env, "QD_FLOW_EVERY", EVERY),
+            "every_days": env_days(env, "QD_FLOW_EVERY_DAYS", EVERY_DAYS)}
 
 
 def file_name(a_days, b_days, decimals=1):
-    w = decimals + 3
-    return f"flow_day_{a_days:0{w}.{decimals}f}_{b_days:0{w}.{decimals}f}.nc"
+    return window_file_name("flow", a_days, b_days, decimals)
 
 
 def window_variables(recs, times, steps, lat, lon, dt, every, complete, sums, count):
@@ -325,7 +308,7 @@ def window_variables(recs, times, steps, lat, lon, dt, every, complete, sums, co
     recs = np.asarray(recs, dtype=np.float64).reshape(-1, REC_W)
     n = len(recs)
     v = {"time_seconds": ("f8", ("time",), np.asarray(times, dtype=np.float64).reshape(n)),
-         "step": (series._i8(), ("time",), np.asarray(steps, dtype=np.int64).reshape(n)),
+         "step": (i8_code(), ("time",), np.asarray(steps, dtype=np.int64).reshape(n)),
          "lat": ("f8", ("lat",), lat), "lon": ("f8", ("lon",), lon)}
     with np.errstate(invalid="ignore", divide="ignore"):
         for q, name in enumerate(PLANES):
@@ -338,84 +321,27 @@ def window_variables(recs, times, steps, lat, lon, dt, every, complete, sums, co
     return {"time": n, "lat": int(lat.size), "lon": int(lon.size)}, v
 
 
-class Flow:
-    """The lane's participant in Device.step_n (like Spectra): the run-local step index is its clock, span_schedule uploads the
-    span's sample flags, span_deliver drains the span's records into the open window, flush() writes the window's file."""
+class Flow(LogWindowLane):
+    """The lane's participant in Device.step_n (like Spectra): the clock and the span protocol are window_lane's, flush() writes the
+    window's file.  drop() forgets the delivered records, _pending, and on the device the log, the sums and their sample count."""
+    NAME, TAG = "flow", "Flow"
 
     def __init__(self, dev, grid, cfg, dt=300.0, day=None, out=print, output_dir=None):
-        self.dev, self.grid, self.cfg, self.out = dev, grid, dict(cfg), out
-        self.dt = float(dt)
-        self.day = float(2.0 * np.pi / dev.params.omega) if day is None else float(day)
-        self.S = history.steps_per_window(cfg["every_days"], self.day, self.dt)
-        self.every = int(cfg["every"])
-        self.decimals = history.label_decimals(self.S * self.dt / self.day)
-        self.output_dir = output_dir
+        super().__init__(dev, grid, cfg, out, dt, day, cfg["every_days"], cfg["every"], REC_W, output_dir)
         self.lat = np.asarray(grid.lat, dtype=np.float64).reshape(-1)
         self.lon = np.asarray(grid.lon, dtype=np.float64).reshape(-1)
-        self.width = REC_W
         self.tables = grid_tables(grid, dev.params.a)
-        self.i = 0                                   # run-local index of the next step
-        self._pending = []                           # (times, steps) of spans that ran and whose records are still in the device log
-        self.recs, self.times, self.steps = [], [], []
-        self.files = []
         dev.flow_configure(self.tables)
 
-    # -- the span protocol of Device.step_n
-    def span_clock(self):
-        return (self.i, len(self._pending))
+    def key(self):
+        """The lane's part of a checkpoint's subsystem set."""
+        return f"every={int(self.every)}"
 
-    def span_restore(self, clock):
-        self.i = clock[0]
-        del self._pending[clock[1]:]
+    def _upload(self, flags):
+        self.dev.flow_schedule(flags)
 
-    def span_schedule(self, t0, dt, n):
-        flags = history.schedule(self.i, n, self.S, self.every)
-        self.dev.flow_schedule(flags)                # (more than QD_FLOW_LOG_CAP samples between two drains: qd_step_n refuses the span)
-        if t0 is None:
-            times = (self.i + np.arange(int(n))) * float(dt)
-        elif np.ndim(t0) == 0:
-            times = float(t0) + float(dt) * np.arange(int(n))
-        else:
-            times = np.asarray(t0, dtype=np.float64)
-        hit = np.flatnonzero(flags)
-        return (int(n), np.asarray(times, dtype=np.float64)[hit].copy(), (self.i + hit).astype(np.int64))
-
-    def _fired(self, k):
-        n, times, steps = k
-        self.i += n
-        if len(times):
-            self._pending.append((times, steps))
-
-    def span_deliver(self, dt):
-        """Drain the device log into the open window -> the records [n][REC_W] that came."""
-        want = sum(len(t) for t, _ in self._pending)
-        if want == 0:
-            return np.empty((0, self.width))
-        recs = self.dev.flow_log(want)
-        if len(recs) != want:
-            raise RuntimeError(f"Flow: the device log held {len(recs)} records where the schedule says {want}")
-        self.recs.append(recs)
-        for t, s in self._pending:
-            self.times.append(t)
-            self.steps.append(s)
-        self._pending = []
-        return recs
-
-    # -- windows
-    def steps_to_window_end(self, i=None):
-        """Steps from step i (default: the next step) up to and including its window's last step."""
-        i = self.i if i is None else int(i)
-        return self.S - (i % self.S)
-
-    def window_closed(self):
-        """The last step that ran was a window's last step."""
-        return self.i > 0 and self.i % self.S == 0
-
-    def window(self):
-        """The open window as delivered so far -> (recs [n][REC_W], times [n], steps [n])."""
-        if not self.recs:
-            return np.empty((0, self.width)), np.empty(0), np.empty(0, dtype=np.int64)
-        return np.concatenate(self.recs), np.concatenate(self.times), np.concatenate(self.steps)
+    def _drain(self, want):
+        return self.dev.flow_log(want)
 
     def sums(self):
         """The sum planes as they stand on the device -> (sums [4][n_lat][n_lon], count)."""
@@ -423,48 +349,25 @@ class Flow:
 
     def restore_window(self, recs, times, steps, i, sums=None, count=0):
         """The inverse of window(), sums() and the clock, for an exact resume (checkpoint.py)."""
-        self.drop()
-        recs = np.asarray(recs, dtype=np.float64).reshape(-1, self.width)
-        if len(recs):
-            self.recs, self.times = [recs.copy()], [np.asarray(times, dtype=np.float64).reshape(-1).copy()]
-            self.steps = [np.asarray(steps).reshape(-1).astype(np.int64)]
-        self.i = int(i)
+        super().restore_window(recs, times, steps, i)
         if sums is not None:
             self.dev.flow_sums_set(sums, int(count))
 
-    def path(self, a_days, b_days):
-        out = self.output_dir if self.output_dir is not None else os.environ.get("QD_OUTPUT_DIR", "output")
-        return os.path.join(out, "flow", file_name(a_days, b_days, self.decimals))
-
-    def flush(self, complete=1):
-        """Write the open window's file, print one line, start the next window -> the path, or None when it holds no record."""
+    def _window_file(self, complete):
         recs, times, steps = self.window()
         if len(recs) == 0:
             return None
         sums, count = self.sums()
         a, b = float(times[0]) / self.day, float(times[-1]) / self.day
-        path = self.path(a, b)
         dims, variables = window_variables(recs, times, steps, self.lat, self.lon, self.dt, self.every, complete, sums, count)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        tmp = path + ".part"
-        try:
-            ncio.write_nc(tmp, dims, variables)
-            os.replace(tmp, path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
         d, k = self.decimals, {name: q for q, name in enumerate(REC)}
-        self.out(f"[Flow] day {a:.{d}f}–{b:.{d}f}: {len(recs)} samples | vort rms={recs[0, k['vort_rms']]:.6g}→{recs[-1, k['vort_rms']]:.6g} "
-                 f"div rms={recs[0, k['div_rms']]:.6g}→{recs[-1, k['div_rms']]:.6g} KE={recs[-1, k['ke']]:.6g} "
-                 f"rot={recs[-1, k['ke_rot']]:.6g} div={recs[-1, k['ke_div']]:.6g} bad={int(recs[:, k['bad_rows']].sum())}")
-        self.drop()
-        self.files.append(path)
-        return path
+        line = (f"[Flow] day {a:.{d}f}–{b:.{d}f}: {len(recs)} samples | vort rms={recs[0, k['vort_rms']]:.6g}→{recs[-1, k['vort_rms']]:.6g} "
+                f"div rms={recs[0, k['div_rms']]:.6g}→{recs[-1, k['div_rms']]:.6g} KE={recs[-1, k['ke']]:.6g} "
+                f"rot={recs[-1, k['ke_rot']]:.6g} div={recs[-1, k['ke_div']]:.6g} bad={int(recs[:, k['bad_rows']].sum())}")
+        return a, b, dims, variables, line
 
     def drop(self):
-        """Forget the open window: the delivered records, and on the device the log, the sums and their sample count; the next
-        sample starts the next file."""
-        self.recs, self.times, self.steps = [], [], []
+        super().drop()
         self._pending = []
         self.dev.flow_reset()
 
@@ -474,6 +377,4 @@ def from_env(dev, grid, env, dt=None, day=None, out=print):
     cfg = read_env(env)
     if not cfg["enabled"]:
         return None
-    if dt is None:
-        dt = float(env.get("QD_DT_SECONDS", "300"))
-    return Flow(dev, grid, cfg, dt=dt, day=day, out=out)
+    return Flow(dev, grid, cfg, dt=env_dt(env, dt), day=day, out=out)

@@ -25,12 +25,12 @@ from __future__ import annotations
 
 import functools
 import math
-import os
 
 import numpy as np
 
-from . import history, ncio, series
+from . import history, order, series
 from ._lib import SPECTRA_STATS
+from .window_lane import LogWindowLane, env_days, env_dt, env_every, env_int, i8_code, window_file_name
 
 FIELDS_VAR = "QD_SPECTRA_FIELDS"
 DEFAULT_FIELDS = ("U", "V", "H", "Q", "CLOUD")     # what the hyperdiffusion acts on
@@ -151,13 +151,13 @@ def combine_reference(P_rows, lat):
         raise ValueError("combine_reference: P_rows is [n_lat][n_bins], lat holds one latitude per row")
     with np.errstate(invalid="ignore", over="ignore"):
         prod = (w[:, None] * P).T                                             # [bin][row]
-        rows_p = series._lanes(prod, 64, 0.0)                                 # [bin][round][lane]
-        rows_w = series._lanes(w, 64, 0.0)                                    # [round][lane]
+        rows_p = order.lanes(prod, 64, 0.0)                                 # [bin][round][lane]
+        rows_w = order.lanes(w, 64, 0.0)                                    # [round][lane]
         num, W = np.zeros((P.shape[1], 64)), np.zeros(64)
         for k in range(rows_w.shape[0]):
             num = num + rows_p[:, k, :]
             W = W + rows_w[k]
-        return series._wave(num, np.add) / series._wave(W, np.add)
+        return order.wave(num, np.add) / order.wave(W, np.add)
 
 
 def hi_frac(P):
@@ -184,30 +184,15 @@ def split_records(recs, n_entries, n_lon):
 
 
 # ------------------------------------------------------------------------------------- environment
-def _int(env, name, default):
-    try:
-        return int(env.get(name, str(default)))
-    except (TypeError, ValueError):
-        return default
-
-
 def read_env(env):
     """-> dict: enabled (QD_SPECTRA, default 0), every (QD_SPECTRA_EVERY, default 24: ten samples per planet-day at the default
     300 s step; unparsable or < 1 -> 24), lat (QD_SPECTRA_LAT, default 1), every_days (QD_SPECTRA_EVERY_DAYS, default 10;
     unparsable or <= 0 -> 10), fields (QD_SPECTRA_FIELDS through history's parser, or None = U,V,H,Q,CLOUD)."""
-    enabled = _int(env, "QD_SPECTRA", 0) == 1
-    every = _int(env, "QD_SPECTRA_EVERY", EVERY)
-    if every < 1:
-        every = EVERY
-    try:
-        days = float(env.get("QD_SPECTRA_EVERY_DAYS", str(EVERY_DAYS)))
-    except (TypeError, ValueError):
-        days = EVERY_DAYS
-    if not (days > 0.0) or not math.isfinite(days):
-        days = EVERY_DAYS
+    enabled = env_int(env, "QD_SPECTRA", 0) == 1
     text = env.get(FIELDS_VAR)
     fields = history.parse_fields(text, var=FIELDS_VAR) if (enabled and text is not None and str(text).strip()) else None
-    return {"enabled": enabled, "every": every, "lat": _int(env, "QD_SPECTRA_LAT", LAT) != 0, "every_days": days, "fields": fields}
+    return {"enabled": enabled, "every": env_every(env, "QD_SPECTRA_EVERY", EVERY), "lat": env_int(env, "QD_SPECTRA_LAT", LAT) != 0,
+            "every_days": env_days(env, "QD_SPECTRA_EVERY_DAYS", EVERY_DAYS), "fields": fields}
 
 
 def resolve_fields(fields, with_ocean):
@@ -218,8 +203,7 @@ def resolve_fields(fields, with_ocean):
 
 
 def file_name(a_days, b_days, decimals=1):
-    w = decimals + 3
-    return f"spectra_day_{a_days:0{w}.{decimals}f}_{b_days:0{w}.{decimals}f}.nc"
+    return window_file_name("spectra", a_days, b_days, decimals)
 
 
 def window_variables(names, recs, times, steps, lat, n_lon, dt, every, complete, sums=None, count=0):
@@ -229,7 +213,7 @@ def window_variables(names, recs, times, steps, lat, n_lon, dt, every, complete,
     n, nb = int(np.shape(recs)[0]), n_bins(n_lon)
     power, bad = split_records(recs, len(names), n_lon)
     v = {"time_seconds": ("f8", ("time",), np.asarray(times, dtype=np.float64).reshape(n)),
-         "step": (series._i8(), ("time",), np.asarray(steps, dtype=np.int64).reshape(n)),
+         "step": (i8_code(), ("time",), np.asarray(steps, dtype=np.int64).reshape(n)),
          "wavenumber": ("f8", ("k",), np.arange(nb, dtype=np.float64)),
          "lat": ("f8", ("lat",), lat)}
     for q, name in enumerate(names):
@@ -247,85 +231,28 @@ def window_variables(names, recs, times, steps, lat, n_lon, dt, every, complete,
     return {"time": n, "k": nb, "lat": int(lat.size)}, v
 
 
-class Spectra:
-    """The lane's participant in Device.step_n (like Series): the run-local step index is its clock, span_schedule uploads the
-    span's sample flags, span_deliver drains the span's records into the open window, flush() writes the window's file."""
+class Spectra(LogWindowLane):
+    """The lane's participant in Device.step_n (like Series): the clock and the span protocol are window_lane's, flush() writes the
+    window's file.  drop() forgets the delivered records, _pending, and on the device the log, the sums and their sample count."""
+    NAME, TAG = "spectra", "Spectra"
 
     def __init__(self, dev, grid, cfg, with_ocean=True, dt=300.0, day=None, out=print, output_dir=None):
-        self.dev, self.grid, self.cfg, self.out = dev, grid, dict(cfg), out
-        self.dt = float(dt)
-        self.day = float(2.0 * np.pi / dev.params.omega) if day is None else float(day)
         self.names = resolve_fields(cfg.get("fields"), with_ocean)
-        self.S = history.steps_per_window(cfg["every_days"], self.day, self.dt)
-        self.every = int(cfg["every"])
         self.lat_resolved = bool(cfg["lat"])
-        self.decimals = history.label_decimals(self.S * self.dt / self.day)
-        self.output_dir = output_dir
         self.lat = np.asarray(grid.lat, dtype=np.float64).reshape(-1)
         self.n_lon = int(np.asarray(grid.lon).size)
-        self.width = record_width(len(self.names), self.n_lon)
-        self.i = 0                                   # run-local index of the next step
-        self._pending = []                           # (times, steps) of spans that ran and whose records are still in the device log
-        self.recs, self.times, self.steps = [], [], []
-        self.files = []
+        super().__init__(dev, grid, cfg, out, dt, day, cfg["every_days"], cfg["every"], record_width(len(self.names), self.n_lon), output_dir)
         dev.spectra_configure(history.entries_for(self.names), self.lat_resolved, series.row_weights(self.lat))
 
-    # -- the span protocol of Device.step_n
-    def span_clock(self):
-        return (self.i, len(self._pending))
+    def key(self):
+        """The lane's part of a checkpoint's subsystem set."""
+        return f"{','.join(self.names)}|every={int(self.every)}|lat={int(self.lat_resolved)}"
 
-    def span_restore(self, clock):
-        self.i = clock[0]
-        del self._pending[clock[1]:]
+    def _upload(self, flags):
+        self.dev.spectra_schedule(flags)
 
-    def span_schedule(self, t0, dt, n):
-        flags = history.schedule(self.i, n, self.S, self.every)
-        self.dev.spectra_schedule(flags)             # (more than QD_SPECTRA_LOG_CAP samples between two drains: qd_step_n refuses the span)
-        if t0 is None:
-            times = (self.i + np.arange(int(n))) * float(dt)
-        elif np.ndim(t0) == 0:
-            times = float(t0) + float(dt) * np.arange(int(n))
-        else:
-            times = np.asarray(t0, dtype=np.float64)
-        hit = np.flatnonzero(flags)
-        return (int(n), np.asarray(times, dtype=np.float64)[hit].copy(), (self.i + hit).astype(np.int64))
-
-    def _fired(self, k):
-        n, times, steps = k
-        self.i += n
-        if len(times):
-            self._pending.append((times, steps))
-
-    def span_deliver(self, dt):
-        """Drain the device log into the open window -> the records [n][width] that came."""
-        want = sum(len(t) for t, _ in self._pending)
-        if want == 0:
-            return np.empty((0, self.width))
-        recs = self.dev.spectra_log(want)
-        if len(recs) != want:
-            raise RuntimeError(f"Spectra: the device log held {len(recs)} records where the schedule says {want}")
-        self.recs.append(recs)
-        for t, s in self._pending:
-            self.times.append(t)
-            self.steps.append(s)
-        self._pending = []
-        return recs
-
-    # -- windows
-    def steps_to_window_end(self, i=None):
-        """Steps from step i (default: the next step) up to and including its window's last step."""
-        i = self.i if i is None else int(i)
-        return self.S - (i % self.S)
-
-    def window_closed(self):
-        """The last step that ran was a window's last step."""
-        return self.i > 0 and self.i % self.S == 0
-
-    def window(self):
-        """The open window as delivered so far -> (recs [n][width], times [n], steps [n])."""
-        if not self.recs:
-            return np.empty((0, self.width)), np.empty(0), np.empty(0, dtype=np.int64)
-        return np.concatenate(self.recs), np.concatenate(self.times), np.concatenate(self.steps)
+    def _drain(self, want):
+        return self.dev.spectra_log(want)
 
     def sums(self):
         """The lat-resolved sum planes as they stand on the device -> (sums [n_entries][n_lat][n_bins], count), or (None, 0)."""
@@ -333,50 +260,27 @@ class Spectra:
 
     def restore_window(self, recs, times, steps, i, sums=None, count=0):
         """The inverse of window(), sums() and the clock, for an exact resume (checkpoint.py)."""
-        self.drop()
-        recs = np.asarray(recs, dtype=np.float64).reshape(-1, self.width)
-        if len(recs):
-            self.recs, self.times = [recs.copy()], [np.asarray(times, dtype=np.float64).reshape(-1).copy()]
-            self.steps = [np.asarray(steps).reshape(-1).astype(np.int64)]
-        self.i = int(i)
+        super().restore_window(recs, times, steps, i)
         if self.lat_resolved and sums is not None:
             self.dev.spectra_sums_set(sums, int(count))
 
-    def path(self, a_days, b_days):
-        out = self.output_dir if self.output_dir is not None else os.environ.get("QD_OUTPUT_DIR", "output")
-        return os.path.join(out, "spectra", file_name(a_days, b_days, self.decimals))
-
-    def flush(self, complete=1):
-        """Write the open window's file, print one line, start the next window -> the path, or None when it holds no record."""
+    def _window_file(self, complete):
         recs, times, steps = self.window()
         if len(recs) == 0:
             return None
         sums, count = self.sums()
         a, b = float(times[0]) / self.day, float(times[-1]) / self.day
-        path = self.path(a, b)
         dims, variables = window_variables(self.names, recs, times, steps, self.lat, self.n_lon, self.dt, self.every, complete,
                                            sums=sums, count=count)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        tmp = path + ".part"
-        try:
-            ncio.write_nc(tmp, dims, variables)
-            os.replace(tmp, path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
         d = self.decimals
         power, _ = split_records(recs, len(self.names), self.n_lon)
         hf = hi_frac(power)                                                   # [time][entry]
-        self.out(f"[Spectra] day {a:.{d}f}–{b:.{d}f}: {len(recs)} samples | " +
-                 " ".join(f"{n} hi={hf[0, k]:.6g}→{hf[-1, k]:.6g}" for k, n in list(enumerate(self.names))[:6]))
-        self.drop()
-        self.files.append(path)
-        return path
+        line = (f"[Spectra] day {a:.{d}f}–{b:.{d}f}: {len(recs)} samples | " +
+                " ".join(f"{n} hi={hf[0, k]:.6g}→{hf[-1, k]:.6g}" for k, n in list(enumerate(self.names))[:6]))
+        return a, b, dims, variables, line
 
     def drop(self):
-        """Forget the open window: the delivered records, and on the device the log, the sums and their sample count; the next
-        sample starts the next file."""
-        self.recs, self.times, self.steps = [], [], []
+        super().drop()
         self._pending = []
         self.dev.spectra_reset()
 
@@ -386,6 +290,4 @@ def from_env(dev, grid, env, with_ocean=True, dt=None, day=None, out=print):
     cfg = read_env(env)
     if not cfg["enabled"]:
         return None
-    if dt is None:
-        dt = float(env.get("QD_DT_SECONDS", "300"))
-    return Spectra(dev, grid, cfg, with_ocean=with_ocean, dt=dt, day=day, out=out)
+    return Spectra(dev, grid, cfg, with_ocean=with_ocean, dt=env_dt(env, dt), day=day, out=out)

@@ -37,14 +37,13 @@ spectra lane: <QD_OUTPUT_DIR, default output>/spharm/spharm_day_{a}_{b}.nc.  Not
 from __future__ import annotations
 
 import functools
-import math
-import os
 import types
 
 import numpy as np
 
-from . import flow, history, ncio, series
+from . import flow, history, order
 from ._lib import C
+from .window_lane import LogWindowLane, env_days, env_dt, env_every, env_int, i8_code, window_file_name
 
 FIELDS_VAR = "QD_SPHARM_FIELDS"
 DEFAULT_FIELDS = ("VORT", "DIV", "H")
@@ -246,11 +245,11 @@ def power_reference(coef, plane=None, g=None):
         x = np.ascontiguousarray(plane, dtype=np.float64)
         bad = ~np.isfinite(x).all(axis=1)
         msrow = np.where(bad, np.nan, flow._row_sums(x * x) / np.float64(g.n_lon))
-        rows = series._lanes(g.w * msrow, 64, 0.0)
+        rows = order.lanes(g.w * msrow, 64, 0.0)
         acc = np.zeros(64)
         for k in range(rows.shape[0]):
             acc = acc + rows[k]
-        return P, 0.5 * float(series._wave(acc, np.add)), int(bad.sum())
+        return P, 0.5 * float(order.wave(acc, np.add)), int(bad.sum())
 
 
 def resid(P, ms):
@@ -310,13 +309,6 @@ def analyse_grid(n_lat, n_lon, plane, device=0):
 
 
 # ------------------------------------------------------------------------------------- environment
-def _int(env, name, default):
-    try:
-        return int(env.get(name, str(default)))
-    except (TypeError, ValueError):
-        return default
-
-
 def parse_fields(text):
     """QD_SPHARM_FIELDS -> upper-cased names, in order: history's names and VORT, DIV; an unknown name, or more than 32, raises a
     ValueError that names it."""
@@ -333,19 +325,11 @@ def read_env(env):
     """-> dict: enabled (QD_SPHARM, default 0), every (QD_SPHARM_EVERY, default 24; unparsable or < 1 -> 24), two_d (QD_SPHARM_2D,
     default 1), every_days (QD_SPHARM_EVERY_DAYS, default 10; unparsable or <= 0 -> 10), fields (QD_SPHARM_FIELDS parsed, or None =
     VORT,DIV,H)."""
-    enabled = _int(env, "QD_SPHARM", 0) == 1
-    every = _int(env, "QD_SPHARM_EVERY", EVERY)
-    if every < 1:
-        every = EVERY
-    try:
-        days = float(env.get("QD_SPHARM_EVERY_DAYS", str(EVERY_DAYS)))
-    except (TypeError, ValueError):
-        days = EVERY_DAYS
-    if not (days > 0.0) or not math.isfinite(days):
-        days = EVERY_DAYS
+    enabled = env_int(env, "QD_SPHARM", 0) == 1
     text = env.get(FIELDS_VAR)
     fields = parse_fields(text) if (enabled and text is not None and str(text).strip()) else None
-    return {"enabled": enabled, "every": every, "two_d": _int(env, "QD_SPHARM_2D", TWO_D) != 0, "every_days": days, "fields": fields}
+    return {"enabled": enabled, "every": env_every(env, "QD_SPHARM_EVERY", EVERY), "two_d": env_int(env, "QD_SPHARM_2D", TWO_D) != 0,
+            "every_days": env_days(env, "QD_SPHARM_EVERY_DAYS", EVERY_DAYS), "fields": fields}
 
 
 def resolve_fields(fields, with_ocean):
@@ -364,8 +348,7 @@ def entries_for(names):
 
 
 def file_name(a_days, b_days, decimals=1):
-    w = decimals + 3
-    return f"spharm_day_{a_days:0{w}.{decimals}f}_{b_days:0{w}.{decimals}f}.nc"
+    return window_file_name("spharm", a_days, b_days, decimals)
 
 
 def window_variables(names, recs, times, steps, N, dt, every, complete, radius, sums=None, count=0):
@@ -375,7 +358,7 @@ def window_variables(names, recs, times, steps, N, dt, every, complete, radius, 
     n = int(np.shape(recs)[0])
     power, ms, bad = split_records(recs, len(names), N)
     v = {"time_seconds": ("f8", ("time",), np.asarray(times, dtype=np.float64).reshape(n)),
-         "step": (series._i8(), ("time",), np.asarray(steps, dtype=np.int64).reshape(n)),
+         "step": (i8_code(), ("time",), np.asarray(steps, dtype=np.int64).reshape(n)),
          "degree": ("f8", ("n",), np.arange(N + 1, dtype=np.float64))}
     for q, name in enumerate(names):
         low = name.lower()
@@ -395,28 +378,18 @@ def window_variables(names, recs, times, steps, N, dt, every, complete, radius, 
     return {"time": n, "n": N + 1, "m": N + 1}, v
 
 
-class Spharm:
-    """The lane's participant in Device.step_n (like Spectra): the run-local step index is its clock, span_schedule uploads the
-    span's sample flags, span_deliver drains the span's records into the open window, flush() writes the window's file."""
+class Spharm(LogWindowLane):
+    """The lane's participant in Device.step_n (like Spectra): the clock and the span protocol are window_lane's, flush() writes the
+    window's file.  drop() forgets the delivered records, _pending, and on the device the log, the sums and their sample count."""
+    NAME, TAG = "spharm", "SphSpec"
 
     def __init__(self, dev, grid, cfg, with_ocean=True, dt=300.0, day=None, out=print, output_dir=None):
-        self.dev, self.grid, self.cfg, self.out = dev, grid, dict(cfg), out
-        self.dt = float(dt)
-        self.day = float(2.0 * np.pi / dev.params.omega) if day is None else float(day)
         self.names = resolve_fields(cfg.get("fields"), with_ocean)
-        self.S = history.steps_per_window(cfg["every_days"], self.day, self.dt)
-        self.every = int(cfg["every"])
         self.two_d = bool(cfg["two_d"])
-        self.decimals = history.label_decimals(self.S * self.dt / self.day)
-        self.output_dir = output_dir
         self.tables = grid_tables(grid)                  # (a grid with N < 1 is refused here)
         self.N = self.tables.N
         self.radius = float(dev.params.a)
-        self.width = record_width(len(self.names), self.N)
-        self.i = 0                                   # run-local index of the next step
-        self._pending = []                           # (times, steps) of spans that ran and whose records are still in the device log
-        self.recs, self.times, self.steps = [], [], []
-        self.files = []
+        super().__init__(dev, grid, cfg, out, dt, day, cfg["every_days"], cfg["every"], record_width(len(self.names), self.N), output_dir)
         needs_flow = any(n in OWN for n in self.names)
         dev.spharm_configure(entries_for(self.names), self.two_d, self.tables,
                              flow.grid_tables(grid, dev.params.a) if needs_flow else None)
@@ -425,62 +398,11 @@ class Spharm:
         """What a checkpoint's subsystem set says of this lane."""
         return f"{','.join(self.names)}|every={self.every}|2d={int(self.two_d)}"
 
-    # -- the span protocol of Device.step_n
-    def span_clock(self):
-        return (self.i, len(self._pending))
+    def _upload(self, flags):
+        self.dev.spharm_schedule(flags)
 
-    def span_restore(self, clock):
-        self.i = clock[0]
-        del self._pending[clock[1]:]
-
-    def span_schedule(self, t0, dt, n):
-        flags = history.schedule(self.i, n, self.S, self.every)
-        self.dev.spharm_schedule(flags)              # (more than QD_SPHARM_LOG_CAP samples between two drains: qd_step_n refuses the span)
-        if t0 is None:
-            times = (self.i + np.arange(int(n))) * float(dt)
-        elif np.ndim(t0) == 0:
-            times = float(t0) + float(dt) * np.arange(int(n))
-        else:
-            times = np.asarray(t0, dtype=np.float64)
-        hit = np.flatnonzero(flags)
-        return (int(n), np.asarray(times, dtype=np.float64)[hit].copy(), (self.i + hit).astype(np.int64))
-
-    def _fired(self, k):
-        n, times, steps = k
-        self.i += n
-        if len(times):
-            self._pending.append((times, steps))
-
-    def span_deliver(self, dt):
-        """Drain the device log into the open window -> the records [n][width] that came."""
-        want = sum(len(t) for t, _ in self._pending)
-        if want == 0:
-            return np.empty((0, self.width))
-        recs = self.dev.spharm_log(want)
-        if len(recs) != want:
-            raise RuntimeError(f"Spharm: the device log held {len(recs)} records where the schedule says {want}")
-        self.recs.append(recs)
-        for t, s in self._pending:
-            self.times.append(t)
-            self.steps.append(s)
-        self._pending = []
-        return recs
-
-    # -- windows
-    def steps_to_window_end(self, i=None):
-        """Steps from step i (default: the next step) up to and including its window's last step."""
-        i = self.i if i is None else int(i)
-        return self.S - (i % self.S)
-
-    def window_closed(self):
-        """The last step that ran was a window's last step."""
-        return self.i > 0 and self.i % self.S == 0
-
-    def window(self):
-        """The open window as delivered so far -> (recs [n][width], times [n], steps [n])."""
-        if not self.recs:
-            return np.empty((0, self.width)), np.empty(0), np.empty(0, dtype=np.int64)
-        return np.concatenate(self.recs), np.concatenate(self.times), np.concatenate(self.steps)
+    def _drain(self, want):
+        return self.dev.spharm_log(want)
 
     def sums(self):
         """The 2D sum planes as they stand on the device -> (sums [n_entries][N + 1 (n)][N + 1 (m)], count), or (None, 0)."""
@@ -488,37 +410,18 @@ class Spharm:
 
     def restore_window(self, recs, times, steps, i, sums=None, count=0):
         """The inverse of window(), sums() and the clock, for an exact resume (checkpoint.py)."""
-        self.drop()
-        recs = np.asarray(recs, dtype=np.float64).reshape(-1, self.width)
-        if len(recs):
-            self.recs, self.times = [recs.copy()], [np.asarray(times, dtype=np.float64).reshape(-1).copy()]
-            self.steps = [np.asarray(steps).reshape(-1).astype(np.int64)]
-        self.i = int(i)
+        super().restore_window(recs, times, steps, i)
         if self.two_d and sums is not None:
             self.dev.spharm_sums_set(sums, int(count))
 
-    def path(self, a_days, b_days):
-        out = self.output_dir if self.output_dir is not None else os.environ.get("QD_OUTPUT_DIR", "output")
-        return os.path.join(out, "spharm", file_name(a_days, b_days, self.decimals))
-
-    def flush(self, complete=1):
-        """Write the open window's file, print one line, start the next window -> the path, or None when it holds no record."""
+    def _window_file(self, complete):
         recs, times, steps = self.window()
         if len(recs) == 0:
             return None
         sums, count = self.sums()
         a, b = float(times[0]) / self.day, float(times[-1]) / self.day
-        path = self.path(a, b)
         dims, variables = window_variables(self.names, recs, times, steps, self.N, self.dt, self.every, complete, self.radius,
                                            sums=sums, count=count)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        tmp = path + ".part"
-        try:
-            ncio.write_nc(tmp, dims, variables)
-            os.replace(tmp, path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
         d = self.decimals
         parts = []
         if "ke_slope" in variables:
@@ -527,15 +430,10 @@ class Spharm:
         for n in self.names[:6]:
             r = variables[f"{n.lower()}_resid"][2]
             parts.append(f"{n} resid={r[0]:.6g}→{r[-1]:.6g}")
-        self.out(f"[SphSpec] day {a:.{d}f}–{b:.{d}f}: {len(recs)} samples | " + " ".join(parts))
-        self.drop()
-        self.files.append(path)
-        return path
+        return a, b, dims, variables, f"[SphSpec] day {a:.{d}f}–{b:.{d}f}: {len(recs)} samples | " + " ".join(parts)
 
     def drop(self):
-        """Forget the open window: the delivered records, and on the device the log, the sums and their sample count; the next
-        sample starts the next file."""
-        self.recs, self.times, self.steps = [], [], []
+        super().drop()
         self._pending = []
         self.dev.spharm_reset()
 
@@ -545,6 +443,4 @@ def from_env(dev, grid, env, with_ocean=True, dt=None, day=None, out=print):
     cfg = read_env(env)
     if not cfg["enabled"]:
         return None
-    if dt is None:
-        dt = float(env.get("QD_DT_SECONDS", "300"))
-    return Spharm(dev, grid, cfg, with_ocean=with_ocean, dt=dt, day=day, out=out)
+    return Spharm(dev, grid, cfg, with_ocean=with_ocean, dt=env_dt(env, dt), day=day, out=out)
